@@ -9,7 +9,9 @@ configuration: TRBA (TPS+ResNet+BiLSTM+Attn) x 6 experts.
     python bench.py --gpus 1 --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the K steps and prints the headline; --full adds
+everything else (kernel timer and roofline, detail / isolated passes, power probe, CPU baseline, comm telemetry, extra lines,
+bench_detail.json).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import contextlib
@@ -20,6 +22,7 @@ import sys
 import time
 import types
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -405,9 +408,9 @@ def time_loop_a(args, opt, rank, world, steps, warmup, with_cpu_baseline=False):
     for _ in range(warmup):
         learner.train_step(*data.get_batch())
     reducer = getattr(learner, "reducer", None)
-    if reducer is not None:
+    if args.full and reducer is not None:
         reducer.record, reducer.exposed = True, []
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         ops.CONV_TIMER = ops.KernelTimer()
     parallel.barrier()
     torch.cuda.synchronize()
@@ -436,7 +439,7 @@ def time_loop_a(args, opt, rank, world, steps, warmup, with_cpu_baseline=False):
             res["roofline"]["measured"] = "timed region, HIP events per launch on the launch stream; rate over the union of the launch intervals"
             if len(rl) > 1 or hbm:
                 res["roofline_other_kernels"] = rl[1:4] + hbm
-    if world > 1:
+    if args.full and world > 1:
         res["comm"] = comm_telemetry(reducer, world, learner.device, elapsed / steps * 1e3)
         res["comm"]["side_stream_parameters_per_step"] = side_params      # parameter gradients accumulated on the second stream (as at N = 1)
     if with_cpu_baseline and world == 1 and rank == 0:
@@ -664,6 +667,25 @@ def emit(res):
     print(compact_line(res, rel), flush=True)
 
 
+DUMP_ARRAY_LIMIT = 32 << 20        # bytes per dumped array: larger ones keep a fixed, seeded sample of their leading-axis rows
+DUMP_TOTAL_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  An array above DUMP_ARRAY_LIMIT keeps the rows (entries of its
+    first axis) drawn by numpy's default_rng(0), in ascending order: the same rows for the same shape, run after run."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_ARRAY_LIMIT:
+            k = max(1, DUMP_ARRAY_LIMIT // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))]
+        total += a.nbytes
+        assert total <= DUMP_TOTAL_LIMIT, (name, total)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher (how the driver calls it): run the same command line under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` as a child
@@ -710,7 +732,15 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="do not append the short loop-A measurement under \"extra\"")
     ap.add_argument("--no-power-probe", action="store_true", help="skip the live zero-operand probe of the dominant layer shape")
     ap.add_argument("--no-reduced", action="store_true", help="skip the short reduced-precision lines (extra.fp16_loop_b / extra.fp16_der)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: kernel timer + roofline (detail, isolated and power-probe "
+                    "passes), CPU baseline, comm telemetry (N > 1), extra lines, bench_detail.json; the --no-* switches above trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (losses, fused logits, "
+                    "routing weights, updated router parameters) as DIR/<name>.npy, float32, at most 64 MB (loop B only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.loop != "b":
+        ap.error("--dump-outputs covers the default loop B only")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # The driver's bare `python bench.py --gpus N ...`: start one rank per GPU as CHILD processes (never exec: nothing in this
@@ -740,7 +770,7 @@ def main():
     opt = make_opt(args.model, args.batch)
     if args.loop in ("a", "der", "lwf", "ewc"):
         fn = {"a": time_loop_a, "der": time_der_step, "lwf": time_il_step, "ewc": time_il_step}[args.loop]
-        kw = {"with_cpu_baseline": not args.no_cpu_baseline} if args.loop == "a" else {}
+        kw = {"with_cpu_baseline": args.full and not args.no_cpu_baseline} if args.loop == "a" else {}
         res = fn(args, opt, rank, world, args.steps, args.warmup, **kw)
         if rank == 0:
             what = {"a": f"MRN loop A: one {args.model.upper()} expert trained",
@@ -749,7 +779,10 @@ def main():
             res.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
                         "config": {"workload": f"{what} on 32x256x4 crops, random-init weights",
                                    "per_gpu_batch": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}"}})
-            emit(res)
+            if args.full:
+                emit(res)
+            else:
+                print(compact_line(res), flush=True)
         parallel.barrier()
         return
     learner = build_learner(opt, args.experts, quiet=not args.verbose)
@@ -780,25 +813,33 @@ def main():
     for _ in range(args.warmup):
         step()
     reducer = getattr(learner, "reducer", None)
-    if reducer is not None:
+    if args.full and reducer is not None:
         reducer.record, reducer.exposed = True, []
     sites = None
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         # the timed region brackets the DOMINANT kernel's launches only (site "wino": the Winograd convolutions of the TRBA / CRNN experts:
         # 26 launches a step); HIP events around every timed launch cost ~0.9 ms of an 84 ms step (A/B, round 5).  The other kernels'
         # figures of the detail file come from a short pass of its own behind the timed region.  SVTR has no such site: every launch.
         only = os.environ.get("MRN_TIMER_ONLY")
         sites = set(only.split(",")) if only else ({"wino"} if (args.model in ("trba", "crnn") and not args.timer_all) else None)
         ops.CONV_TIMER = ops.KernelTimer(sites)
+    last = {}
     parallel.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:     # keep the model output of the last timed step
+            hook = learner.model.register_forward_hook(lambda mod, inp, out: last.update(out))
         loss_clf, loss_t = step()
     host_elapsed = time.perf_counter() - t0          # time the host needed to ISSUE the timed steps (it runs ahead of the GPU)
     torch.cuda.synchronize()
     parallel.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        hook.remove()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loss_clf": loss_clf, "loss_taski": loss_t, "logits": last["logits"],
+                                             "routing_weights": last["index"], "router_parameters": learner.optimizer.flat})
     timer = ops.CONV_TIMER
     ops.CONV_TIMER = None
     timer_steps, timer_elapsed = args.steps, elapsed
@@ -806,7 +847,7 @@ def main():
         timer = None
     # detail pass (outside the timed region, every rank): the same pipelined steps with events around EVERY timed launch
     detail = None
-    if not args.no_kernel_timer and sites is not None:
+    if args.full and not args.no_kernel_timer and sites is not None:
         ops.CONV_TIMER = ops.KernelTimer()
         torch.cuda.synchronize()
         td = time.perf_counter()
@@ -840,7 +881,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    comm = comm_telemetry(reducer, world, dev, elapsed / args.steps * 1e3) if world > 1 else None
+    comm = comm_telemetry(reducer, world, dev, elapsed / args.steps * 1e3) if (args.full and world > 1) else None
     # live power probe of the dominant layer shape (rank 0, TRBA x3 mode only: the shape is TRBA's)
     probe = None
     if rank == 0 and timer is not None and not args.no_power_probe and args.model == "trba" and ops.X3_PRODUCTS == 3 \
@@ -898,11 +939,11 @@ def main():
                 res["roofline_other_kernels"] = rl[1:] + hbm
         if comm is not None:
             res["comm"] = comm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(learner, opt, args.experts)
     extra = None
     reduced = {}
-    if not args.no_extra:                  # (every rank: loop A's train_step holds the gradient all-reduce)
+    if args.full and not args.no_extra:    # (every rank: loop A's train_step holds the gradient all-reduce)
         del learner
         pending.clear()
         torch.cuda.empty_cache()
@@ -937,7 +978,10 @@ def main():
         if extra is not None:
             res["extra"] = {"loop_a": extra}
             res["extra"].update(reduced)
-        emit(res)
+        if args.full:
+            emit(res)
+        else:
+            print(compact_line(res), flush=True)
     parallel.barrier()
 
 

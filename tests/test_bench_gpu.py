@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def _detail(d):
 
 def test_bench_single_process_line():
     _fresh_process_only()
-    r = subprocess.run([sys.executable, "bench.py", "--model", "crnn", "--experts", "3", "--batch", "32", "--steps", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--model", "crnn", "--experts", "3", "--batch", "32", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _the_line(r.stdout)
@@ -54,12 +55,31 @@ def test_bench_single_process_line():
     assert full["value"] == pytest.approx(d["value"], rel=1e-4) and "measured" in full["roofline"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """without --full: the headline fields only, --steps timed steps, and --dump-outputs writes the last timed step's losses, fused
+    logits, routing weights and router parameters as float32 .npy files"""
+    _fresh_process_only()
+    r = subprocess.run([sys.executable, "bench.py", "--model", "crnn", "--experts", "3", "--batch", "32", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _the_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(32e3 / d["ms_per_step"], rel=1e-3)
+    for k in ("roofline", "cpu_baseline", "extra", "comm", "detail"):
+        assert k not in d, k
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss_clf", "loss_taski", "logits", "routing_weights", "router_parameters")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["logits"].ndim == 3 and got["logits"].shape[0] == 32 and got["routing_weights"].shape == (32, 3)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+
+
 def test_bench_default_command_line_is_compact_and_complete():
-    """the driver's command (default workload: TRBA x 6, batch 256, every extra line, the CPU baseline leg), shortened only in
+    """the --full command (default workload: TRBA x 6, batch 256, every extra line, the CPU baseline leg), shortened only in
     --steps / --warmup: ONE parseable line under 4 KB carrying roofline.frac and cpu_baseline.value (the 20 KB line
     of round 5 did not parse and voided the round's measurement)"""
     _fresh_process_only()
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _the_line(r.stdout)
     for k in FIELDS + ("cpu_baseline", "extra", "detail"):
@@ -83,7 +103,7 @@ def test_bench_two_ranks_control_flow():
     # the DRIVER's command: bare `python bench.py --gpus 2 ...`, no launcher -- bench.py starts its own ranks as child processes
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MRN_DIST_BACKEND="gloo", MRN_SHARE_DEVICE="1")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--model", "crnn", "--experts", "3", "--batch", "16", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--model", "crnn", "--experts", "3", "--batch", "16", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)     # (a timeout FAILS the test)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _the_line(r.stdout)                 # rank 0 prints exactly one line

@@ -453,6 +453,24 @@ def test_bench_compact_line_is_bounded_and_strict_json():
     assert len(line) < bench.LINE_LIMIT and "extra" not in d and d["roofline"]["frac"] == 0.3 and d["cpu_baseline"]["value"] == 14.0
 
 
+def test_bench_dump_outputs_samples_large_arrays_the_same_way(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files; an array above the per-array limit keeps the same seeded sample of its
+    rows in every run, whole rows in ascending order; small arrays and scalars are written whole"""
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(300 * 8 * 4096, dtype=torch.float64).view(300, 8, 4096)       # 75 MB in float64, 37.5 MB in float32
+    arrays = {"big": big, "small": torch.ones(5, 3, dtype=torch.float16), "loss": torch.tensor(2.5)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and np.array_equal(a, b) and a.nbytes <= bench.DUMP_ARRAY_LIMIT and 0 < a.shape[0] < 300
+    rows = a[:, 0, 0] / (8 * 4096)
+    assert np.array_equal(rows, np.round(rows)) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a, big.float().numpy()[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.ones((5, 3), np.float32))
+    assert np.load(tmp_path / "a" / "loss.npy") == np.float32(2.5)
+
+
 def test_reduced_mode_winograd_eligibility():
     """host logic of the reduced-precision mode's Winograd form (no kernel is launched): which layers take the plain-fp16 (d16) operands"""
     from mrn_amd import ops
