@@ -637,6 +637,28 @@ int mrn_sgd_step_f32(float* p, float* g, float* buf, int64_t n, const float* nor
 int mrn_adadelta_step_f32(float* p, float* g, float* square_avg, float* acc_delta, int64_t n, const float* norm_coef, float lr,
                           float rho, float eps, void* stream);
 
+/* ---- training-time text augmentation (data/dataset.py:249-290: Text_augment, Aug = Blur / Crop / Rot tokens) ---------------
+ * Ragged batches of RGBA uint8 crops, bit-exact with Pillow (the reference's PIL / torchvision 0.10.1 chain): `pixels` is ONE
+ * device buffer of n_pixels RGBA dwords (n_pixels < 2^31) holding the sources and every stage's output; `desc` is int32 [B][8]
+ * per sample with offsets / strides in pixels, planned on the host (mrn_amd/data/augment.py; crops are window changes there).
+ * Compiled-in limit MRN_AUG_MAX_SIDE = 4096 on every side of every window; a call whose max_* lies outside 1..4096 returns an
+ * error, and a sample whose window leaves the buffer or the limit is skipped (never read or written). */
+/* GaussianBlur(radius) (data/dataset.py:199-209, under RandomApply p=0.5): Pillow's 3 extended-box passes along x then y.
+ * desc {src_off, src_stride, w, h, dst_off, box_radius, ww, fw}: box_radius = int part of the box radius, ww / fw its 24-bit
+ * inner / edge weights (BoxBlur.c); box_radius < 0: sample not blurred.  dst stride = w.  max_w / max_h: largest w / h. */
+int mrn_aug_gaussian_blur_rgba_u8(void* pixels, int64_t n_pixels, const int* desc, int B, int max_w, int max_h, void* stream);
+/* RandomRotation(D, BICUBIC, expand=True, fill=0) (torchvision 0.10.1 transforms.py, PIL Image.rotate): desc {src_off, src_stride,
+ * w, h, dst_off, out_w, out_h, mode}, mode 0 = none (angle 0), 1 = inverse affine with Geometry.c's bicubic on premultiplied RGBa
+ * (matrix: 6 doubles per sample, as Image.rotate computes them), 2 / 3 / 4 = exact 180 / 90 / 270 degrees.  dst stride = out_w. */
+int mrn_aug_rotate_bicubic_rgba_u8(void* pixels, int64_t n_pixels, const int* desc, const void* matrix, int B,
+                                   int max_out_w, int max_out_h, void* stream);
+/* transforms.Resize((H, W), BICUBIC) + ToTensor + sub_(0.5).div_(0.5) (data/dataset.py:277-288; same bits as ResizeNormalize,
+ * :235-246): desc {src_off, src_stride, w, h, tmp_off, mode, 0, 0}, mode 0 = same size (copy), 1 = horizontal, 2 = vertical,
+ * 3 = horizontal then vertical (tmp: W x h RGBa), 4 = vertical then horizontal (taller than 100x wide; tmp: w x H).
+ * out: fp32 [N][4][out_h][out_w] contiguous, sample b written to row row0 + b. */
+int mrn_aug_resize_normalize_rgba_u8_f32(void* pixels, int64_t n_pixels, const int* desc, int B, int max_w, int max_h,
+                                         float* out, int row0, int out_h, int out_w, void* stream);
+
 /* ---- data-parallel collectives over RCCL / xGMI ------------------------------------------------------------------
  * Replace the per-iteration replicate / scatter / gather / reduce of torch.nn.DataParallel (il_modules/base.py:68,
  * il_modules/mrn.py:106,133) for one-process-per-GPU hosts: rank 0 calls mrn_comm_unique_id (HOST buffer of

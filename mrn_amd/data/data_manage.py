@@ -6,14 +6,18 @@ same numpy / torch seeds (pinned against the reference's own classes by tests/go
 
 MI355X-first addition: batches are staged to the GPU ahead of use -- collated into pinned host memory, copied on a side
 HIP stream while the previous step computes, handed to the learner as device tensors (33.5 MB per 256-crop batch; the
-reference's `image_tensors.to(device)` on pageable memory serialises behind the whole step).
+reference's `image_tensors.to(device)` on pageable memory serialises behind the whole step).  With a GPU stager and an Aug string
+of Blur / Crop / Rot tokens, the training loaders' workers only decode and draw: the augmentation runs on the side stream
+(mrn_amd/data/augment.py, augment.hip) and yields the host path's batches bit for bit.
 """
 import bisect
 
+import numpy as np
 import numpy.random
 import torch
 from torch.utils.data import ConcatDataset, DataLoader, Subset
 
+from . import augment as A
 from .dataset import AlignCollate, AlignCollate2, hierarchical_dataset, open_leaf
 
 REPEAT_UP_TO = 50000          # "for faster training, we multiply small datasets itself" (data_manage.py:137-141)
@@ -33,6 +37,70 @@ class IndexConcatDataset(ConcatDataset):
         return self.datasets[dataset_idx][sample_idx], dataset_idx
 
 
+class DeferredCollate(object):
+    """train-mode collate of AlignCollate / AlignCollate2 with Text_augment deferred to the GPU: decoding (the dataset), the random
+    draws (same order as the host path, so both consume identical RNG streams) and the planning run in the worker, which returns an
+    augment.RaggedBatch instead of the image tensor.  A batch with a sample outside the kernels' limits (a side of 0 or above
+    augment.MAX_SIDE, or a non-RGBA image) is produced by the host path here, with the same draws and bits."""
+
+    _noticed = False
+
+    def __init__(self, opt, with_index=False):
+        self.opt, self.with_index = opt, with_index
+        self.stages = A.parse_aug(opt.Aug)
+        self.host = A.TextAugment(opt)
+
+    def _images(self, images):
+        size = (self.opt.imgW, self.opt.imgH)
+        if any(im.mode != "RGBA" for im in images):
+            return torch.stack([self.host(im) for im in images], 0)
+        rb, draws = A.plan_batch(images, self.stages, size)
+        if rb is not None:
+            return rb
+        if not DeferredCollate._noticed:
+            DeferredCollate._noticed = True
+            print(f"[Dataset_Manager] a batch holds a crop outside the augmentation kernels' limits (sides 1..{A.MAX_SIDE}): "
+                  "such batches are augmented on the host")
+        return torch.stack([A.apply_host(im, self.stages, d, size) for im, d in zip(images, draws)], 0)
+
+    def __call__(self, batch):
+        if self.with_index:
+            b_info, index = zip(*batch)
+            images, labels = zip(*b_info)
+            return self._images(images), labels, index
+        images, labels = zip(*batch)
+        return self._images(images), labels
+
+
+class PinnedByteRing:
+    """grow-only pinned byte buffers for ragged batches (their size changes every batch; reallocating pinned memory per batch costs
+    more than the copy, see DeviceStager._pinned).  A slot is handed out again only after the event recorded behind the last
+    kernel that read its upload."""
+
+    RING = 3
+
+    def __init__(self):
+        self._slots, self._turn = [], 0
+
+    def take(self, nbytes):
+        if len(self._slots) < self.RING:
+            self._slots.append([None, None])
+            slot = self._slots[-1]
+        else:
+            slot = self._slots[self._turn % self.RING]
+            self._turn += 1
+            if slot[1] is not None:
+                slot[1].synchronize()
+                slot[1] = None
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(nbytes, nbytes * 5 // 4, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return slot
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
 class DeviceStager:
     """keeps ONE batch in flight to the GPU: pinned host copy -> async H2D on a side stream -> event the consumer stream waits on"""
 
@@ -42,6 +110,7 @@ class DeviceStager:
         self.device = device
         self.stream = torch.cuda.Stream(device=device) if device.type == "cuda" else None
         self._ring, self._turn = [], 0
+        self._bytes = PinnedByteRing()
 
     def _pinned(self, like):
         """a reusable pinned buffer of `like`'s shape whose previous copy has completed (allocating pinned memory per batch costs
@@ -69,6 +138,53 @@ class DeviceStager:
             done.record(self.stream)
         slot[1] = done
         return dev, (done, slot[0])
+
+    def upload_parts(self, parts, size):
+        """a batch made of loader parts, each an augment.RaggedBatch (augmented here on the side stream) or a dense host tensor, into
+        one [N, 4, H, W] device tensor: one pinned slot, its bytes copied up, the kernels, one event"""
+        from .. import ops
+        W, H = size
+        layout, off = [], 0
+        for p in parts:
+            if isinstance(p, A.RaggedBatch):
+                sec = (off, p.pool.nbytes, _align(p.pool.nbytes) + _align(p.desc.nbytes), p.desc.nbytes, p.matrix.nbytes)
+                off += _align(sec[2] + p.matrix.nbytes)
+            else:
+                sec = (off, p.numel() * 4)
+                off += _align(sec[1])
+            layout.append(sec)
+        slot = self._bytes.take(off)
+        host = slot[0]
+        for p, sec in zip(parts, layout):
+            if isinstance(p, A.RaggedBatch):
+                o = sec[0]
+                host[o:o + sec[1]].numpy()[:] = p.pool
+                host[o + _align(sec[1]):o + _align(sec[1]) + sec[3]].numpy()[:] = p.desc.view(np.uint8).reshape(-1)
+                host[o + sec[2]:o + sec[2] + sec[4]].numpy()[:] = p.matrix.view(np.uint8).reshape(-1)
+            else:
+                host[sec[0]:sec[0] + sec[1]].view(torch.float32).view(p.shape).copy_(p)
+        n = sum(len(p) if isinstance(p, A.RaggedBatch) else p.shape[0] for p in parts)
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((n, 4, H, W), dtype=torch.float32, device=self.device)
+            row = 0
+            for p, sec in zip(parts, layout):
+                if isinstance(p, A.RaggedBatch):
+                    o, meta = sec[0], sec[0] + _align(sec[1])
+                    pixels = torch.empty(p.total * 4, dtype=torch.uint8, device=self.device)
+                    pixels[:sec[1]].copy_(host[o:o + sec[1]], non_blocking=True)
+                    dmeta = host[meta:o + sec[2] + sec[4]].to(self.device, non_blocking=True)
+                    desc = dmeta[:sec[3]].view(torch.int32).view(p.desc.shape)
+                    k = o + sec[2] - meta
+                    matrix = dmeta[k:k + sec[4]].view(torch.float64).view(p.matrix.shape)
+                    ops.augment_batch(pixels, p, desc, matrix, out, row)
+                    row += len(p)
+                else:
+                    out[row:row + p.shape[0]].copy_(host[sec[0]:sec[0] + sec[1]].view(torch.float32).view(p.shape), non_blocking=True)
+                    row += p.shape[0]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        slot[1] = done
+        return out, (done, host)
 
     def ready(self, dev, ticket):
         if ticket is not None:
@@ -196,11 +312,14 @@ class Dataset_Manager(object):
         self.data_loader_list.append(loader)
         self.dataloader_iter_list.append(iter(loader))
 
+    def _device_augment(self):
+        return self.stager.stream is not None and A.uses_text_augment(self.opt)
+
     def create_dataloader(self, dataset, batch_size=None):
-        self._loader(dataset, batch_size, AlignCollate(self.opt))
+        self._loader(dataset, batch_size, DeferredCollate(self.opt) if self._device_augment() else AlignCollate(self.opt))
 
     def create_dataloader_mix(self, dataset, batch_size=None):
-        self._loader(dataset, batch_size, AlignCollate2(self.opt))
+        self._loader(dataset, batch_size, DeferredCollate(self.opt, True) if self._device_augment() else AlignCollate2(self.opt))
 
     # -- batches (reference :174-217) ----------------------------------------------------------------------------------
     def _next(self, i):
@@ -221,17 +340,24 @@ class Dataset_Manager(object):
             labels += got[1]
             if with_index:
                 index.append(got[2])
+        if any(isinstance(p, A.RaggedBatch) for p in images):
+            return images, labels, index          # deferred augmentation: the parts go to DeviceStager.upload_parts
         return (images[0] if len(images) == 1 else torch.cat(images, 0)), labels, index
+
+    def _upload(self, images):
+        if isinstance(images, list):
+            return self.stager.upload_parts(images, (self.opt.imgW, self.opt.imgH))
+        return self.stager.upload(images)
 
     def _staged_batch(self, with_index):
         """the batch prepared by the previous call (already on its way to the GPU) + start the next one"""
         key = "mix" if with_index else "plain"
         if self._staged is None or self._staged[0] != key:
             images, labels, index = self._host_batch(with_index)
-            self._staged = (key, self.stager.upload(images), labels, index)
+            self._staged = (key, self._upload(images), labels, index)
         _, (dev, ticket), labels, index = self._staged
         nxt = self._host_batch(with_index)
-        self._staged = (key, self.stager.upload(nxt[0]), nxt[1], nxt[2])
+        self._staged = (key, self._upload(nxt[0]), nxt[1], nxt[2])
         return self.stager.ready(dev, ticket), labels, index
 
     def get_batch(self):

@@ -10,9 +10,11 @@ Same on-disk format, classes, constructor arguments and tensor contract as the r
                         pipelines use, and the in-memory stand-in when LMDB is not installed;
   * NpzDataset       -- a directory holding `data.npz` (`images`: object array of encoded image bytes or uint8 arrays,
                         `labels`): the portable sibling of an LMDB leaf directory;
-  * ResizeNormalize / AlignCollate / AlignCollate2 / hierarchical_dataset -- as in the reference (no torchvision needed).
+  * ResizeNormalize / AlignCollate / AlignCollate2 / hierarchical_dataset -- as in the reference (no torchvision needed);
+  * training-time augmentation: Aug strings of Blur / Crop / Rot tokens (the reference's Text_augment, :249-290) through
+    mrn_amd/data/augment.py -- on the host with PIL here, on the GPU inside Dataset_Manager (same bits).
 
-The reference's augmentation classes (cv2-based, data/transform.py) are out of scope: every shipped config sets Aug="None".
+Out of scope: Aug="ABINet" (cv2-based CVGeometry / CVDeterioration / CVColorJitter, data/transform.py) and MoCo_augment.
 """
 import io
 import os
@@ -22,6 +24,8 @@ import numpy as np
 import PIL.Image
 import torch
 from torch.utils.data import ConcatDataset, Dataset
+
+from .augment import TextAugment
 
 
 def _open_rgba(buf_or_array, opt):
@@ -149,8 +153,11 @@ class AlignCollate(object):
         self.opt, self.mode = opt, mode
         if getattr(opt, "Aug", "None") == "None" or mode != "train":
             self.transform = ResizeNormalize((opt.imgW, opt.imgH))
+        elif opt.Aug == "ABINet":
+            raise NotImplementedError("Aug='ABINet' needs cv2 (CVGeometry / CVDeterioration / CVColorJitter, reference data/transform.py), "
+                                      "which is out of scope; Blur / Crop / Rot tokens (e.g. 'Blur5-Crop90-Rot15') are supported")
         else:
-            raise NotImplementedError(f"Aug='{opt.Aug}': the cv2-based augmentations are out of scope (every shipped config uses 'None')")
+            self.transform = TextAugment(opt)
 
     def __call__(self, batch):
         images, labels = zip(*batch)

@@ -2449,3 +2449,51 @@ def weight_align_(weight, increment):
     gamma = torch.empty(1, device=weight.device, dtype=torch.float32)
     call("mrn_weight_align_f32", _p(weight), weight.stride(0), rows, rows - increment, C, _p(ws), _p(gamma), _stream())
     return gamma
+
+
+# -- training-time text augmentation (mrn_amd/data/augment.py plans, augment.hip runs) ------------------------------------------
+def _chk_aug(pixels, *ts):
+    if not pixels.is_cuda or pixels.dtype != torch.uint8 or not pixels.is_contiguous():
+        raise RuntimeError("augmentation kernels need a contiguous uint8 CUDA (HIP) pixel buffer; there is no CPU fallback")
+    for t in ts:
+        if not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError("augmentation descriptors must be contiguous CUDA (HIP) tensors")
+
+
+def aug_gaussian_blur(pixels, desc, max_w, max_h):
+    """PIL GaussianBlur of every sample whose descriptor radius is >= 0 (desc: int32 [B, 8], see include/mrn_hip.h)"""
+    _chk_aug(pixels, desc)
+    call("mrn_aug_gaussian_blur_rgba_u8", _p(pixels), pixels.numel() // 4, _p(desc), desc.shape[0], int(max_w), int(max_h), _stream())
+
+
+def aug_rotate(pixels, desc, matrix, max_out_w, max_out_h):
+    """PIL rotate(angle, BICUBIC, expand=True, fillcolor=0) (desc: int32 [B, 8], matrix: float64 [B, 6])"""
+    _chk_aug(pixels, desc, matrix)
+    assert matrix.dtype == torch.float64
+    call("mrn_aug_rotate_bicubic_rgba_u8", _p(pixels), pixels.numel() // 4, _p(desc), _p(matrix), desc.shape[0], int(max_out_w),
+         int(max_out_h), _stream())
+
+
+def aug_resize_normalize(pixels, desc, max_w, max_h, out, row0=0):
+    """PIL resize((W, H), BICUBIC) + ToTensor + (x - 0.5) / 0.5 into out[row0 : row0 + B] (out: fp32 [N, 4, H, W] contiguous)"""
+    _chk_aug(pixels, desc)
+    _chk(out)
+    assert out.is_contiguous() and out.dim() == 4 and out.shape[1] == 4 and row0 + desc.shape[0] <= out.shape[0]
+    call("mrn_aug_resize_normalize_rgba_u8_f32", _p(pixels), pixels.numel() // 4, _p(desc), desc.shape[0], int(max_w), int(max_h),
+         _p(out), int(row0), out.shape[2], out.shape[3], _stream())
+
+
+def augment_batch(pixels, rb, desc, matrix, out, row0=0):
+    """the whole chain of a RaggedBatch (mrn_amd/data/augment.py) on the current stream: pixels = uint8 device buffer of rb.total
+    RGBA pixels whose start holds rb.pool; desc / matrix = device copies of rb.desc / rb.matrix; result in out[row0 : row0 + B]"""
+    ri = 0
+    for si, kind in enumerate(rb.kinds):
+        mw, mh, ow, oh = rb.maxima[si]
+        if kind == "blur":
+            aug_gaussian_blur(pixels, desc[si], mw, mh)
+        else:
+            aug_rotate(pixels, desc[si], matrix[ri], ow, oh)
+            ri += 1
+    mw, mh = rb.maxima[-1][:2]
+    aug_resize_normalize(pixels, desc[len(rb.kinds)], mw, mh, out, row0)
+    return out
