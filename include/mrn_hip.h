@@ -258,6 +258,13 @@ int mrn_bn_apply_grouped_f32(const float* y, const float* residual, const void* 
 int mrn_maxpool_grouped_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32,
                             void* out_hl32, int G, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                             void* stream);
+/* Height mean at the end of the visual stage: permute(0,3,1,2) + AdaptiveAvgPool2d((None, 1)) + squeeze(3), reference
+ * modules/model.py:92, for feature maps of height H > 1 (imgH 48 / 64).  x [G][B][H][W][C] -> mean over H of
+ * relu?(x * scale[g] + shift[g]) as out_f32 [G][B][W][C] and / or the HL32 operand (out_hl32, C % 32 == 0); scale / shift [G][C]
+ * or NULL; the rows are summed in order in fp32 and divided by H.  mrn_height_mean_bwd_f32: dx [B][H][W][C] = dy [B][W][C] / H. */
+int mrn_height_mean_grouped_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32,
+                                void* out_hl32, int G, int B, int H, int W, int C, void* stream);
+int mrn_height_mean_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, void* stream);
 
 /* Convolution backward (loss.backward() through Conv2d, il_modules/mrn.py:260-261):
  *   data gradient  = mrn_conv2d_nhwc_* of dy (zero-dilated by the stride, mrn_dilate_nhwc_f32) with the flipped /

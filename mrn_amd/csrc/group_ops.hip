@@ -561,7 +561,114 @@ __global__ __launch_bounds__(256) void add_layernorm_grouped_kernel(const float*
   }
 }
 
+// The height reduction that ends the visual stage for inputs taller than 32 pixels: out[g][b][w][c] = mean over h of
+// act(x[g][b][h][w][c] * scale[g][c] + shift[g][c]).  One lane = 8 channels of one (b, w) column; consecutive lanes walk the channels,
+// so every row h is a coalesced read of the column's C channels.  The H rows are summed in order in fp32 and the sum is divided by H,
+// as torch's adaptive_avg_pool2d does.  blockIdx.y = group.
+__global__ __launch_bounds__(256) void height_mean_grouped_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, float* __restrict__ out,
+                                                                  unsigned char* __restrict__ out_hl, int relu, int B, int H, int W,
+                                                                  int C) {
+  const int C8 = C >> 3;
+  const long n8 = (long)B * W * C8;                  // lanes of one group
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= n8) return;
+  const int g = blockIdx.y;
+  const int c8 = (int)(i % C8);
+  const long bw = i / C8;                            // b * W + w
+  const long b = bw / W;
+  const int w = (int)(bw - b * W);
+  F8 sc, sf;
+  if (scale) {
+    sc = load8(scale + (long)g * C + c8 * 8);
+    sf = load8(shift + (long)g * C + c8 * 8);
+  }
+  const float* src = x + ((((long)g * B + b) * H * W + w) * C8 + c8) * 8;
+  const long step = (long)W * C;
+  F8 s;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) s.a[e] = s.b[e] = 0.f;
+  for (int h = 0; h < H; ++h) {
+    F8 v = load8(src + h * step);
+    if (scale) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v.a[e] = v.a[e] * sc.a[e] + sf.a[e];
+        v.b[e] = v.b[e] * sc.b[e] + sf.b[e];
+      }
+    }
+    if (relu) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v.a[e] = relu_nan(v.a[e]);
+        v.b[e] = relu_nan(v.b[e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s.a[e] += v.a[e];
+      s.b[e] += v.b[e];
+    }
+  }
+  const float fh = (float)H;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    s.a[e] = s.a[e] / fh;
+    s.b[e] = s.b[e] / fh;
+  }
+  const long row = (long)g * B * W + bw;
+  if (out) store8(out + row * C + c8 * 8, s);
+  if (out_hl) store_hl(out_hl, row, C, c8, s);
+}
+
+// its gradient: dx[b][h][w][c] = dy[b][w][c] / H; one lane = 4 channels of one output pixel (16-byte load and store)
+__global__ __launch_bounds__(256) void height_mean_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, long n4, int H,
+                                                              int W, int C4) {
+  const float fh = (float)H;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const int c4 = (int)(i % C4);
+    const long p = i / C4;                           // (b * H + h) * W + w
+    const int w = (int)(p % W);
+    const long b = p / ((long)W * H);
+    f32x4 v = reinterpret_cast<const f32x4*>(dy)[(b * W + w) * C4 + c4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] / fh;
+    reinterpret_cast<f32x4*>(dx)[i] = v;
+  }
+}
+
 }  // namespace
+
+// permute(0,3,1,2) + AdaptiveAvgPool2d((None, 1)) + squeeze(3) at the end of the visual stage (reference modules/model.py:92) for
+// feature maps of height H > 1 (imgH 48 / 64): x [G][B][H][W][C] fp32 -> mean over H of act(x * scale[g] + shift[g]) as out_f32
+// [G][B][W][C] and / or the HL32 operand of the next grouped Linear (out_hl32, C % 32 == 0).  scale / shift [G][C] or NULL (a train- or
+// eval-mode BatchNorm of the final convolution applied in the same pass over its raw output); relu 0 / 1.  G = 1: one network.
+MRN_EXPORT int mrn_height_mean_grouped_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32,
+                                           void* out_hl32, int G, int B, int H, int W, int C, void* stream) {
+  MRN_CHECK_ARG(x && (out_f32 || out_hl32) && C > 0 && C % 8 == 0 && (!out_hl32 || C % 32 == 0) && (!scale == !shift) && G >= 1 &&
+                    H >= 1 && W >= 1 && B >= 0 && G <= 65535,
+                "mrn_height_mean_grouped_f32: bad operands (G=%d H=%d W=%d C=%d)", G, H, W, C);
+  const long n8 = (long)B * W * (C / 8);
+  if (n8 == 0) return MRN_OK;
+  hipLaunchKernelGGL(height_mean_grouped_kernel, dim3((unsigned)((n8 + 255) / 256), G), dim3(256), 0, (hipStream_t)stream, x, scale,
+                     shift, out_f32, (unsigned char*)out_hl32, relu, B, H, W, C);
+  MRN_LAUNCH_CHECK("height_mean_grouped");
+  return MRN_OK;
+}
+
+// backward of mrn_height_mean_grouped_f32 without the affine (what autograd sees of modules/model.py:92): dy [B][W][C] -> dx [B][H][W][C]
+// = dy / H broadcast over the rows; C % 4 == 0
+MRN_EXPORT int mrn_height_mean_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, void* stream) {
+  MRN_CHECK_ARG(dy && dx && C > 0 && C % 4 == 0 && H >= 1 && W >= 1 && B >= 0, "mrn_height_mean_bwd_f32: bad operands (H=%d W=%d C=%d)",
+                H, W, C);
+  const long n4 = (long)B * H * W * (C / 4);
+  if (n4 == 0) return MRN_OK;
+  long grid = (n4 + 255) / 256;
+  if (grid > 32768) grid = 32768;
+  hipLaunchKernelGGL(height_mean_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dy, dx, n4, H, W, C / 4);
+  MRN_LAUNCH_CHECK("height_mean_bwd");
+  return MRN_OK;
+}
 
 // Train-mode BatchNorm2d statistics for G BatchNorm modules of C channels at once.  partials: [G][nblk][2][C] from the
 // grouped conv epilogue; ptrs: device table [4][G] of device pointers {gamma, beta, running_mean, running_var} (entries

@@ -750,6 +750,20 @@ class AvgPoolFn(torch.autograd.Function):
         return ops.avgpool_bwd(dy, H * W).view(B, H, W, C)
 
 
+class HeightMeanFn(torch.autograd.Function):
+    """permute(0,3,1,2) + AdaptiveAvgPool2d((None, 1)) + squeeze(3) of the visual stage (reference modules/model.py:92) on NHWC:
+    [B,H,W,C] -> [B,W,C], the mean over H"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.H = x.shape[1]
+        return ops.height_mean(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.height_mean_bwd(dy, ctx.H)
+
+
 class TPSSampleFn(torch.autograd.Function):
     """grid generation + bilinear sampling; gradient flows to the fiducials C' only (the image is an input)."""
 

@@ -20,6 +20,7 @@ import torch
 
 from .. import ops
 from ._nn import _pair, packed_weight, require_no_grad, to_nhwc
+from .geometry import geometry_supported, unsupported_geometry_message
 
 
 EVAL_BN_FOLD = os.environ.get("MRN_EVAL_BN_FOLD", "1") != "0"      # eval-mode BatchNorm folded into the conv epilogue (A/B switch)
@@ -29,6 +30,11 @@ SVTR_GROUPED_EMBED = os.environ.get("MRN_SVTR_EMBED", "grouped") == "grouped"   
 TPS_WINO = os.environ.get("MRN_TPS_WINO", "1") == "1"          # TPS localisation network: convs 3 and 4 on the Winograd form
 EVAL_WINO = os.environ.get("MRN_EVAL_WINO", "1") != "0"
 RESIDUAL_FROM_F32 = bool(int(os.environ.get("MRN_RESIDUAL_F32", "0")))      # True: keep an fp32 copy of every identity-shortcut source (one extra 4 B/element write)
+
+
+def conv_out_rows(H, pool):
+    """rows of a layer's result: its conv output's H, or the pooled map's when a max-pool follows"""
+    return H if pool is None else ops.conv_out_hw(H, 1, pool[0], pool[1], pool[2])[0]
 
 
 class Act:
@@ -108,6 +114,7 @@ class BackboneGroup(_GroupedLinear):
         self._wcache = {}
         self._bncache = {}
         self._nbt = []
+        self._height_mean = False
 
     # ---- caches ------------------------------------------------------------------------------------------------
     def _weights_hl(self, convs):
@@ -127,12 +134,14 @@ class BackboneGroup(_GroupedLinear):
         return got[1]
 
     @staticmethod
-    def wino_for(conv, bns):
+    def wino_for(conv, bns, H=None):
         """R of the Winograd form this conv would run in when its input arrives as a Winograd-domain operand, else 0: 3x3 / stride 1
-        / pad 1, wide enough, and NOT followed by an eval-mode BatchNorm (that fold keeps its one-launch direct form)"""
+        / pad 1, wide enough, and NOT followed by an eval-mode BatchNorm (that fold keeps its one-launch direct form); H: rows of its
+        input map when known (the reduced mode's plain-fp16 form takes 4-row blocks only)"""
         if bns is not None and not bns[0].training and not EVAL_WINO:
             return 0
-        ok = ops.wino_eligible(_pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding), conv.in_channels, conv.out_channels)
+        ok = ops.wino_eligible(_pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding), conv.in_channels, conv.out_channels,
+                               H=H)
         return ops.WINO_R if ok else 0
 
     def _bn_table(self, bns):
@@ -151,10 +160,13 @@ class BackboneGroup(_GroupedLinear):
         return torch.stack([c.bias.detach() for c in convs]).contiguous()
 
     # ---- one conv (+BN) (+residual) (+ReLU) (+pool) layer for all groups ----------------------------------------------
-    def layer(self, x, convs, bns=None, relu=True, residual=None, pool=None, want_f32=False, want_hl=True, want_wino=0, gelu=False):
+    def layer(self, x, convs, bns=None, relu=True, residual=None, pool=None, want_f32=False, want_hl=True, want_wino=0, gelu=False,
+              height_mean=False):
         """want_wino = R: the result also as the Winograd-domain operand of a following 3x3 conv (only from the BatchNorm-apply
         pass, i.e. with bns and no pool); a layer whose INPUT carries x.wino and qualifies (wino_for) runs as F(R,3).
-        gelu: BatchNorm -> GELU instead of ReLU (SVTR PatchEmbed; plain BatchNorm-apply pass only)"""
+        gelu: BatchNorm -> GELU instead of ReLU (SVTR PatchEmbed; plain BatchNorm-apply pass only).
+        height_mean: the last layer of the visual stage -- a map of more than one row leaves as its mean over the rows (reference
+        modules/model.py:92), taken by the pass that applies the BatchNorm + ReLU to the raw conv output: a [G,B,1,W,C] Act"""
         if gelu:
             assert bns is not None and bns[0].training and pool is None and not want_wino and residual is None
             relu = True
@@ -171,13 +183,18 @@ class BackboneGroup(_GroupedLinear):
         stats = None
         res = residual.f32 if residual is not None else None
         res_hl = residual.hl if residual is not None and res is None else None
-        use_wino = x.wino is not None and x.wino_R == self.wino_for(c0, bns)
+        use_wino = x.wino is not None and x.wino_R == self.wino_for(c0, bns, H)
+        if want_wino and not ops.wino_rows_fit(conv_out_rows(Ho, pool)):
+            want_wino, want_hl = 0, True             # (the consumer runs on the plain operand: a 6-row map in the reduced mode, imgH = 48)
+        height_mean = height_mean and Ho > 1 and self._height_mean
+        if height_mean:
+            assert pool is None and residual is None and not want_wino and not gelu
         # (an eval-mode layer with a 2x2 / 2 pool behind it that the patch-resident kernel takes runs there too: the pool in the conv
         #  epilogue and the running-statistics affine on the pooled map beat the one-launch fold + a pooling pass over the full map)
         patch_pool = (pool == ((2, 2), (2, 2), (0, 0)) and Ho % 2 == 0 and Wo % 2 == 0
                       and ops.patch_conv_supported(ksize, stride, padding, Cin, Cout))
         if (EVAL_BN_FOLD and bns is not None and not training and Cin % 32 == 0 and Cout >= 64 and Cout % 32 == 0
-                and (want_hl or res_hl is None) and not use_wino and not want_wino and not patch_pool):
+                and (want_hl or res_hl is None) and not use_wino and not want_wino and not patch_pool and not height_mean):
             # frozen experts in EVAL mode (DERNet's old extractors, LwF's previous network, validation): the BatchNorm is a fixed
             # per-channel affine, so conv -> BN -> (+ identity) -> ReLU -> operand split is ONE launch: the affine, the shortcut
             # and the activation run in the conv epilogue, which writes the HL32 operand of the next layer directly
@@ -270,6 +287,9 @@ class BackboneGroup(_GroupedLinear):
                                                     want_f32=want_f32, want_hl=want_hl)
             return Act((G, B, Hp, Wp, Cout), f32, hl)
         Ho, Wo = y.shape[2], y.shape[3]              # (a pooled patch convolution left the pooled map)
+        if height_mean:
+            f32, hl = ops.height_mean_grouped(y, scale, shift, relu=post_relu, want_f32=want_f32, want_hl=want_hl)
+            return Act((G, B, 1, Wo, Cout), None if f32 is None else f32.view(G, B, 1, Wo, Cout), hl)
         if scale is None and res is None and res_hl is None and not post_relu and not want_hl and not want_wino:
             return Act((G, B, Ho, Wo, Cout), y, None)
         if want_wino:
@@ -347,7 +367,7 @@ class BackboneGroup(_GroupedLinear):
                        want_wino=first_wino("layer4"))
         x = stage(x, "layer4", "conv4_1", "bn4_1")
         x = self.layer(x, [n.conv4_1 for n in nets], [n.bn4_1 for n in nets])
-        return self.layer(x, [n.conv4_2 for n in nets], [n.bn4_2 for n in nets], want_f32=not last_hl, want_hl=last_hl)
+        return self.layer(x, [n.conv4_2 for n in nets], [n.bn4_2 for n in nets], want_f32=not last_hl, want_hl=last_hl, height_mean=True)
 
     def _vgg(self, x, last_hl=False):
         nets = [e.FeatureExtraction.ConvNet for e in self.experts]
@@ -359,7 +379,7 @@ class BackboneGroup(_GroupedLinear):
             if nxt is not None:
                 ww = self.wino_for(nets[0][nxt[0]], None if nxt[1] is None else [n[nxt[1]] for n in nets])
             return self.layer(x, [n[i] for n in nets], None if bn is None else [n[bn] for n in nets], pool=pool,
-                              want_f32=last and not last_hl, want_hl=(not last or last_hl) and not ww, want_wino=ww)
+                              want_f32=last and not last_hl, want_hl=(not last or last_hl) and not ww, want_wino=ww, height_mean=last)
         x = L(x, 0, pool=p22, nxt=(3, None))
         x = L(x, 3, pool=p22, nxt=(6, None))
         x = L(x, 6, nxt=(8, None))
@@ -573,11 +593,14 @@ class BackboneGroup(_GroupedLinear):
 
     def visual_all(self, image, as_act=False):
         """image: logical [B,C,H,W] -> backbone features [G,B,T,C'] (the reference's permute + AdaptiveAvgPool + squeeze
-        is the identity on the height-1 NHWC map).  as_act: return the [G,B,1,T,C'] Act holding only the HL32 operand
-        (what HeadsGroup's first grouped Linear consumes)."""
+        is the identity on the height-1 NHWC map of 32-pixel inputs; a taller final map is averaged over its rows by the last
+        layer's BatchNorm-apply pass).  as_act: return the [G,B,1,T,C'] Act holding only the HL32 operand (what HeadsGroup's first
+        grouped Linear consumes)."""
         img = to_nhwc(image)
         B, H, W, C = img.shape
         self._nbt = []
+        stages = self.experts[0].stages
+        self._height_mean = geometry_supported(stages["Feat"], H, W, stages["Trans"])     # (else a taller final map is refused below)
         if self.experts[0].stages["Trans"] == "TPS":
             x = self._tps(img)
         else:
@@ -593,7 +616,7 @@ class BackboneGroup(_GroupedLinear):
             torch._foreach_add_(self._nbt, 1)
         G, B, Ho, Wo, Cf = x.shape
         if Ho != 1:
-            raise NotImplementedError("HIP path expects a height-1 feature map (32x256 inputs); got H=%d" % Ho)
+            raise NotImplementedError(unsupported_geometry_message(stages["Trans"], stages["Feat"], H, W, Ho))
         return x if as_act else x.f32.view(G, B, Wo, Cf)
 
 

@@ -16,10 +16,11 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..functional import FaninFn, GateTailFn, LinearFn, needs_grad
+from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
+from .geometry import geometry_supported, unsupported_geometry_message
 from .prediction import Attention
 from .sequence_modeling import BidirectionalLSTM
 from .transformation import TPS_SpatialTransformerNetwork
@@ -74,10 +75,16 @@ class Model_Extractor(nn.Module):
                 image = self.Transformation(image)
             fmap = self.FeatureExtraction(image)             # logical [B,C,H,W], NHWC memory
         B, C, H, W = fmap.shape
-        if H != 1:
-            raise NotImplementedError("HIP path expects a height-1 feature map (32x256 inputs); got H=%d" % H)
-        # permute(0,3,1,2) + AdaptiveAvgPool((None,1)) + squeeze(3) of the reference is the identity on [B,1,W,C]
-        return to_nhwc(fmap).view(B, W, C)
+        if H == 1:
+            # permute(0,3,1,2) + AdaptiveAvgPool((None,1)) + squeeze(3) of the reference is the identity on [B,1,W,C]
+            return to_nhwc(fmap).view(B, W, C)
+        Hi, Wi = image.shape[2], image.shape[3]
+        if not geometry_supported(self.stages["Feat"], Hi, Wi, self.stages["Trans"]):
+            raise NotImplementedError(unsupported_geometry_message(self.stages["Trans"], self.stages["Feat"], Hi, Wi, H))
+        x = to_nhwc(fmap)                                    # 48- / 64-pixel inputs: the mean over the map's 2 / 3 rows
+        if torch.is_grad_enabled() and x.requires_grad:
+            return HeightMeanFn.apply(x)
+        return ops.height_mean(x)
 
     def sequence(self, visual, out=None):
         """SequenceModeling stage: [B,T,C'] -> [B,T,hidden]; `out` = optional (strided) destination."""

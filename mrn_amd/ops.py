@@ -662,14 +662,22 @@ def wino_dense(products=None):
     return (X3_PRODUCTS if products is None else products) == 1 and WINO_DENSE and WINO_R == 4
 
 
-def wino_eligible(ksize, stride, padding, Cin, Cout, products=None):
-    """products: of the pass that asks (None: X3_PRODUCTS, the frozen experts; the trained layers pass TRAIN_PRODUCTS)"""
+def wino_rows_fit(H, products=None):
+    """can a map of H rows take the Winograd form of a `products`-product pass: the plain-fp16 (d16) form of the reduced mode runs on the
+    row-block kernel only (4-row blocks), the split form on every height"""
+    return not wino_dense(products) or (H >= 4 and H % 4 == 0)
+
+
+def wino_eligible(ksize, stride, padding, Cin, Cout, products=None, H=None):
+    """products: of the pass that asks (None: X3_PRODUCTS, the frozen experts; the trained layers pass TRAIN_PRODUCTS); H: rows of the
+    map the conv is applied to, when known (None: not checked -- at imgH = 32 every such map has 4k rows)"""
     products = X3_PRODUCTS if products is None else products
     ok = (WINO_R in (2, 4) and tuple(ksize) == (3, 3) and tuple(stride) == (1, 1) and tuple(padding) == (1, 1)
           and Cin % 32 == 0 and Cin >= WINO_MIN_CIN and Cout >= 64)
     if products == 3:
         return ok
-    return ok and wino_dense(products) and Cin % 64 == 0 and Cout % 4 == 0          # (the d16 form has no fallback kernel: row-block geometry only)
+    # (the d16 form has no fallback kernel: row-block geometry only)
+    return ok and wino_dense(products) and Cin % 64 == 0 and Cout % 4 == 0 and (H is None or wino_rows_fit(H, products))
 
 
 def pack_weights_wino(ws, R, scale=None, dense=None):
@@ -1210,6 +1218,37 @@ def avgpool_nhwc(x, scale=None, shift=None, relu=False):
     y = torch.empty(B, C, device=x.device, dtype=torch.float32)
     call("mrn_avgpool_nhwc_f32", _p(x), _p(y), _p(scale), _p(shift), int(relu), B, H * W, C, _stream())
     return y
+
+
+def height_mean_grouped(x, scale=None, shift=None, relu=False, want_f32=True, want_hl=False):
+    """x [G,B,H,W,C] fp32 -> (fp32 [G,B,W,C] or None, HL32 bytes or None): the mean over H of act(x * scale[g] + shift[g]) -- the
+    reference's permute + AdaptiveAvgPool2d((None, 1)) + squeeze at the end of the visual stage (modules/model.py:92) for maps of
+    height > 1, with the final BatchNorm-apply + ReLU in the same pass; scale / shift [G,C] or None"""
+    _chk(x, scale, shift)
+    G, B, H, W, C = x.shape
+    assert x.is_contiguous()
+    out = torch.empty(G, B, W, C, device=x.device, dtype=torch.float32) if want_f32 else None
+    out_hl = torch.empty(G * B * W * C * 4, device=x.device, dtype=torch.uint8) if want_hl else None
+    t0 = CONV_TIMER.begin("hmean") if CONV_TIMER is not None else None
+    call("mrn_height_mean_grouped_f32", _p(x), _p(scale), _p(shift), int(bool(relu)), _p(out), _p(out_hl), G, B, H, W, C, _stream())
+    if t0 is not None:
+        CONV_TIMER.end(t0, 0.0, "hbm/height_mean_grouped", 4.0 * x.numel() + 4.0 * G * B * W * C * (int(want_f32) + int(want_hl)))
+    return out, out_hl
+
+
+def height_mean(x):
+    """one network's [B,H,W,C] -> [B,W,C] (height_mean_grouped with G = 1, no affine)"""
+    B, H, W, C = x.shape
+    return height_mean_grouped(x.contiguous().view(1, B, H, W, C))[0].view(B, W, C)
+
+
+def height_mean_bwd(dy, H):
+    """gradient of height_mean: dy [B,W,C] -> dx [B,H,W,C] = dy / H on every row"""
+    _chk(dy)
+    B, W, C = dy.shape
+    dx = torch.empty(B, H, W, C, device=dy.device, dtype=torch.float32)
+    call("mrn_height_mean_bwd_f32", _p(dy.contiguous()), _p(dx), B, H, W, C, _stream())
+    return dx
 
 
 # ---------------------------------------------------------------------------------------------------------
