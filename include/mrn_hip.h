@@ -608,6 +608,17 @@ int mrn_ctc_loss_fwd_f32(const float* logits, int64_t ld, const int64_t* targets
 int mrn_ctc_loss_bwd_f32(const float* logits, int64_t ld, const float* lse, const float* occ, const int64_t* targets,
                          int64_t tstride, const int* target_len, const float* nll, const float* upstream,
                          float* dlogits, int64_t ldd, int B, int T, int C, int blank, void* stream);
+/* The same CTCLoss (il_modules/base.py:131: no limit on the label length) for padded target widths up to 255: one wave per sample,
+ * K = 1 / 2 / 4 / 8 states per lane chosen from max_target_len, alpha kept in occ (no LDS, any T).  occ holds
+ * mrn_ctc_occ_floats_long(B, T, max_target_len) floats (-1 beyond 255) and the bwd takes the fwd's max_target_len; both return
+ * MRN_ERR naming the range when max_target_len > 255.  The entry points above keep their 64-state kernel (max_target_len <= 31). */
+int64_t mrn_ctc_occ_floats_long(int B, int T, int max_target_len);
+int mrn_ctc_loss_fwd_long_f32(const float* logits, int64_t ld, const int64_t* targets, int64_t tstride,
+                              const int* target_len, int max_target_len, float* lse, float* nll, float* occ, float* loss,
+                              int B, int T, int C, int blank, void* stream);
+int mrn_ctc_loss_bwd_long_f32(const float* logits, int64_t ld, const float* lse, const float* occ, const int64_t* targets,
+                              int64_t tstride, const int* target_len, int max_target_len, const float* nll,
+                              const float* upstream, float* dlogits, int64_t ldd, int B, int T, int C, int blank, void* stream);
 
 /* Knowledge distillation of LwF / WA (il_modules/lwf.py:81-87,111-114): loss = -sum softmax(old/T) log_softmax(new/T) / rows
  * over the class slice [c0, c1); bwd writes d loss / d new over all C columns (zeros outside the slice). */

@@ -451,21 +451,24 @@ __global__ __launch_bounds__(256) void tps_sample_bwd_kernel(const float* __rest
 }
 
 // ---- the two deferred sums of the decoder backward (one workgroup of 256 threads per sample and 256-column block) ------------------
+// Each launch sums the steps s0 <= s < s0 + s_len and writes (accumulate = 0) or adds to (accumulate = 1) its output: attn_bwd_launch
+// splits S into chunks whose LDS staging fits, and uses one launch over all of S when it does (long labels: batch_max_length >= 127).
 // dHb[b][t][d] = sum_s alpha[b][s][t] * dctx[b][s][d]: thread = column d; alpha[b] and the block's dctx[b] staged in LDS
 __global__ __launch_bounds__(256) void attn_bwd_dhb_kernel(const float* __restrict__ alpha, const float* __restrict__ dctx,
-                                                           float* __restrict__ dHb, int T, int D, int S) {
+                                                           float* __restrict__ dHb, int T, int D, int S, int s0, int s_len,
+                                                           int accumulate) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* al = sm;                 // [S][T]
-  float* dc = sm + S * T;         // [S][256]
+  float* al = sm;                 // [s_len][T]
+  float* dc = sm + s_len * T;     // [s_len][256]
   const int b = blockIdx.x, d0 = blockIdx.y * 256, tid = threadIdx.x;
-  for (int i = tid; i < S * T; i += 256) al[i] = alpha[(long)b * S * T + i];
-  for (int s = 0; s < S; ++s) dc[s * 256 + tid] = dctx[((long)b * S + s) * D + d0 + tid];
+  for (int i = tid; i < s_len * T; i += 256) al[i] = alpha[((long)b * S + s0) * T + i];
+  for (int s = 0; s < s_len; ++s) dc[s * 256 + tid] = dctx[((long)b * S + s0 + s) * D + d0 + tid];
   __syncthreads();
   float* out = dHb + (long)b * T * D + d0 + tid;
   for (int t = 0; t < T; ++t) {
     float a = 0.f;
-    for (int s = 0; s < S; ++s) a = fmaf(al[s * T + t], dc[s * 256 + tid], a);
-    out[(long)t * D] = a;
+    for (int s = 0; s < s_len; ++s) a = fmaf(al[s * T + t], dc[s * 256 + tid], a);
+    out[(long)t * D] = accumulate ? out[(long)t * D] + a : a;
   }
 }
 
@@ -473,13 +476,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dhb_kernel(const float* __restri
 // of the T positions; hp[b] and de[b] staged in LDS.  The terms are the main kernel's dpre (same expression, same fast_tanh).
 __global__ __launch_bounds__(256) void attn_bwd_dhproj_kernel(const float* __restrict__ Hproj, const float* __restrict__ hp,
                                                               const float* __restrict__ de, const float* __restrict__ w_score,
-                                                              float* __restrict__ dHproj, int T, int S) {
+                                                              float* __restrict__ dHproj, int T, int S, int s0, int s_len,
+                                                              int accumulate) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* hps = sm;                // [S][HID]
-  float* des = sm + S * HID;      // [S][T]
+  float* hps = sm;                // [s_len][HID]
+  float* des = sm + s_len * HID;  // [s_len][T]
   const int b = blockIdx.x, c = threadIdx.x;
-  for (int s = 0; s < S; ++s) hps[s * HID + c] = hp[((long)b * S + s) * HID + c];
-  for (int i = c; i < S * T; i += 256) des[i] = de[(long)b * S * T + i];
+  for (int s = 0; s < s_len; ++s) hps[s * HID + c] = hp[((long)b * S + s0 + s) * HID + c];
+  for (int i = c; i < s_len * T; i += 256) des[i] = de[((long)b * S + s0) * T + i];
   __syncthreads();
   const float w = w_score[c];
   const int per = (T + gridDim.y - 1) / gridDim.y;
@@ -487,11 +491,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dhproj_kernel(const float* __res
   for (int t = blockIdx.y * per; t < t_end; ++t) {
     const float x = Hproj[((long)b * T + t) * HID + c];
     float a = 0.f;
-    for (int s = 0; s < S; ++s) {
+    for (int s = 0; s < s_len; ++s) {
       const float uu = fast_tanh(x + hps[s * HID + c]);
       a += des[s * T + t] * w * (1.f - uu * uu);
     }
-    dHproj[((long)b * T + t) * HID + c] = a;
+    float* o = dHproj + ((long)b * T + t) * HID + c;
+    *o = accumulate ? *o + a : a;
   }
 }
 
@@ -518,9 +523,12 @@ static int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st) {
     hipFuncSetAttribute((const void*)attn_decoder_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  const size_t lds_b = sizeof(float) * (size_t)p.S * (p.T + 256), lds_p = sizeof(float) * (size_t)p.S * (HID + p.T);
-  MRN_CHECK_ARG(lds_b <= 160 * 1024 && lds_p <= 160 * 1024, "mrn_attn_decoder_bwd: S=%d, T=%d beyond the deferred sums' LDS staging", p.S, p.T);
-  if (lds_b > 64 * 1024 || lds_p > 64 * 1024) {
+  // the deferred sums stage [s_len][T + 256] floats (HID = 256 = the dctx column block): steps per launch that fit in 160 KB
+  const int s_fit = (int)((160 * 1024) / (sizeof(float) * (size_t)(p.T + 256)));
+  MRN_CHECK_ARG(s_fit >= 1, "mrn_attn_decoder_bwd: T=%d beyond the deferred sums' LDS staging", p.T);
+  const int s_chunk = p.S < s_fit ? p.S : s_fit;
+  const size_t lds_s = sizeof(float) * (size_t)s_chunk * (p.T + 256);
+  if (lds_s > 64 * 1024) {
     static bool big = false;
     if (!big) {
       (void)hipFuncSetAttribute((const void*)attn_bwd_dhb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -531,10 +539,16 @@ static int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st) {
   if (x3) hipLaunchKernelGGL(attn_decoder_bwd_kernel<true>, dim3(ceil_div(p.B, p.vb)), dim3(NTH), lds, st, p);
   else hipLaunchKernelGGL(attn_decoder_bwd_kernel<false>, dim3(ceil_div(p.B, p.vb)), dim3(NTH), lds, st, p);
   MRN_LAUNCH_CHECK("attn_decoder_bwd");
-  hipLaunchKernelGGL(attn_bwd_dhb_kernel, dim3(p.B, p.D / 256), dim3(256), lds_b, st, p.alpha, (const float*)p.dctx, p.dHb, p.T, p.D, p.S);
-  MRN_LAUNCH_CHECK("attn_bwd_dhb");
-  hipLaunchKernelGGL(attn_bwd_dhproj_kernel, dim3(p.B, 4), dim3(256), lds_p, st, p.Hproj, p.hp, (const float*)p.de, p.w_score, p.dHproj, p.T, p.S);
-  MRN_LAUNCH_CHECK("attn_bwd_dhproj");
+  for (int s0 = 0; s0 < p.S; s0 += s_chunk) {
+    const int n = p.S - s0 < s_chunk ? p.S - s0 : s_chunk;
+    const size_t lds_n = sizeof(float) * (size_t)n * (p.T + 256);
+    hipLaunchKernelGGL(attn_bwd_dhb_kernel, dim3(p.B, p.D / 256), dim3(256), lds_n, st, p.alpha, (const float*)p.dctx, p.dHb, p.T, p.D,
+                       p.S, s0, n, s0 > 0 ? 1 : 0);
+    MRN_LAUNCH_CHECK("attn_bwd_dhb");
+    hipLaunchKernelGGL(attn_bwd_dhproj_kernel, dim3(p.B, 4), dim3(256), lds_n, st, p.Hproj, p.hp, (const float*)p.de, p.w_score,
+                       p.dHproj, p.T, p.S, s0, n, s0 > 0 ? 1 : 0);
+    MRN_LAUNCH_CHECK("attn_bwd_dhproj");
+  }
   return MRN_OK;
 }
 

@@ -185,6 +185,185 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// CTC for long labels (up to CTC_LONG_MAXL = 255, 511 states).  Still one wave per sample, but lane l owns the K consecutive
+// states s = l*K .. l*K+K-1 in registers (K = 1, 2, 4, 8: 64 / 128 / 256 / 512 states).  The recursion's s-1 / s-2 neighbours
+// sit in the same lane except for the lane's first one or two states, which take lane-1's last two values through __shfl_up
+// (K = 1: lane-1 and lane-2), so a time step needs no barrier.  alpha goes to the global occ buffer [B][T][64*K] instead of
+// LDS (no ceiling on T); the backward sweep overwrites it in place with the posterior: each lane reads and writes only its
+// own addresses.
+// Over hundreds of frames log alpha reaches -1e3, where an fp32 ulp is 1e-4 and the posterior exp(alpha + beta - lp - ll) would
+// lose ~1e-2 to cancellation.  So both sweeps are scaled (Rabiner): after each forward step the wave subtracts o_t = max_s alpha_t,
+// and the backward step t subtracts the same o_t.  The offsets then cancel exactly in the posterior,
+// exp(alpha^_t + beta^_t + o_t - lp - ll^), and ll = sum_t o_t + ll^.  o_t lives in the row's last slot, state 64*K - 1, which
+// no label reaches (2L+1 <= 64*K - 1).
+// ---------------------------------------------------------------------------------------------
+constexpr int CTC_LONG_MAXL = 255;
+
+__host__ __device__ constexpr int ctc_long_k(int max_target_len) {
+  return max_target_len <= 31 ? 1 : max_target_len <= 63 ? 2 : max_target_len <= 127 ? 4 : 8;
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void ctc_alpha_beta_long_kernel(const float* __restrict__ x, long ld, const float* __restrict__ lse,
+                                                                 const int64_t* __restrict__ targets, long tstride,
+                                                                 const int* __restrict__ tlen, int max_len,
+                                                                 float* __restrict__ nll_out,
+                                                                 float* __restrict__ occ,  // [B][T][64*K]: alpha^, then posterior
+                                                                 int T, int blank) {
+  constexpr int SP = 64 * K;
+  const int b = blockIdx.x, lane = threadIdx.x, s0 = lane * K;
+  const int L = min(max(tlen[b], 0), max_len);   // (a length beyond the padded width would read past the target row)
+  const int S = 2 * L + 1;
+  const int64_t* tb = targets + (long)b * tstride;
+  // per state: class, skip from s-2 allowed (forward), skip to s+2 allowed (backward)
+  int cls[K];
+  bool live[K], skip_bw[K], skip_fw[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int s = s0 + k;
+    live[k] = s < S;
+    cls[k] = (live[k] && (s & 1)) ? (int)tb[s >> 1] : blank;
+    skip_bw[k] = live[k] && (s & 1) && s >= 3 && cls[k] != (int)tb[(s >> 1) - 1];
+    skip_fw[k] = live[k] && (s & 1) && s + 2 < S && cls[k] != (int)tb[(s >> 1) + 1];
+  }
+  const float* xb = x + (long)b * T * ld;
+  const float* lb = lse + (long)b * T;
+  float* ob = occ + (long)b * T * SP + s0;           // this lane's K slots of row 0
+  float* off = occ + (long)b * T * SP + (SP - 1);    // o_t at off[t * SP]
+
+  // forward: a = alpha^_t; o_t = max_s of the unscaled step (state 0 is always reachable, so it is finite)
+  float a[K], lp[K], lpn[K];
+  float sum_o = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int s = s0 + k;
+    lp[k] = live[k] ? xb[cls[k]] - lb[0] : -INFINITY;
+    a[k] = (s == 0 || (s == 1 && L > 0)) ? lp[k] : -INFINITY;
+  }
+  // the next step's log-probabilities are loaded one step ahead (they do not depend on the recursion)
+#pragma unroll
+  for (int k = 0; k < K; ++k) lpn[k] = (live[k] && T > 1) ? xb[ld + cls[k]] - lb[1] : -INFINITY;
+  for (int t = 0;;) {
+    float m = a[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) m = fmaxf(m, a[k]);
+    m = wave_max(m);
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] -= m;           // (-inf stays -inf)
+    sum_o += m;
+    float* o = ob + (long)t * SP;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (live[k]) o[k] = a[k];
+    if (lane == 63) off[(long)t * SP] = m;
+    if (++t == T) break;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      lp[k] = lpn[k];
+      lpn[k] = (live[k] && t + 1 < T) ? xb[(long)(t + 1) * ld + cls[k]] - lb[t + 1] : -INFINITY;
+    }
+    float p1 = __shfl_up(a[K - 1], 1);                         // state s0-1
+    float p2 = K >= 2 ? __shfl_up(a[K >= 2 ? K - 2 : 0], 1)    // state s0-2
+                      : __shfl_up(a[0], 2);
+    if (lane < 1) p1 = -INFINITY;
+    if (s0 < 2) p2 = -INFINITY;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {   // descending: a[k-1], a[k-2] are still step t-1's
+      const float am1 = k >= 1 ? a[k >= 1 ? k - 1 : 0] : p1;
+      const float am2 = k >= 2 ? a[k >= 2 ? k - 2 : 0] : (k == 1 ? p1 : p2);
+      float acc = lse2(a[k], am1);
+      if (skip_bw[k]) acc = lse2(acc, am2);
+      a[k] = live[k] ? acc + lp[k] : -INFINITY;
+    }
+  }
+  // total log-likelihood: ll = sum_t o_t + lse(alpha^[T-1][S-1], alpha^[T-1][S-2])
+  float v1 = -INFINITY, v2 = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (s0 + k == S - 1) v1 = a[k];
+    if (s0 + k == S - 2) v2 = a[k];
+  }
+  const float aS1 = __shfl(v1, (S - 1) / K);
+  const float aS2 = S >= 2 ? __shfl(v2, (S - 2) / K) : -INFINITY;
+  const float ll_hat = lse2(aS1, aS2);
+  if (lane == 0) nll_out[b] = -(sum_o + ll_hat);
+  __syncthreads();   // (one wave) orders lane 63's o_t stores before every lane's loads below
+
+  // backward: be = beta^_t; posterior = exp(alpha^ + beta^ + o_t - lp - ll^)
+  float be[K], al[K], aln[K];
+  float o_t = off[(long)(T - 1) * SP];
+#pragma unroll
+  for (int k = 0; k < K; ++k) lp[k] = live[k] ? xb[(long)(T - 1) * ld + cls[k]] - lb[T - 1] : -INFINITY;
+  {
+    float* o = ob + (long)(T - 1) * SP;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int s = s0 + k;
+      be[k] = (s == S - 1 || (s == S - 2 && S >= 2)) ? lp[k] - o_t : -INFINITY;
+      if (live[k]) o[k] = expf(o[k] + be[k] + o_t - lp[k] - ll_hat);
+    }
+  }
+  float o_n = T > 1 ? off[(long)(T - 2) * SP] : 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    lpn[k] = (live[k] && T > 1) ? xb[(long)(T - 2) * ld + cls[k]] - lb[T - 2] : -INFINITY;
+    aln[k] = (live[k] && T > 1) ? ob[(long)(T - 2) * SP + k] : 0.f;
+  }
+  for (int t = T - 2; t >= 0; --t) {
+    float* o = ob + (long)t * SP;
+    o_t = o_n;
+    o_n = t > 0 ? off[(long)(t - 1) * SP] : 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      lp[k] = lpn[k];
+      al[k] = aln[k];
+      lpn[k] = (live[k] && t > 0) ? xb[(long)(t - 1) * ld + cls[k]] - lb[t - 1] : -INFINITY;
+      aln[k] = (live[k] && t > 0) ? o[k - SP] : 0.f;
+    }
+    float n1 = __shfl_down(be[0], 1);                          // state s0+K
+    float n2 = K >= 2 ? __shfl_down(be[K >= 2 ? 1 : 0], 1)     // state s0+K+1
+                      : __shfl_down(be[0], 2);
+    if (s0 + K >= S) n1 = -INFINITY;
+    if (s0 + K + 1 >= S) n2 = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {        // ascending: be[k+1], be[k+2] are still step t+1's
+      const float bp1 = k + 1 < K ? be[k + 1 < K ? k + 1 : 0] : n1;
+      const float bp2 = k + 2 < K ? be[k + 2 < K ? k + 2 : 0] : (k + 2 == K ? n1 : n2);
+      float acc = lse2(be[k], bp1);
+      if (skip_fw[k]) acc = lse2(acc, bp2);
+      be[k] = live[k] ? acc + lp[k] - o_t : -INFINITY;
+      if (live[k]) o[k] = expf(al[k] + be[k] + o_t - lp[k] - ll_hat);
+    }
+  }
+}
+
+// ctc_grad_kernel over the long layout: the states are looped over instead of one per thread
+__global__ __launch_bounds__(256) void ctc_grad_long_kernel(const float* __restrict__ x, long ld, const float* __restrict__ lse,
+                                                            const float* __restrict__ occ, int sp, const int64_t* __restrict__ targets,
+                                                            long tstride, const int* __restrict__ tlen, int max_len,
+                                                            const float* __restrict__ nll, const float* __restrict__ upstream,
+                                                            float* __restrict__ dx, long ldd, int B, int T, int C, int blank) {
+  const long row = blockIdx.x;
+  const int b = (int)(row / T);
+  const int L = min(max(tlen[b], 0), max_len);
+  const float nl = nll[b];
+  float g = upstream[0] / ((float)B * (float)(tlen[b] < 1 ? 1 : tlen[b]));
+  if (isinf(nl) || nl != nl) g = 0.f;   // zero_infinity
+  const float l = lse[row];
+  const float* xr = x + row * ld;
+  float* dr = dx + row * ldd;
+  for (int c = threadIdx.x; c < C; c += 256) dr[c] = g == 0.f ? 0.f : expf(xr[c] - l) * g;
+  __syncthreads();
+  if (g == 0.f) return;
+  const int S = 2 * L + 1;
+  const float* orow = occ + row * sp;
+  for (int s = threadIdx.x; s < S; s += 256) {
+    const int cls = (s & 1) ? (int)targets[(long)b * tstride + (s >> 1)] : blank;
+    atomicAdd(dr + cls, -orow[s] * g);
+  }
+}
+
 // ---- knowledge distillation (LwF): -sum softmax(old/T) * log_softmax(new/T) / rows over the class slice [c0, c1) -------
 // reference il_modules/lwf.py:81-87,111-114.  One block per row.  loss_rows[row] = -sum_c p_old * logp_new.
 // When dnew != nullptr also writes d loss / d new = (softmax(new/T) - softmax(old/T)) / T * g (zeros outside the slice).
@@ -303,5 +482,54 @@ MRN_EXPORT int mrn_ctc_loss_bwd_f32(const float* logits, int64_t ld, const float
   hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)(B * T)), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, lse, occ,
                      targets, (long)tstride, target_len, nll, upstream, dlogits, (long)ldd, B, T, C, blank);
   MRN_LAUNCH_CHECK("ctc_loss_bwd");
+  return MRN_OK;
+}
+
+// ---- CTC for labels up to CTC_LONG_MAXL: occ is [B][T][64 * K], K from the padded target width ---------------------------------------
+MRN_EXPORT int64_t mrn_ctc_occ_floats_long(int B, int T, int max_target_len) {
+  if (max_target_len < 0 || max_target_len > CTC_LONG_MAXL) return -1;
+  return (int64_t)B * T * 64 * ctc_long_k(max_target_len);
+}
+
+MRN_EXPORT int mrn_ctc_loss_fwd_long_f32(const float* logits, int64_t ld, const int64_t* targets, int64_t tstride,
+                                         const int* target_len, int max_target_len, float* lse, float* nll, float* occ,
+                                         float* loss, int B, int T, int C, int blank, void* stream) {
+  MRN_CHECK_ARG(logits && targets && target_len && lse && nll && occ && loss, "mrn_ctc_loss_fwd_long_f32: null operand");
+  MRN_CHECK_ARG(max_target_len >= 0 && max_target_len <= CTC_LONG_MAXL && max_target_len <= tstride,
+                "mrn_ctc_loss_fwd_long_f32: target length %d outside the long kernel's range 0..%d (target stride %ld)",
+                max_target_len, CTC_LONG_MAXL, (long)tstride);
+  MRN_CHECK_ARG(T > 0 && C > 0, "mrn_ctc_loss_fwd_long_f32: bad shape T=%d C=%d", T, C);
+  if (B == 0) return MRN_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(row_lse_kernel, dim3((unsigned)(B * T)), dim3(256), 0, st, logits, (long)ld, (const int64_t*)nullptr, -1L, lse,
+                     (float*)nullptr, C);
+  const int K = ctc_long_k(max_target_len);
+#define MRN_CTC_LONG(KK)                                                                                                          \
+  hipLaunchKernelGGL(ctc_alpha_beta_long_kernel<KK>, dim3(B), dim3(64), 0, st, logits, (long)ld, (const float*)lse, targets,       \
+                     (long)tstride, target_len, max_target_len, nll, occ, T, blank)
+  if (K == 1) MRN_CTC_LONG(1);
+  else if (K == 2) MRN_CTC_LONG(2);
+  else if (K == 4) MRN_CTC_LONG(4);
+  else MRN_CTC_LONG(8);
+#undef MRN_CTC_LONG
+  hipLaunchKernelGGL(ctc_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)nll, target_len, B, loss);
+  MRN_LAUNCH_CHECK("ctc_loss_fwd_long");
+  return MRN_OK;
+}
+
+MRN_EXPORT int mrn_ctc_loss_bwd_long_f32(const float* logits, int64_t ld, const float* lse, const float* occ,
+                                         const int64_t* targets, int64_t tstride, const int* target_len, int max_target_len,
+                                         const float* nll, const float* upstream, float* dlogits, int64_t ldd, int B, int T, int C,
+                                         int blank, void* stream) {
+  MRN_CHECK_ARG(logits && lse && occ && targets && target_len && nll && upstream && dlogits,
+                "mrn_ctc_loss_bwd_long_f32: null operand");
+  MRN_CHECK_ARG(max_target_len >= 0 && max_target_len <= CTC_LONG_MAXL && max_target_len <= tstride,
+                "mrn_ctc_loss_bwd_long_f32: target length %d outside the long kernel's range 0..%d (target stride %ld)",
+                max_target_len, CTC_LONG_MAXL, (long)tstride);
+  if (B == 0) return MRN_OK;
+  hipLaunchKernelGGL(ctc_grad_long_kernel, dim3((unsigned)(B * T)), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, lse, occ,
+                     64 * ctc_long_k(max_target_len), targets, (long)tstride, target_len, max_target_len, nll, upstream, dlogits,
+                     (long)ldd, B, T, C, blank);
+  MRN_LAUNCH_CHECK("ctc_loss_bwd_long");
   return MRN_OK;
 }

@@ -10,6 +10,7 @@ import weakref
 import torch
 
 from ._lib import call
+from .modules.label_length import ctc_label_length_supported, ctc_uses_long_kernel, unsupported_label_length_message
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -1758,7 +1759,12 @@ def ce_loss_bwd(ctx, upstream, like):
 
 
 def ctc_loss_fwd(logits, targets, target_len, blank=0):
-    """logits [B,T,C] (strided rows), targets [B,L] int64, target_len [B] int32 -> (loss, ctx)"""
+    """logits [B,T,C] (strided rows), targets [B,L] int64, target_len [B] int32 -> (loss, ctx).  The padded width L picks the kernel:
+    the 64-state one up to 31, the long one up to 255 (modules/label_length.py); wider targets are refused before any launch."""
+    W = targets.shape[1]
+    if not ctc_label_length_supported(W):
+        raise NotImplementedError(unsupported_label_length_message(W))
+    long_path = ctc_uses_long_kernel(W)
     B, T, C = logits.shape
     assert logits.stride(2) == 1 and logits.stride(0) == T * logits.stride(1)
     dev = logits.device
@@ -1766,19 +1772,29 @@ def ctc_loss_fwd(logits, targets, target_len, blank=0):
     target_len = target_len.to(torch.int32).contiguous()
     lse = torch.empty(B * T, device=dev, dtype=torch.float32)
     nll = torch.empty(B, device=dev, dtype=torch.float32)
-    occ = torch.empty(call("mrn_ctc_occ_floats", B, T), device=dev, dtype=torch.float32)
     loss = torch.empty(1, device=dev, dtype=torch.float32)
-    call("mrn_ctc_loss_fwd_f32", _p(logits), logits.stride(1), _p(targets), targets.stride(0), _p(target_len),
-         targets.shape[1], _p(lse), _p(nll), _p(occ), _p(loss), B, T, C, blank, _stream())
+    if long_path:
+        occ = torch.empty(call("mrn_ctc_occ_floats_long", B, T, W), device=dev, dtype=torch.float32)
+        call("mrn_ctc_loss_fwd_long_f32", _p(logits), logits.stride(1), _p(targets), targets.stride(0), _p(target_len), W, _p(lse),
+             _p(nll), _p(occ), _p(loss), B, T, C, blank, _stream())
+    else:
+        occ = torch.empty(call("mrn_ctc_occ_floats", B, T), device=dev, dtype=torch.float32)
+        call("mrn_ctc_loss_fwd_f32", _p(logits), logits.stride(1), _p(targets), targets.stride(0), _p(target_len),
+             W, _p(lse), _p(nll), _p(occ), _p(loss), B, T, C, blank, _stream())
     return loss, (logits, targets, target_len, lse, nll, occ, blank)
 
 
 def ctc_loss_bwd(ctx, upstream):
     logits, targets, target_len, lse, nll, occ, blank = ctx
     B, T, C = logits.shape
+    W = targets.shape[1]
     d = torch.empty_strided(logits.shape, logits.stride(), device=logits.device, dtype=torch.float32)
-    call("mrn_ctc_loss_bwd_f32", _p(logits), logits.stride(1), _p(lse), _p(occ), _p(targets), targets.stride(0),
-         _p(target_len), _p(nll), _p(upstream), _p(d), d.stride(1), B, T, C, blank, _stream())
+    if ctc_uses_long_kernel(W):
+        call("mrn_ctc_loss_bwd_long_f32", _p(logits), logits.stride(1), _p(lse), _p(occ), _p(targets), targets.stride(0),
+             _p(target_len), W, _p(nll), _p(upstream), _p(d), d.stride(1), B, T, C, blank, _stream())
+    else:
+        call("mrn_ctc_loss_bwd_f32", _p(logits), logits.stride(1), _p(lse), _p(occ), _p(targets), targets.stride(0),
+             _p(target_len), _p(nll), _p(upstream), _p(d), d.stride(1), B, T, C, blank, _stream())
     return d
 
 
