@@ -591,6 +591,18 @@ int mrn_gate_tail_fwd_f32(const float* r, const float* w_route, const float* b_r
                           float* w_out, int64_t* argmax_out, int B, int P, int I, void* stream);
 int mrn_gate_tail_bwd_f32(const float* w, const float* dw, const float* r, const float* w_route, float beta,
                           float* ds, float* dr, float* d_w_route, float* d_b_route, int B, int P, int I, void* stream);
+/* The same five with 16-wide per-expert register arrays: I in 1..16 (the entry points above take 1..8).  At I <= 8 they compute
+ * what the 8-wide ones do, bit for bit; mrn_amd/ops.py takes these from 9 experts on (modules/task_count.py). */
+int mrn_fanin_fwd_wide_f32(const void* const* logits, const int64_t* lds, const int* classes, int I, const float* w,
+                           float* out, int64_t ldo, int B, int T, int C, void* stream);
+int mrn_fanin_bwd_wide_f32(const void* const* logits, const int64_t* lds, const int* classes, int I, const float* dout,
+                           int64_t ldd, float* dw, float* workspace, int B, int T, int C, void* stream);
+int mrn_select_expert_wide_f32(const void* const* logits, const int64_t* lds, const int* classes, int I,
+                               const int64_t* index, float* out, int64_t ldo, int B, int T, int C, void* stream);
+int mrn_gate_tail_fwd_wide_f32(const float* r, const float* w_route, const float* b_route, float beta, float* s_out,
+                               float* w_out, int64_t* argmax_out, int B, int P, int I, void* stream);
+int mrn_gate_tail_bwd_wide_f32(const float* w, const float* dw, const float* r, const float* w_route, float beta,
+                               float* ds, float* dr, float* d_w_route, float* d_b_route, int B, int P, int I, void* stream);
 
 /* ---- losses -------------------------------------------------------------------------------------------------- */
 

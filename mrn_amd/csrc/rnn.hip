@@ -56,6 +56,35 @@ __device__ __forceinline__ void mma_rows(f32x4 (&acc)[NG], const float* __restri
   }
 }
 
+// mma_rows over the k-steps of the columns [k0, k0 + kn) of a K-wide fragment-major W, with A holding just those kn columns (from its
+// column 0): the wide-context decoder keeps one chunk of the context in LDS at a time.  Chunk after chunk on the same accumulators,
+// the MFMAs run in the order of one mma_rows over all of K.
+template <int NG>
+__device__ __forceinline__ void mma_rows_k(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
+                                           const float* __restrict__ Wp, int K, int k0, int kn, int wave, int lane) {
+  const int n = lane & 15, g4 = (lane >> 4) * 4;
+  const float* ap = a_lds + n * lda + g4;
+  const int Q = K / 16, nq = kn / 16;
+  const f32x4* wp = reinterpret_cast<const f32x4*>(Wp) + (long)wave * NG * Q * 64 + (long)(k0 / 16) * 64 + lane;
+  f32x4 wv[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) wv[g] = wp[(long)g * Q * 64];
+#pragma unroll 1
+  for (int q = 0; q < nq; ++q) {
+    f32x4 wn[NG];
+    const int qn = (q + 1 < nq) ? q + 1 : q;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) wn[g] = wp[((long)g * Q + qn) * 64];
+    const f32x4 av = *reinterpret_cast<const f32x4*>(ap + q * 16);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) acc[g] = mfma4(av[r], wv[g][r], acc[g]);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) wv[g] = wn[g];
+  }
+}
+
 // act[g][r] receives the post-activation gates (i, f, g, o) for the backward pass
 __device__ __forceinline__ void lstm_pointwise(const f32x4 (&acc)[4], const float (&xg)[4][4], const float (&bh)[4],
                                                float (&c)[4], float (&h)[4], float (&act)[4][4]) {
@@ -244,6 +273,49 @@ __device__ __forceinline__ void mma_rows_hb(f32x4 (&acc)[NG], const _Float16* __
   for (int q = 0; q < Q; ++q) {
     f16v8 nh[NG], nl[NG];
     const int qn = (q + 1 < Q) ? q + 1 : q;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      nh[g] = wfrag(g, qn, 0);
+      nl[g] = wfrag(g, qn, 1);
+    }
+    const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + q * 32), xl = *reinterpret_cast<const f16v8*>(al + q * 32);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      wh[g] = nh[g];
+      wl[g] = nl[g];
+    }
+  }
+}
+
+// mma_rows_hb over the k-steps of the columns [k0, k0 + kn) of a K-wide stream, A holding just those kn columns (see mma_rows_k)
+template <int NG>
+__device__ __forceinline__ void mma_rows_hb_k(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
+                                              const __amdgpu_buffer_rsrc_t rw, int K, int k0, int kn, int wave, int lane, int ld) {
+  const int n = lane & 15, kg = lane >> 4;
+  const int Q = K / 32, q0 = k0 / 32, nq = kn / 32;
+  const int wwave = __builtin_amdgcn_readfirstlane(wave) * NG * Q * 2048;
+  const int wlane = lane * 32;
+  auto wfrag = [&](int g, int q, int plane) -> f16v8 {
+    return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + ((g * Q + q0 + q) * 128 + plane) * 16, 0));
+  };
+  const _Float16* ah = a_hi + n * ld + kg * 8;
+  const _Float16* al = a_lo + n * ld + kg * 8;
+  f16v8 wh[NG], wl[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    wh[g] = wfrag(g, 0, 0);
+    wl[g] = wfrag(g, 0, 1);
+  }
+#pragma unroll 1
+  for (int q = 0; q < nq; ++q) {
+    f16v8 nh[NG], nl[NG];
+    const int qn = (q + 1 < nq) ? q + 1 : q;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       nh[g] = wfrag(g, qn, 0);
@@ -539,7 +611,55 @@ struct AttnDecGroup {
 // context live in LDS as fp16 hi / lo planes, the weights come as fragment-major hi / lo streams with a power-of-two prescale
 // (ops.pack_fragment_major_h).  On the exact-fp32 pipe those products are 30 us of a step (576 MFMAs of 32 cycles per wave, four
 // waves per SIMD); as x3 216 MFMAs of 16 cycles.
+// (4) of the WIDE form, one chunk: ctx[row][k0 + c] = sum_t alpha[row][t] * Hb[b][t][k0 + c] for the kn columns from k0, into column c
+// of the LDS tile (fp32 rows of stride cld, or the fp16 hi / lo planes of stride cldh) and ctx_out; the same sums as (4) in the kernel
 template <bool X3>
+__device__ __forceinline__ void context_chunk(const AttnDecParams& p, const float* __restrict__ e_lds, float* ctx_lds, _Float16* c_hi,
+                                              _Float16* c_lo, int cld, int cldh, int b0, int Bend, int vb, int step, int k0, int kn,
+                                              int t_) {
+  const int T = p.T, D = p.D, n4 = kn / 4;
+  for (int it = t_; it < vb * n4; it += NTH) {
+    const int row = it / n4, c4 = it - row * n4;
+    const int b = b0 + row;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (b < Bend) {
+      const float* hb = p.Hb + (long)b * T * D + k0 + c4 * 4;
+      int t = 0;
+#pragma unroll 1
+      for (; t + 4 <= T; t += 4) {
+        f32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float w = e_lds[row * T + t + u];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
+        }
+      }
+      for (; t < T; ++t) {
+        const float w = e_lds[row * T + t];
+        const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
+      }
+    }
+    if constexpr (X3) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * cldh + c4 * 4 + k, a[k]);
+    } else {
+      *reinterpret_cast<f32x4*>(ctx_lds + row * cld + c4 * 4) = a;
+    }
+    if (p.ctx_out && b < Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + k0 + c4 * 4) = a;
+  }
+}
+
+// WIDE: the context tile holds CTX_CHUNK columns instead of D.  Phases (4) and the context half of (5) then run chunk by chunk: form
+// one chunk of every row's context, multiply it into the gate accumulators, next chunk (attn_launch takes this form when the whole
+// tile would not fit the LDS budget: D = 256 * G for G >= 8 at T = 65, DERNet's main head).
+constexpr int CTX_CHUNK = 1024;
+
+template <bool X3, bool WIDE>
 __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup grp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // pinned == 1: one expert's recurrent weights (2.3 MiB) stay in one XCD's L2, all tiles of a group run on XCD (group % 8); pinned == 2
@@ -557,8 +677,9 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
   if (gi >= grp.groups) return;
   const AttnDecParams p = grp.g[gi];
   const int D = p.D, T = p.T;
-  const int CLD = D + 4;
-  const int CLDH = D + 8;                  // x3: fp16 row of the context planes
+  const int DC = WIDE ? CTX_CHUNK : D;     // context columns the LDS tile holds
+  const int CLD = DC + 4;
+  const int CLDH = DC + 8;                 // x3: fp16 row of the context planes
   float* h_lds = lds;                      // [BT][HLD]                     (x3: two fp16 planes [BT][LDH])
   float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;        // [BT][HLD]
   float* ctx_lds = hp_lds + BT * HLD;      // [BT][CLD]                     (x3: two fp16 planes [BT][CLDH])
@@ -700,42 +821,44 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
     }
-    // (4) context[b][:] = sum_t alpha[b][t] * Hb[b][t][:]
-    for (int it = t_; it < vb * (D / 4); it += NTH) {
-      const int row = it / (D / 4), c4 = it - row * (D / 4);
-      const int b = b0 + row;
-      f32x4 a = {0.f, 0.f, 0.f, 0.f};
-      if (b < Bend) {
-        const float* hb = p.Hb + (long)b * T * D + c4 * 4;
-        int t = 0;
+    // (4) context[b][:] = sum_t alpha[b][t] * Hb[b][t][:]   (WIDE: chunk by chunk in (5))
+    if constexpr (!WIDE) {
+      for (int it = t_; it < vb * (D / 4); it += NTH) {
+        const int row = it / (D / 4), c4 = it - row * (D / 4);
+        const int b = b0 + row;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        if (b < Bend) {
+          const float* hb = p.Hb + (long)b * T * D + c4 * 4;
+          int t = 0;
 #pragma unroll 1
-        for (; t + 4 <= T; t += 4) {                 // four independent loads in flight per lane, 16 waves per CU (eight: no faster)
-          f32x4 v[4];
+          for (; t + 4 <= T; t += 4) {                 // four independent loads in flight per lane, 16 waves per CU (eight: no faster)
+            f32x4 v[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float w = e_lds[row * T + t + u];
+            for (int u = 0; u < 4; ++u) {
+              const float w = e_lds[row * T + t + u];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
+              for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
+            }
+          }
+          for (; t < T; ++t) {
+            const float w = e_lds[row * T + t];
+            const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
           }
         }
-        for (; t < T; ++t) {
-          const float w = e_lds[row * T + t];
-          const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+        if constexpr (X3) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
+          for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
+        } else {
+          *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
         }
+        if (p.ctx_out && b < Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + c4 * 4) = a;
       }
-      if constexpr (X3) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
-      } else {
-        *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
-      }
-      if (p.ctx_out && b < Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + c4 * 4) = a;
+      __syncthreads();
     }
-    __syncthreads();
     // (5) gates = eproj + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
     {
       f32x4 acc[4];
@@ -743,7 +866,17 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
       if constexpr (X3) {
-        mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
+        if constexpr (WIDE) {
+          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
+            const int kn = min(CTX_CHUNK, D - k0);
+            context_chunk<true>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
+            __syncthreads();
+            mma_rows_hb_k<4>(acc, c_hi, c_lo, r_ih, D, k0, kn, wave, lane, CLDH);
+            if (k0 + CTX_CHUNK < D) __syncthreads();   // every wave is done with this chunk before the next one lands
+          }
+        } else {
+          mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
+        }
         const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[g] *= ratio;
@@ -751,7 +884,17 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
       } else {
-        mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
+        if constexpr (WIDE) {
+          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
+            const int kn = min(CTX_CHUNK, D - k0);
+            context_chunk<false>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
+            __syncthreads();
+            mma_rows_k<4>(acc, ctx_lds, CLD, p.w_ih, D, k0, kn, wave, lane);
+            if (k0 + CTX_CHUNK < D) __syncthreads();
+          }
+        } else {
+          mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
+        }
         mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
       }
       __syncthreads();  // every wave has finished reading h_lds
@@ -909,6 +1052,13 @@ static int attn_fill(AttnDecParams& p, const float* Hb, const float* Hproj, cons
   return MRN_OK;
 }
 
+template <bool X3, bool WIDE>
+static void attn_kernel_launch(const AttnDecGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024)
+    hipFuncSetAttribute((const void*)attn_decoder_kernel<X3, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_decoder_kernel<X3, WIDE>), grid, dim3(NTH), lds, st, grp);
+}
+
 static int attn_launch(AttnDecGroup& grp, int groups, int D, int T, hipStream_t st) {
   grp.groups = groups;
   const int B = grp.g[0].B;
@@ -927,16 +1077,22 @@ static int attn_launch(AttnDecGroup& grp, int groups, int D, int T, hipStream_t 
   static const bool balance = !(getenv("MRN_ATTN_BALANCE") && atoi(getenv("MRN_ATTN_BALANCE")) == 0);     // (A/B switch, read once)
   if (balance && groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
   const bool x3 = grp.g[0].w_inv != nullptr;
-  const size_t lds = sizeof(float) * (2 * BT * HLD + BT * (D + 4) + BT * T + HID) + (x3 ? 1024 : 0);
+  // the single-launch form holds the tile's whole context (BT x (D + 4) floats) in LDS; where that breaks the 160 KB budget (D = 256 * G,
+  // G >= 8 at T = 65) the WIDE form holds CTX_CHUNK columns of it at a time.  MRN_ATTN_CTX_CHUNK=1 takes the WIDE form at any D (test
+  // switch, read per launch)
+  auto lds_for = [&](int dc) { return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0); };
+  const char* force = getenv("MRN_ATTN_CTX_CHUNK");
+  const bool wide = lds_for(D) > 160 * 1024 || (force && atoi(force) == 1);
+  const size_t lds = lds_for(wide ? CTX_CHUNK : D);
   MRN_CHECK_ARG(lds <= 160 * 1024, "mrn_attn_decoder_fwd: LDS budget exceeded (D=%d T=%d)", D, T);
   MRN_CHECK_ARG(!x3 || D % 32 == 0, "mrn_attn_decoder_fwd (x3): D=%d must be a multiple of 32", D);
   const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
   if (x3) {
-    if (lds > 64 * 1024) hipFuncSetAttribute((const void*)attn_decoder_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_decoder_kernel<true>, grid, dim3(NTH), lds, st, grp);
+    if (wide) attn_kernel_launch<true, true>(grp, grid, lds, st);
+    else attn_kernel_launch<true, false>(grp, grid, lds, st);
   } else {
-    if (lds > 64 * 1024) hipFuncSetAttribute((const void*)attn_decoder_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_decoder_kernel<false>, grid, dim3(NTH), lds, st, grp);
+    if (wide) attn_kernel_launch<false, true>(grp, grid, lds, st);
+    else attn_kernel_launch<false, false>(grp, grid, lds, st);
   }
   MRN_LAUNCH_CHECK("attn_decoder");
   return MRN_OK;

@@ -23,6 +23,7 @@ from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import geometry_supported, unsupported_geometry_message
 from .prediction import Attention
 from .sequence_modeling import BidirectionalLSTM
+from .task_count import tasks_supported, unsupported_task_count_message
 from .transformation import TPS_SpatialTransformerNetwork
 
 
@@ -299,6 +300,8 @@ class DERNet(Model):
         return {"logits": logits, "aux_logits": aux, "features": feat}
 
     def update_fc(self, hidden_size, nb_classes, device=None):
+        if not tasks_supported(len(self.model) + 1):
+            raise NotImplementedError(unsupported_task_count_message("DERNet", len(self.model) + 1))
         dev = next(self.parameters()).device if len(self.model) else None
         self.model.append(Model_Extractor(self.opt))
         if len(self.model) > 1:
@@ -592,6 +595,8 @@ class MRNNet(nn.Module):
         self.update_fc(hidden_size, nb_classes)
 
     def update_fc(self, hidden_size, nb_classes):
+        if not tasks_supported(len(self.model) + 1):
+            raise NotImplementedError(unsupported_task_count_message("MRNNet", len(self.model) + 1))
         dev = next(self.parameters()).device if len(self.model) else None
         self.model.append(Model(self.opt))
         self.model[-1].new_fc(hidden_size, nb_classes)

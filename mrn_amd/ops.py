@@ -11,6 +11,7 @@ import torch
 
 from ._lib import call
 from .modules.label_length import ctc_label_length_supported, ctc_uses_long_kernel, unsupported_label_length_message
+from .modules.task_count import router_uses_wide_kernels, tasks_supported, unsupported_task_count_message
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -1680,53 +1681,64 @@ def padded_rows(B, T, C, device):
     return torch.empty(B, T, ld, device=device, dtype=torch.float32)[:, :, :C]
 
 
-def fanin_fwd(logits, w):
+def _router_fn(name, I, wide):
+    """the router entry point for I experts: the 8-wide form up to 8, the 16-wide one from 9 to 16 (modules/task_count.py), chosen
+    here from I (no device-to-host sync); more than 16 are refused before any launch.  wide=True / False forces a form."""
+    if not tasks_supported(I):
+        raise NotImplementedError(unsupported_task_count_message("the router", I))
+    if wide is None:
+        wide = router_uses_wide_kernels(I)
+    return name + ("_wide_f32" if wide else "_f32")
+
+
+def fanin_fwd(logits, w, wide=None):
     I, ptrs, lds, cls = _fanin_args(logits)
     B, T, C = logits[-1].shape
     out = padded_rows(B, T, C, w.device)
-    call("mrn_fanin_fwd_f32", ptrs, lds, cls, I, _p(w), _p(out), out.stride(1), B, T, C, _stream())
+    call(_router_fn("mrn_fanin_fwd", I, wide), ptrs, lds, cls, I, _p(w), _p(out), out.stride(1), B, T, C, _stream())
     return out
 
 
-def fanin_bwd(logits, dout):
+def fanin_bwd(logits, dout, wide=None):
     I, ptrs, lds, cls = _fanin_args(logits)
     B, T, C = logits[-1].shape
     assert dout.stride(2) == 1 and dout.stride(0) == T * dout.stride(1)
     dw = torch.empty(B, I, device=dout.device, dtype=torch.float32)
     ws = torch.empty(B * T * I, device=dout.device, dtype=torch.float32)
-    call("mrn_fanin_bwd_f32", ptrs, lds, cls, I, _p(dout), dout.stride(1), _p(dw), _p(ws), B, T, C, _stream())
+    call(_router_fn("mrn_fanin_bwd", I, wide), ptrs, lds, cls, I, _p(dout), dout.stride(1), _p(dw), _p(ws), B, T, C, _stream())
     return dw
 
 
-def select_expert(logits, index):
+def select_expert(logits, index, wide=None):
     I, ptrs, lds, cls = _fanin_args(logits)
     B, T, C = logits[-1].shape
     out = torch.empty(B, T, C, device=index.device, dtype=torch.float32)
-    call("mrn_select_expert_f32", ptrs, lds, cls, I, _p(index), _p(out), C, B, T, C, _stream())
+    call(_router_fn("mrn_select_expert", I, wide), ptrs, lds, cls, I, _p(index), _p(out), C, B, T, C, _stream())
     return out
 
 
-def gate_tail_fwd(r, w_route, b_route, beta=1.0, hard=False):
+def gate_tail_fwd(r, w_route, b_route, beta=1.0, hard=False, wide=None):
     """r [B,P,I] -> (s, w) or (s, argmax)"""
     B, P, I = r.shape
+    fn = _router_fn("mrn_gate_tail_fwd", I, wide)
     s = torch.empty(B, I, device=r.device, dtype=torch.float32)
     if hard:
         am = torch.empty(B, device=r.device, dtype=torch.int64)
-        call("mrn_gate_tail_fwd_f32", _p(r), _p(w_route), _p(b_route), float(beta), _p(s), None, _p(am), B, P, I, _stream())
+        call(fn, _p(r), _p(w_route), _p(b_route), float(beta), _p(s), None, _p(am), B, P, I, _stream())
         return s, am
     w = torch.empty(B, I, device=r.device, dtype=torch.float32)
-    call("mrn_gate_tail_fwd_f32", _p(r), _p(w_route), _p(b_route), float(beta), _p(s), _p(w), None, B, P, I, _stream())
+    call(fn, _p(r), _p(w_route), _p(b_route), float(beta), _p(s), _p(w), None, B, P, I, _stream())
     return s, w
 
 
-def gate_tail_bwd(w, dw, r, w_route, beta=1.0):
+def gate_tail_bwd(w, dw, r, w_route, beta=1.0, wide=None):
     B, P, I = r.shape
+    fn = _router_fn("mrn_gate_tail_bwd", I, wide)
     ds = torch.empty(B, I, device=r.device, dtype=torch.float32)
     dr = torch.empty(B, P, I, device=r.device, dtype=torch.float32)
     dW = torch.empty(P, device=r.device, dtype=torch.float32)
     db = torch.empty(1, device=r.device, dtype=torch.float32)
-    call("mrn_gate_tail_bwd_f32", _p(w), _p(dw.contiguous()), _p(r), _p(w_route), float(beta), _p(ds), _p(dr), _p(dW), _p(db),
-         B, P, I, _stream())
+    call(fn, _p(w), _p(dw.contiguous()), _p(r), _p(w_route), float(beta), _p(ds), _p(dr), _p(dW), _p(db), B, P, I, _stream())
     return dr, dW, db
 
 
