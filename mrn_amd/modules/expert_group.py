@@ -20,7 +20,7 @@ import torch
 
 from .. import ops
 from ._nn import _pair, packed_weight, require_no_grad, to_nhwc
-from .geometry import geometry_supported, unsupported_geometry_message
+from .geometry import check_call, geometry_supported, unsupported_geometry_message
 
 
 EVAL_BN_FOLD = os.environ.get("MRN_EVAL_BN_FOLD", "1") != "0"      # eval-mode BatchNorm folded into the conv epilogue (A/B switch)
@@ -596,10 +596,11 @@ class BackboneGroup(_GroupedLinear):
         is the identity on the height-1 NHWC map of 32-pixel inputs; a taller final map is averaged over its rows by the last
         layer's BatchNorm-apply pass).  as_act: return the [G,B,1,T,C'] Act holding only the HL32 operand (what HeadsGroup's first
         grouped Linear consumes)."""
+        stages = self.experts[0].stages
+        check_call(stages["Trans"], stages["Feat"], image.shape[0], image.shape[2], image.shape[3])      # (before any launch)
         img = to_nhwc(image)
         B, H, W, C = img.shape
         self._nbt = []
-        stages = self.experts[0].stages
         self._height_mean = geometry_supported(stages["Feat"], H, W, stages["Trans"])     # (else a taller final map is refused below)
         if self.experts[0].stages["Trans"] == "TPS":
             x = self._tps(img)

@@ -20,7 +20,7 @@ from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
-from .geometry import geometry_supported, unsupported_geometry_message
+from .geometry import check_call, frames
 from .prediction import Attention
 from .sequence_modeling import BidirectionalLSTM
 from .task_count import tasks_supported, unsupported_task_count_message
@@ -71,6 +71,7 @@ class Model_Extractor(nn.Module):
 
     def visual(self, image):
         """Transformation + FeatureExtraction (+ the reference's permute / AdaptiveAvgPool / squeeze): [B,C,H,W] -> [B,T,C']"""
+        check_call(self.stages["Trans"], self.stages["Feat"], image.shape[0], image.shape[2], image.shape[3])     # (before any launch)
         with ops.batch_counters():                           # (the train-mode BatchNorm layers' num_batches_tracked: one launch)
             if not self.stages["Trans"] == "None":
                 image = self.Transformation(image)
@@ -79,9 +80,6 @@ class Model_Extractor(nn.Module):
         if H == 1:
             # permute(0,3,1,2) + AdaptiveAvgPool((None,1)) + squeeze(3) of the reference is the identity on [B,1,W,C]
             return to_nhwc(fmap).view(B, W, C)
-        Hi, Wi = image.shape[2], image.shape[3]
-        if not geometry_supported(self.stages["Feat"], Hi, Wi, self.stages["Trans"]):
-            raise NotImplementedError(unsupported_geometry_message(self.stages["Trans"], self.stages["Feat"], Hi, Wi, H))
         x = to_nhwc(fmap)                                    # 48- / 64-pixel inputs: the mean over the map's 2 / 3 rows
         if torch.is_grad_enabled() and x.requires_grad:
             return HeightMeanFn.apply(x)
@@ -226,6 +224,7 @@ class DERNet(Model):
         forward(..., frozen=handle).  They are frozen and in eval mode (reference il_modules/der.py:101-104,137-141), so their
         features for batch n+1 do not depend on the update of batch n: only the launch order changes.  None when the frozen
         extractors cannot run in lock-step (the caller then simply does not pass a handle)."""
+        check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         image = to_nhwc(image).permute(0, 3, 1, 2)
         plan = self._frozen_lockstep(image)
         if plan is None or plan[2] is None or not (self.frozen_stream and image.is_cuda):
@@ -245,6 +244,7 @@ class DERNet(Model):
         """[B,T,out_dim*N]: frozen extractors write straight into their channel slice (no torch.cat pass); two or more
         frozen extractors of one architecture run conv backbones and BiLSTMs in lock-step (modules/expert_group.py), on a side
         stream next to the trained extractor's forward -- or earlier still, through frozen_prefetch()"""
+        check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         image = to_nhwc(image).permute(0, 3, 1, 2)
         trainable = [needs_grad(ext, image) for ext in self.model]
         visuals, seq_done, buf, join = {}, set(), None, None
@@ -362,7 +362,7 @@ class MRNNet(nn.Module):
         self.fc = None
         self.opt = opt
         self.task_sizes = []
-        self.patch = {"VGG": 63, "SVTR": 64, "ResNet": 65}[opt.FeatureExtraction]
+        self.patch = frames(opt.FeatureExtraction, opt.imgW)      # router tokens = frames of an imgW-pixel line (63 / 64 / 65 at 256)
         self.router = "dm-router"
         self.layer_num = 1
         self.beta = 1
@@ -439,6 +439,7 @@ class MRNNet(nn.Module):
 
     def forward(self, image, cross=True, text=None, is_train=True, experts=None):
         """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier"""
+        check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
             features, index = self.model[-1](image, text, is_train)["predict"], None
         elif is_train == False:  # noqa: E712
@@ -458,6 +459,7 @@ class MRNNet(nn.Module):
         conversion), every output lives in the issuing stream's allocator pool, and the consumer waits on per-half
         events, so nothing orders the prefetch behind the router work of the previous step."""
         I = len(self.model)
+        check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         with torch.no_grad():
             group = self._backbone_group() if I > 1 else None
             halves = self._half_groups(is_train) if self._heads_group(group, is_train) is not None else None

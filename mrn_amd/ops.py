@@ -1384,6 +1384,15 @@ def attn_decoder_grouped(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_
 DECODER_X3 = os.environ.get("MRN_DECODER_X3", "1") == "1"     # attention decoder: the three recurrent products as split-fp16 x3
 
 
+def attn_decoder_whole_context(D, T, x3=None):
+    """does the decoder forward hold a 16-sample tile's whole [16, D] context in LDS (its single-launch form) for T frames, or does it
+    take the chunked WIDE form -- the rule of csrc/rnn.hip attn_launch, restated for callers and tests: 4 * (2 * 16 * 260 + 16 * (D + 4)
+    + 16 * T + 256) bytes (+ 1024 in the x3 form) within 160 KiB.  DERNet's D = 256 * G fits up to G = 7 at every supported width
+    (T <= 129), as at T = 65."""
+    x3 = DECODER_X3 if x3 is None else x3
+    return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) <= 160 * 1024
+
+
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):
     """(h2h.weight [H,H], rnn.weight_ih [4H, D+E], rnn.weight_hh [4H,H]) -> (three pack_fragment_major_h streams, w_inv float[3])"""
     a, b, c = pack_fragment_major_h(w_h2h.detach()), pack_fragment_major_h(w_ih.detach()[:, :D].contiguous()), pack_fragment_major_h(w_hh.detach())
