@@ -403,8 +403,10 @@ int mrn_attn_decoder_fwd_grouped_f32(const void* const* Hb, const void* const* H
  * dctx [B][S][D] (gradient of every step's context vector) and de [B][S][T] (gradient of every step's pre-softmax scores): the step
  * loop writes them, and two small launches behind it form dHb = sum_s alpha[s] (x) dctx[s] and dHproj = sum_s de[s] * w * (1 - tanh^2)
  * -- instead of a read-modify-write of both arrays in every step.
- * D must be a multiple of hidden (256). */
+ * D must be a multiple of hidden (256).  The two sums stage s_len * (T + 256) floats in LDS, so they run in
+ * ceil(S / mrn_attn_decoder_bwd_steps_per_launch(T)) launches each, the later ones adding to the first one's result. */
 int64_t mrn_attn_decoder_bwd_parts(int B);
+int64_t mrn_attn_decoder_bwd_steps_per_launch(int T);
 int mrn_attn_decoder_bwd_f32(const float* Hb, const float* Hproj, const float* alpha, const float* gates,
                              const float* cseq, const float* ctx, const float* hp, const float* dhid,
                              const float* w_score, const float* w_h2hT, const float* w_ih_ctxT, const float* w_hhT,

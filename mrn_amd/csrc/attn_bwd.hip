@@ -513,6 +513,9 @@ static int attn_bwd_vb(int B) {
   return 16;
 }
 
+// the deferred sums stage [s_len][T + 256] floats (HID = 256 = the dctx column block): steps per launch that fit in 160 KB
+static int attn_bwd_s_fit(int T) { return (int)((160 * 1024) / (sizeof(float) * (size_t)(T + 256))); }
+
 static int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st) {
   const bool x3 = p.w_inv != nullptr;
   const size_t lds = sizeof(float) * (BT * GLD + 3 * BT * HLD + 2 * BT * p.T + HID + NW * HID) + (x3 ? 1024 : 0);
@@ -523,8 +526,7 @@ static int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st) {
     hipFuncSetAttribute((const void*)attn_decoder_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  // the deferred sums stage [s_len][T + 256] floats (HID = 256 = the dctx column block): steps per launch that fit in 160 KB
-  const int s_fit = (int)((160 * 1024) / (sizeof(float) * (size_t)(p.T + 256)));
+  const int s_fit = attn_bwd_s_fit(p.T);
   MRN_CHECK_ARG(s_fit >= 1, "mrn_attn_decoder_bwd: T=%d beyond the deferred sums' LDS staging", p.T);
   const int s_chunk = p.S < s_fit ? p.S : s_fit;
   const size_t lds_s = sizeof(float) * (size_t)s_chunk * (p.T + 256);
@@ -554,6 +556,9 @@ static int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st) {
 
 // rows of the d w_score partial-sum buffer (= workgroups of mrn_attn_decoder_bwd_f32) for a batch of B
 MRN_EXPORT int64_t mrn_attn_decoder_bwd_parts(int B) { return B > 0 ? ceil_div(B, attn_bwd_vb(B)) : 0; }
+
+// steps of the deferred dHb / dHproj sums per launch at T frames (the launcher's own s_fit: S steps take ceil(S / this) launches each)
+MRN_EXPORT int64_t mrn_attn_decoder_bwd_steps_per_launch(int T) { return T > 0 ? attn_bwd_s_fit(T) : 0; }
 
 MRN_EXPORT int mrn_attn_decoder_bwd_f32(const float* Hb, const float* Hproj, const float* alpha, const float* gates,
                                         const float* cseq, const float* ctx, const float* hp, const float* dhid,

@@ -1284,7 +1284,8 @@ def test_maxpool_winograd_producer(ops, G, B, H, W, C, pool):
     assert torch.equal(f32, pf) and torch.equal(hl, ph) and torch.equal(v, v_ref)
 
 
-@pytest.mark.parametrize("C,G,rows_pg", [(64, 3, 700), (128, 2, 515), (64, 1, 256), (128, 6, 31), (256, 2, 515), (256, 3, 128)])
+@pytest.mark.parametrize("C,G,rows_pg", [(64, 3, 700), (128, 2, 515), (64, 1, 256), (128, 6, 31), (256, 2, 515), (256, 3, 128),
+                                         (256, 4, 129), (256, 5, 77), (64, 5, 333), (128, 4, 51)])
 def test_svtr_fused_mlp_matches_two_gemms(ops, C, G, rows_pg):
     """mrn_svtr_mlp_x3_f32 (fc1 -> GELU -> fc2 of G experts in one kernel, hidden activation in registers, chained MFMAs on the
     transposed problem with the hidden-permuted fc2 weights) against torch float64 and against the two grouped x3 GEMMs it replaces"""
@@ -1308,7 +1309,8 @@ def test_svtr_fused_mlp_matches_two_gemms(ops, C, G, rows_pg):
     assert_close("fused vs two GEMMs", y.view(G, rows_pg, C), y2.view(G, rows_pg, C), atol=2e-6, rtol=2e-6)
 
 
-@pytest.mark.parametrize("G,imgs_pg,N,with_drop", [(2, 3, 128, True), (3, 1, 100, False), (1, 5, 128, True)])
+@pytest.mark.parametrize("G,imgs_pg,N,with_drop", [(2, 3, 128, True), (3, 1, 100, False), (1, 5, 128, True),
+                                                   (4, 3, 75, True), (5, 1, 127, False), (5, 3, 128, True)])
 def test_svtr_fused_tail_c256(ops, G, imgs_pg, N, with_drop):
     """mrn_svtr_tail_x3_f32 (stage 3: proj -> DropPath-scaled residual add -> LayerNorm2 -> fc1 -> GELU -> fc2 of G experts in one launch;
     the LayerNorm output becomes fc1's operand in registers through the input-channel permutation of W1) against torch float64: the
@@ -1456,7 +1458,9 @@ def test_svtr_fused_mixer_column_major_walk(ops, C, N, H, G, B):
                                                               (128, 128, 1, 2, False, False, True), (128, 97, 1, 2, False, True, True),
                                                               (64, 512, 2, 3, True, True, True), (64, 512, 1, 2, False, False, False),
                                                               (64, 300, 1, 3, True, True, True), (64, 250, 1, 2, False, True, True),
-                                                              (128, 256, 2, 3, True, True, True), (128, 160, 1, 3, True, False, False)])
+                                                              (128, 256, 2, 3, True, True, True), (128, 160, 1, 3, True, False, False),
+                                                              (64, 200, 4, 3, True, True, True), (128, 100, 5, 2, True, True, True),
+                                                              (64, 512, 5, 3, False, True, False), (128, 256, 4, 3, True, False, True)])
 def test_svtr_fused_mixer(ops, C, N, G, B, masked, bias, with_pending):
     """mrn_svtr_mixer_x3_f32 (LayerNorm1 -> qkv -> local / global attention -> proj -> DropPath-scaled residual -> LayerNorm2 of G
     experts in one kernel) against float64 torch (modules/svtr.py:90-152, :196-201) and against the unfused chain it replaces"""
@@ -1481,7 +1485,8 @@ def test_svtr_fused_mixer(ops, C, N, G, B, masked, bias, with_pending):
 
 
 @pytest.mark.parametrize("N,G,B,masked,bias,with_pending", [(128, 2, 4, False, True, True), (128, 1, 2, True, True, False), (50, 2, 4, False, False, True),
-                                                          (100, 1, 6, True, True, True), (64, 1, 4, False, True, False)])
+                                                          (100, 1, 6, True, True, True), (64, 1, 4, False, True, False),
+                                                          (128, 4, 6, True, True, True), (50, 5, 4, False, True, False), (100, 5, 2, True, False, True)])
 def test_svtr_fused_attention_block_c256(ops, N, G, B, masked, bias, with_pending):
     """mrn_svtr_attention_block_x3_f32 (stage 3, C = 256: LayerNorm1 -> qkv -> attention in one kernel, the context as the HL32 operand of
     the proj Linear, t = x + drop * pending as the residual stream) against float64 torch and the unfused chain"""

@@ -127,13 +127,13 @@ def test_long_ctc_vs_torch(T, W, lengths, repeat_rows):
 
 
 @pytest.mark.parametrize("T", [63, 64])
-def test_long_ctc_vs_torch_full_batch(T):
+def test_long_ctc_vs_torch_full_batch(T, W=63):
     """B = 256 and C ~ 5000 (the bench's summed class counts), lengths 0..63 at W = 63"""
     from mrn_amd import ops
-    B, C, W = 256, 4998, 63
+    B, C = 256, 4998
     g = torch.Generator().manual_seed(T)
     lengths = torch.randint(0, W + 1, (B,), generator=g).tolist()
-    lengths[:4] = [0, 63, 32, 1]
+    lengths[:4] = [0, W, 32, 1]
     logits = rnd(B, T, C, seed=3 * T, scale=3.0)
     tg, tl = ctc_targets(lengths, W, C, seed=T, repeat_rows=(5,))
     ref, gref = torch_ctc(logits, tg, tl)
@@ -312,13 +312,13 @@ def test_loop_b_svtr3_vs_oracle_48():
 
 # ---- 5. the attention backward beyond the deferred sums' old LDS staging ------------------------------------------------------
 @pytest.mark.parametrize("B,D,S", [(5, 256, 126), (3, 1536, 128), (4, 256, 200)])
-def test_attention_decoder_backward_long(B, D, S):
+def test_attention_decoder_backward_long(B, D, S, T=65):
     """as test_kernels_gpu.py::test_attention_decoder_backward at T = 65: S * (T + 256) floats exceed 160 KB from S = 128 on,
     so dHb / dHproj are summed over chunks of the steps (S = 126: one launch, as before)"""
     from oracle import mrn_oracle as O
     from mrn_amd.modules.prediction import Attention
     import torch.nn as nn
-    T, Hd, C = 65, 256, 97
+    Hd, C = 256, 97
     att = Attention(D, Hd, C, nn.Linear(Hd, C))
     sd = {k: rnd(*v.shape, seed=140 + i, scale=0.08) for i, (k, v) in enumerate(att.state_dict().items())}
     sd["char_embeddings.weight"] = rnd(C, 256, seed=177)

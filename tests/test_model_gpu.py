@@ -447,7 +447,7 @@ def _trba6_b32_case(net, sd, crops, classes, B, I):
         assert float((am[same] == am32[same]).float().mean()) >= 0.99
 
 
-def _ctc_family_b32_case(kind, classes, crops, seed):
+def _ctc_family_b32_case(kind, classes, crops, seed, B=32):
     """CRNN / SVTR + MRN at the bench's class counts, 32 crops, production lock-step schedule, against the CPU oracle in fp32 (the
     reference's arithmetic, autograd through the router) and float64 (the conditioning yardstick).  No TPS stage in these families, so
     the plain 1e-4 band of north_star has to hold on U(-1,1) noise as well as on smooth crops; indices bit-exact."""
@@ -457,7 +457,7 @@ def _ctc_family_b32_case(kind, classes, crops, seed):
     from oracle import mrn_oracle as O
     from tests.helpers import oracle_dtype
     opt = make_opt(kind)
-    B, I = 32, len(classes)
+    I = len(classes)
     with contextlib.redirect_stdout(io.StringIO()):
         net = MRNNet(opt)
         for c in classes:
@@ -500,6 +500,7 @@ def _ctc_family_b32_case(kind, classes, crops, seed):
     with torch.no_grad():
         handle = net.experts_prefetch(image.cuda(), None, True)
     assert handle is not None
+    groups = net._half_groups(True)                     # the lock-step sub-groups this run took: returned to the caller
     out = net(image.cuda(), True, experts=handle)
     clf = Fn.ctc_loss(out["logits"], labels.cuda(), lens.cuda())
     loss = 15 * clf + Fn.cross_entropy(out["index"], domain.cuda(), -100)
@@ -543,6 +544,7 @@ def _ctc_family_b32_case(kind, classes, crops, seed):
     T = am.shape[1]
     assert conv.decode(am.numpy(), [T] * B) == O.CTCConverter(synthetic_characters(classes[-1] - 4)).decode(am32.numpy(), [T] * B)
     del net
+    return [hi - lo for lo, hi, _, _ in groups] if groups else None
 
 
 def set_drop_masks_from(net, masks):
@@ -1131,7 +1133,7 @@ def test_two_stream_half_groups_are_bit_identical(arch):
         assert torch.equal(outs[0][2][k], outs[1][2][k]), k
 
 
-def test_full_size_svtr_lockstep_matches_per_expert():
+def test_full_size_svtr_lockstep_matches_per_expert(classes=(40, 70, 97, 120, 150, 181)):
     """BASELINE config 4 at full size (6 SVTR experts, 256 images per GPU): the lock-step path (grouped x3 Linear layers, fused
     add + LayerNorm passes, x3 attention over 1536 samples, two half-groups on two streams) against the per-expert path with
     exact-fp32 attention products, same DropPath draws -- a size-independent consistency property, plus the row-stochastic
@@ -1140,7 +1142,6 @@ def test_full_size_svtr_lockstep_matches_per_expert():
     from mrn_amd.modules.model import MRNNet
     from mrn_amd.tools import weights as W
     opt = make_opt("svtr")
-    classes = (40, 70, 97, 120, 150, 181)
     B = 256
     image = torch.from_numpy(W.smooth_image("full_svtr", (B, 4, 32, 256), 3)).cuda()
     outs = []
@@ -1165,10 +1166,12 @@ def test_full_size_svtr_lockstep_matches_per_expert():
             ops.SVTR_ATTENTION_X3 = saved
         torch.cuda.synchronize()
         outs.append((o["logits"].clone(), o["index"].clone()))
+        groups = net._half_groups(True) if lockstep else groups
         del net
     assert_close("full-size logits", outs[0][0], outs[1][0], atol=2e-4, rtol=1e-4)
     assert_close("full-size routing weights", outs[0][1], outs[1][1], atol=2e-5, rtol=1e-4)
     assert_close("routing weights sum to 1", outs[0][1].sum(1), torch.ones(B), atol=1e-5)
+    return [hi - lo for lo, hi, _, _ in groups] if groups else None
 
 
 @pytest.mark.parametrize("arch", ["crnn", "trba"])

@@ -18,10 +18,10 @@ from tests.test_task_count_cpu import DER_CASE, MRN_CASES, STAGES, tasks_state_d
 pytestmark = pytest.mark.gpu
 
 
-def make_opt(kind, **kw):
-    o = types.SimpleNamespace(num_fiducial=20, imgH=32, imgW=256, input_channel=4, output_channel=512, hidden_size=256,
-                              batch_max_length=25, **kw)
-    o.Transformation, o.FeatureExtraction, o.SequenceModeling, o.Prediction = STAGES[kind]
+def make_opt(kind, imgH=32, imgW=256, bml=25, stages=None, **kw):
+    o = types.SimpleNamespace(num_fiducial=20, imgH=imgH, imgW=imgW, input_channel=4, output_channel=512, hidden_size=256,
+                              batch_max_length=bml, **kw)
+    o.Transformation, o.FeatureExtraction, o.SequenceModeling, o.Prediction = stages or STAGES[kind]
     return o
 
 
@@ -201,11 +201,11 @@ def test_wide_decoder_fwd_bwd_vs_float64(D, T):
 
 @pytest.mark.parametrize("D", [256, 1792])
 @pytest.mark.parametrize("x3", ["1", "0"])
-def test_wide_decoder_equals_single_launch_where_it_fits(D, x3, monkeypatch):
+def test_wide_decoder_equals_single_launch_where_it_fits(D, x3, monkeypatch, T=65):
     """at a D the single-launch form takes, the chunked form (forced) computes the same thing: the MFMAs run in the same order"""
     from mrn_amd import ops
     monkeypatch.setattr(ops, "DECODER_X3", x3 == "1")
-    B, T, nc = 37, 65, 41
+    B, nc = 37, 41
     att = _attention(D, nc, D).cuda()
     g = torch.Generator().manual_seed(D)
     H = (torch.randn(B, T, D, generator=g) * 0.5).cuda()
@@ -221,9 +221,9 @@ def test_wide_decoder_equals_single_launch_where_it_fits(D, x3, monkeypatch):
 
 
 # ---- 3. nets past eight tasks against the reference fixture and the oracle -----------------------------------------------------
-def _build(net_cls, kind, classes, der=False):
+def _build(net_cls, kind, classes, der=False, opt=None):
     from mrn_amd.modules import model as M
-    opt = make_opt(kind)
+    opt = opt or make_opt(kind)
     with contextlib.redirect_stdout(io.StringIO()):
         net = getattr(M, net_cls)(opt)
         for c in classes:
@@ -235,25 +235,28 @@ def _build(net_cls, kind, classes, der=False):
 
 
 @pytest.mark.parametrize("kind", ["crnn", "trba"])
-def test_mrn10_vs_reference_fixture(kind):
+def test_mrn10_vs_reference_fixture(kind, case=None):
     """loop B (fused logits, routing weights, router gradients), eval routing and greedy indices of a 10-expert MRNNet against the
     reference (B = 2).  Band: 1e-4, or for TRBA 3x the distance of the reference's fp32 result from float64 arithmetic on the same
-    quantity (as test_geometry_gpu.py::test_mrn2_vs_reference_fixture)"""
+    quantity (as test_geometry_gpu.py::test_mrn2_vs_reference_fixture).  case: another fixture's configuration -- golden (file),
+    prefix, classes, seed, targets (image, targets, lengths, domain), opt, cfg (the oracle's), masks (SVTR DropPath draws)"""
     from mrn_amd import functional as Fn
     from oracle import mrn_oracle as O
-    g = load_golden("many_tasks")
-    p = f"mrn_{kind}/"
-    classes, seed = MRN_CASES[kind]
+    from tests.test_model_gpu import set_drop_masks_from
+    case = case or {}
+    g = load_golden(case.get("golden", "many_tasks"))
+    p = case.get("prefix", f"mrn_{kind}/")
+    classes, seed = (case["classes"], case["seed"]) if case else MRN_CASES[kind]
     attn = kind == "trba"
     B = 2
-    image, tgt, lens, domain = tasks_targets(f"mrn_{kind}", attn, classes, seed)
+    image, tgt, lens, domain = case["targets"] if case else tasks_targets(f"mrn_{kind}", attn, classes, seed)
     text = tgt[:, :-1] if attn else None
-    net = _build("MRNNet", kind, classes)
+    net = _build("MRNNet", kind, classes, opt=case.get("opt"))
     net.load_state_dict(tasks_state_dict(g, p, seed), strict=True)
     ref64 = {}
     if attn:
         with oracle_dtype(torch.float64) as od, torch.no_grad():
-            ob = O.mrn_forward(od.cast(tasks_state_dict(g, p, seed)), O.Cfg(*STAGES[kind]), len(classes), image.double(), True, text, True,
+            ob = O.mrn_forward(od.cast(tasks_state_dict(g, p, seed)), case.get("cfg") or O.Cfg(*STAGES[kind]), len(classes), image.double(), True, text, True,
                                training=True)
         ref64 = {"stepB/weights": ob["index"], "stepB/logits": ob["logits"]}
 
@@ -270,6 +273,7 @@ def test_mrn10_vs_reference_fixture(kind):
     net = net.cuda().train()
     for n, q in net.named_parameters():
         q.requires_grad = not n.startswith("model.")
+    set_drop_masks_from(net, case.get("masks"))
     out = net(image.cuda(), True, None if text is None else text.cuda(), True)
     check("stepB/weights", out["index"], full=True)
     check("stepB/logits", out["logits"])
@@ -292,17 +296,18 @@ def test_mrn10_vs_reference_fixture(kind):
     assert float((oe["logits"].max(2)[1].cpu().numpy() == g[p + "eval/argmax"]).mean()) >= 0.99
 
 
-def test_dernet9_step_vs_reference_fixture():
+def test_dernet9_step_vs_reference_fixture(case=None):
     """one DER training step of a TRBA DERNet over 9 extractors (main head over D = 2304: the wide-context decoder, forward and
     backward) against the reference fixture and the oracle"""
     from mrn_amd import functional as Fn
     from oracle import mrn_oracle as O
     from tests.helpers import sub
-    g = load_golden("many_tasks")
-    p = "der_trba/"
-    classes, seed = DER_CASE
-    image, tgt, _, _ = tasks_targets("der_trba", True, classes, seed)
-    net = _build("DERNet", "trba", classes, der=True)
+    case = case or {}
+    g = load_golden(case.get("golden", "many_tasks"))
+    p = case.get("prefix", "der_trba/")
+    classes, seed = (case["classes"], case["seed"]) if case else DER_CASE
+    image, tgt, _, _ = case["targets"] if case else tasks_targets("der_trba", True, classes, seed)
+    net = _build("DERNet", "trba", classes, der=True, opt=case.get("opt"))
     net.load_state_dict(tasks_state_dict(g, p, seed), strict=True)
     net = net.cuda().train()
     for ext in list(net.model)[:-1]:
@@ -311,8 +316,8 @@ def test_dernet9_step_vs_reference_fixture():
             q.requires_grad = False
     out = net(image.cuda(), tgt[:, :-1].cuda())
     with oracle_dtype(torch.float64) as od, torch.no_grad():
-        o64 = O.dernet_forward(od.cast(tasks_state_dict(g, p, seed)), O.Cfg(*STAGES["trba"]), len(classes), image.double(), tgt[:, :-1],
-                               True, training=True)
+        o64 = O.dernet_forward(od.cast(tasks_state_dict(g, p, seed)), case.get("cfg") or O.Cfg(*STAGES["trba"]), len(classes), image.double(),
+                               tgt[:, :-1], True, training=True)
     for name, t in (("logits", out["logits"]), ("aux_logits", out["aux_logits"])):
         ref, r64 = g[p + name + "/sub"].astype(np.float64), sub(o64[name])[0].astype(np.float64)
         tol = max(1e-4 + 1e-4 * np.abs(ref).max(), 3 * np.abs(ref - r64).max())

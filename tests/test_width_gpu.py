@@ -26,17 +26,17 @@ GEOMETRIES = ((32, 128), (32, 512), (48, 320), (64, 192))
 WIDTH_SET = r"\{128, 192, 256, 320, 384, 448, 512\}"
 
 
-def make_opt(kind, imgH, imgW):
+def make_opt(kind, imgH, imgW, bml=25):
     o = types.SimpleNamespace(num_fiducial=20, imgH=imgH, imgW=imgW, input_channel=4, output_channel=512, hidden_size=256,
-                              batch_max_length=25)
+                              batch_max_length=bml)
     o.Transformation, o.FeatureExtraction, o.SequenceModeling, o.Prediction = CFG[kind]
     return o
 
 
-def build_mrn(kind, imgH, imgW, classes, seed):
+def build_mrn(kind, imgH, imgW, classes, seed, bml=25):
     from mrn_amd.modules.model import MRNNet
     from mrn_amd.tools import weights as W
-    opt = make_opt(kind, imgH, imgW)
+    opt = make_opt(kind, imgH, imgW, bml)
     with contextlib.redirect_stdout(io.StringIO()):
         net = MRNNet(opt)
         for c in classes:
@@ -47,16 +47,16 @@ def build_mrn(kind, imgH, imgW, classes, seed):
     return opt, net.cuda(), sd
 
 
-def inputs(kind, imgH, imgW, B, classes, seed):
+def inputs(kind, imgH, imgW, B, classes, seed, bml=25):
     from mrn_amd.tools import weights as W
     image = torch.from_numpy(W.smooth_image(f"width_{kind}_{imgH}x{imgW}", (B, 4, imgH, imgW), seed))
     if kind == "trba":
-        text = torch.from_numpy(W.randint(f"width_text_{imgH}x{imgW}", (B, 27), 4, classes[-1], seed))
+        text = torch.from_numpy(W.randint(f"width_text_{imgH}x{imgW}", (B, bml + 2), 4, classes[-1], seed))
         text[:, 0] = 2
         return image, text, None
-    lens = torch.from_numpy(W.randint(f"width_len_{imgH}x{imgW}", (B,), 1, 26, seed)).int()
-    labels = torch.from_numpy(W.randint(f"width_ctc_{imgH}x{imgW}", (B, 25), 4, classes[-1], seed))
-    labels[torch.arange(25)[None, :] >= lens[:, None]] = 1
+    lens = torch.from_numpy(W.randint(f"width_len_{imgH}x{imgW}", (B,), 1, bml + 1, seed)).int()
+    labels = torch.from_numpy(W.randint(f"width_ctc_{imgH}x{imgW}", (B, bml), 4, classes[-1], seed))
+    labels[torch.arange(bml)[None, :] >= lens[:, None]] = 1
     return image, labels, lens
 
 
@@ -275,17 +275,18 @@ def test_grouped_decoder_single_launch_form_at_T(ops, D, T, monkeypatch):
     assert torch.equal(ops.attn_decoder_grouped(Hb, Hproj, eproj, *args, w_inv=[p[3] for p in packs]), hid)
 
 
-def _labels_with_repeats(B, T, C, seed):
+def _labels_with_repeats(B, T, C, seed, W=25, lengths=None):
     """[B, 25] padded labels of 16 .. 25 characters built from runs of equal characters: sample b has `rep` adjacent equal pairs, chosen so
-    that L + rep sits at T - 1, T (both feasible), T + 1 or beyond (no alignment in T frames) in turn"""
+    that L + rep sits at T - 1, T (both feasible), T + 1 or beyond (no alignment in T frames) in turn.  W / lengths: another padded width
+    and the B label lengths (0 .. W) instead of 17 .. 25; a label of L characters can hold at most L - 1 pairs"""
     g = torch.Generator().manual_seed(seed)
-    tg = torch.ones(B, 25, dtype=torch.int64)
+    tg = torch.ones(B, W, dtype=torch.int64)
     tl = torch.zeros(B, dtype=torch.int32)
     need = []
     for b in range(B):
-        L = 17 + (b * 3) % 9                                            # 17 .. 25
-        rep = min(L - 1, max(0, T - L + (-1, 1, 0, 3, -6, 2)[b % 6]))
-        same = set(torch.randperm(L - 1, generator=g)[:rep].add(1).tolist())
+        L = 17 + (b * 3) % 9 if lengths is None else lengths[b]         # 17 .. 25
+        rep = min(max(L - 1, 0), max(0, T - L + (-1, 1, 0, 3, -6, 2)[b % 6]))
+        same = set(torch.randperm(max(L - 1, 0), generator=g)[:rep].add(1).tolist())
         ch = int(torch.randint(2, C, (1,), generator=g))
         for i in range(L):
             if i and i not in same:
@@ -629,7 +630,7 @@ def test_loop_a_crnn_gradients_vs_oracle_32x128():
         _grad_check(n, mine[n].grad, rg)
 
 
-def _oracle_trba_grads(sd0, image, labels_index, dtype, imgH, imgW):
+def _oracle_trba_grads(sd0, image, labels_index, dtype, imgH, imgW, bml=25):
     from oracle import mrn_oracle as O
     sd = {k: (v.clone().to(dtype) if v.is_floating_point() else v.clone()) for k, v in sd0.items()}
     names = [k for k in sd if k.startswith("model.0.") and sd[k].is_floating_point() and "running" not in k
@@ -638,7 +639,7 @@ def _oracle_trba_grads(sd0, image, labels_index, dtype, imgH, imgW):
     for k in list(sd):               # Prediction.generator.* aliases fc.*
         if k.startswith("model.0.Prediction.generator."):
             sd[k] = sd[k.replace("Prediction.generator.", "fc.")]
-    cfg = O.Cfg(*CFG["trba"], imgH=imgH, imgW=imgW)
+    cfg = O.Cfg(*CFG["trba"], imgH=imgH, imgW=imgW, batch_max_length=bml)
     old = O.tps_constants
     O.tps_constants = lambda *a: tuple(t.to(dtype) for t in old(*a))
     try:
@@ -652,18 +653,19 @@ def _oracle_trba_grads(sd0, image, labels_index, dtype, imgH, imgW):
     return names, grads, out.detach(), loss.detach()
 
 
-def test_loop_a_trba_gradients_vs_oracle_32x512():
+def test_loop_a_trba_gradients_vs_oracle_32x512(bml=25, B=3):
     """as tests/test_geometry_gpu.py::test_loop_a_trba_gradients_vs_oracle_64 (B = 3): judged against the float64 oracle, at least as
     close to it as 3x the reference's own fp32 arithmetic, floor 2e-3"""
     from mrn_amd import functional as Fn
-    opt, net, sd = build_mrn("trba", 32, 512, (41,), 12)
-    image, text, _ = inputs("trba", 32, 512, 3, (41,), 12)
-    names, g32, out32, loss32 = _oracle_trba_grads(sd, image, text, torch.float32, 32, 512)
-    _, g64, _, _ = _oracle_trba_grads(sd, image, text, torch.float64, 32, 512)
+    opt, net, sd = build_mrn("trba", 32, 512, (41,), 12, bml)
+    image, text, _ = inputs("trba", 32, 512, B, (41,), 12, bml)
+    names, g32, out32, loss32 = _oracle_trba_grads(sd, image, text, torch.float32, 32, 512, bml)
+    _, g64, _, _ = _oracle_trba_grads(sd, image, text, torch.float64, 32, 512, bml)
     net.train()
     for n, p in net.named_parameters():
         p.requires_grad = n.startswith("model.0.")
     preds = net.model[0](image.cuda(), text[:, :-1].cuda(), True)["predict"]
+    assert preds.shape[1] == bml + 1
     loss = Fn.cross_entropy(preds, text[:, 1:].cuda(), 1)
     assert_close("loop A logits", preds, out32, atol=1e-4)
     assert abs(loss.item() - loss32.item()) < 1e-4 * max(1.0, abs(loss32.item()))
@@ -683,26 +685,51 @@ def test_loop_a_trba_gradients_vs_oracle_32x512():
 
 # ---- 4. loop B: two router steps at 48 x 320 -------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["crnn", "trba"])
-def test_loop_b_two_steps_vs_oracle_48x320(kind):
+def test_loop_b_two_steps_vs_oracle_48x320(kind, imgH=48, imgW=320, classes=None, bml=25, f64_yardstick=False):
+    """f64_yardstick: the float64 oracle takes the same two steps next to the fp32 one.  A gradient or an Adam step on which the fp32
+    oracle is itself further from the float64 oracle than the band is judged against float64 instead, at 3x that distance (the rule of
+    tests/test_model_gpu.py::test_loop_a_trba_gradients_vs_oracle).  The first Adam step is lr * g / |g|, so an element whose gradient
+    is round-off sized takes a step of either sign, and the trajectories enter the second step with different weights."""
     from mrn_amd import functional as Fn
     from mrn_amd.optim import FlatAdam
     from oracle import mrn_oracle as O
-    classes = CLASSES[kind]
+    classes = classes or CLASSES[kind]
     I, B = len(classes), 8
-    opt, net, sd = build_mrn(kind, 48, 320, classes, 13)
+    opt, net, sd = build_mrn(kind, imgH, imgW, classes, 13, bml)
     net.train()
     for n, p in net.named_parameters():
         p.requires_grad = not n.startswith("model.")
     tr_names = [n for n, p in net.named_parameters() if p.requires_grad]
     adam = FlatAdam([p for n, p in net.named_parameters() if p.requires_grad], lr=5e-4)
-    cfg = O.Cfg(*CFG[kind], imgH=48, imgW=320)
+    cfg = O.Cfg(*CFG[kind], imgH=imgH, imgW=imgW, batch_max_length=bml)
     attn = kind == "trba"
     sd_ref = {k: v.clone() for k, v in sd.items()}
     state = [{"m": torch.zeros_like(sd_ref[n]), "v": torch.zeros_like(sd_ref[n])} for n in tr_names]
+    if f64_yardstick:
+        sd64 = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+        state64 = [{"m": torch.zeros_like(sd64[n]), "v": torch.zeros_like(sd64[n])} for n in tr_names]
+
+    def dist(a, b):
+        a, b = a.detach().cpu().double().numpy(), b.detach().double().numpy()
+        return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-12), np.abs(a - b).max() / max(np.abs(b).max(), 1e-12)
+
     for step in (1, 2):
-        image, tgt, lens = inputs(kind, 48, 320, B, classes, 100 + step)
+        image, tgt, lens = inputs(kind, imgH, imgW, B, classes, 100 + step, bml)
         domain = torch.from_numpy(np.arange(B) % I)
         text_in = tgt[:, :-1] if attn else None
+        g64, d64 = None, None
+        if f64_yardstick:
+            with oracle_dtype(torch.float64):
+                p64 = [sd64[n].requires_grad_(True) for n in tr_names]
+                o64 = O.mrn_forward(sd64, cfg, I, image.double(), True, text_in, True, training=True)
+                c64 = O.attn_ce_loss(o64["logits"], tgt) if attn else O.ctc_loss(o64["logits"], tgt, lens)
+                g64 = torch.autograd.grad(15 * c64 + F.cross_entropy(o64["index"], domain), p64)
+                for p in p64:
+                    p.requires_grad_(False)
+                b64 = [p.clone() for p in p64]
+                with torch.no_grad():
+                    O.clip_and_adam(p64, g64, state64, 5e-4, step)
+                d64 = [p - b for p, b in zip(p64, b64)]
         params = [sd_ref[n].requires_grad_(True) for n in tr_names]
         o = O.mrn_forward(sd_ref, cfg, I, image, True, text_in, True, training=True)
         clf = O.attn_ce_loss(o["logits"], tgt) if attn else O.ctc_loss(o["logits"], tgt, lens)
@@ -723,30 +750,47 @@ def test_loop_b_two_steps_vs_oracle_48x320(kind):
         assert abs(loss.item() - ref_loss.item()) <= 1e-4 * max(1.0, abs(ref_loss.item())) * (3 if attn else 1), (loss.item(), ref_loss.item())
         loss.backward()
         mine = dict(net.named_parameters())
-        for n, gr in zip(tr_names, ref_grads):
+        rel_l2, rel_max = (2e-3, 1e-2) if not attn else (5e-3, 2.5e-2)
+        for i, (n, gr) in enumerate(zip(tr_names, ref_grads)):
             if n == "route.bias":
                 continue
-            _grad_check(f"step {step} {n}", mine[n].grad, gr, rel_l2=2e-3 if not attn else 5e-3, rel_max=1e-2 if not attn else 2.5e-2)
+            if g64 is not None:
+                l2_ref, mx_ref = dist(gr, g64[i])
+                if l2_ref > rel_l2 or mx_ref > rel_max:
+                    l2, mx = dist(mine[n].grad, g64[i])
+                    assert l2 <= 3.0 * l2_ref and mx <= 3.0 * mx_ref, \
+                        f"step {step} {n}: HIP vs f64 {l2:.2e} / {mx:.2e}, torch-f32 vs f64 {l2_ref:.2e} / {mx_ref:.2e}"
+                    continue
+            _grad_check(f"step {step} {n}", mine[n].grad, gr, rel_l2=rel_l2, rel_max=rel_max)
         mine_before = {n: mine[n].detach().cpu().clone() for n in tr_names}
         adam.step(lr=5e-4, max_norm=5.0)
-        for n, gr in zip(tr_names, ref_grads):
+        for i, (n, gr) in enumerate(zip(tr_names, ref_grads)):
             if n == "route.bias":
                 continue          # (a round-off gradient's Adam step has a random sign)
             d_ref = sd_ref[n] - before[n]
             d_mine = mine[n].detach().cpu() - mine_before[n]
+            if d64 is not None:
+                rel_ref = float((d_ref.double() - d64[i]).norm() / d64[i].norm().clamp_min(1e-30))
+                if rel_ref > 5e-2:
+                    rel = float((d_mine.double() - d64[i]).norm() / d64[i].norm().clamp_min(1e-30))
+                    assert rel <= 3.0 * rel_ref, (step, n, rel, rel_ref)
+                    continue
             rel = float((d_mine - d_ref).norm() / d_ref.norm().clamp_min(1e-30))
             assert rel <= 5e-2, (step, n, rel)
 
 
 # ---- 5. DER: one step at 32 x 384 -------------------------------------------------------------------------------------------
-def test_dernet_step_vs_oracle_32x384():
+def test_dernet_step_vs_oracle_32x384(kind="crnn", imgW=384, classes=(40, 70), bml=25, frames=95):
+    """kind="trba": a gradient on which the fp32 oracle itself is further than the band (2e-3 relative L2, 1e-2 of the maximum) from the
+    float64 oracle is judged against float64 at 3x that distance instead.  Measured on the host for nine extractors at 32 x 512,
+    batch_max_length 120, B = 8: the fp32 oracle is 2.9e-2 .. 4.4e-2 (L2) from float64 on the newest extractor's TPS localisation network
+    and 4e-3 .. 2.7e-2 on its ResNet, while features / logits agree to 8.8e-5 / 4.7e-6"""
     from mrn_amd import functional as Fn
     from mrn_amd.modules.model import DERNet
     from mrn_amd.tools import weights as W
     from oracle import mrn_oracle as O
-    opt = make_opt("crnn", 32, 384)
-    classes = (40, 70)
-    B = 8
+    opt = make_opt(kind, 32, imgW, bml)
+    B, attn, last = 8, kind == "trba", f"model.{len(classes) - 1}."
     with contextlib.redirect_stdout(io.StringIO()):
         net = DERNet(opt)
         for c in classes:
@@ -756,37 +800,58 @@ def test_dernet_step_vs_oracle_32x384():
     W.fill_state_dict(net.state_dict(), seed=17)
     sd = {k: v.detach().clone() for k, v in net.state_dict().items()}
     net = net.cuda().train()
-    net.model[0].eval()                                         # DER's model_eval_and_train: the old extractor in eval mode, frozen
+    for ext in list(net.model)[:-1]:
+        ext.eval()                                              # DER's model_eval_and_train: the old extractors in eval mode, frozen
     for n, p in net.named_parameters():
-        p.requires_grad = not n.startswith("model.0.")
-    image, labels, lens = inputs("crnn", 32, 384, B, classes, 17)
-    cfg = O.Cfg(*CFG["crnn"], imgH=32, imgW=384)
+        p.requires_grad = n.startswith(last) or not n.startswith("model.")
+    image, labels, lens = inputs(kind, 32, imgW, B, classes, 17, bml)
+    text_in = labels[:, :-1] if attn else None
+    cfg = O.Cfg(*CFG[kind], imgH=32, imgW=imgW, batch_max_length=bml)
     names = [n for n, p in net.named_parameters() if p.requires_grad]
     params = [sd[n].requires_grad_(True) for n in names]
-    ref = O.dernet_forward(sd, cfg, len(classes), image, None, True, training=True)
-    assert ref["features"].shape[1] == 95
-    ref_loss = O.ctc_loss(ref["logits"], labels, lens)
+    ref = O.dernet_forward(sd, cfg, len(classes), image, text_in, True, training=True)
+    assert ref["features"].shape[1] == frames
+    ref_loss = O.attn_ce_loss(ref["logits"], labels) if attn else O.ctc_loss(ref["logits"], labels, lens)
     ref_grads = torch.autograd.grad(ref_loss, params, allow_unused=True)      # (the attention heads are unused by CTC)
-    out = net(image.cuda())
+    g64 = None
+    if attn:                                                    # TPS: the conditioning yardstick, as the TRBA loop-A tests
+        with oracle_dtype(torch.float64) as od:
+            sd64 = od.cast({k: v.detach() for k, v in sd.items()})
+            p64 = [sd64[n].requires_grad_(True) for n in names]
+            r64 = O.dernet_forward(sd64, cfg, len(classes), image.double(), text_in, True, training=True)
+            g64 = torch.autograd.grad(O.attn_ce_loss(r64["logits"], labels), p64, allow_unused=True)
+    out = net(image.cuda(), text_in.cuda()) if attn else net(image.cuda())
     assert_close("DER features", out["features"], ref["features"], atol=1e-4)
     assert_close("DER logits", out["logits"], ref["logits"], atol=1e-4)
     assert_close("DER aux logits", out["aux_logits"], ref["aux_logits"], atol=1e-4)
-    loss = Fn.ctc_loss(out["logits"], labels.cuda(), lens.cuda())
+    loss = Fn.cross_entropy(out["logits"], labels[:, 1:].cuda(), 1) if attn else Fn.ctc_loss(out["logits"], labels.cuda(), lens.cuda())
     assert abs(loss.item() - ref_loss.item()) < 1e-4 * max(1.0, abs(ref_loss.item()))
     loss.backward()
     mine = dict(net.named_parameters())
-    for n, rg in zip(names, ref_grads):
+    def dist(a, b):
+        a, b = a.detach().cpu().double().numpy(), b.detach().double().numpy()
+        return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-12), np.abs(a - b).max() / max(np.abs(b).max(), 1e-12)
+
+    for i, (n, rg) in enumerate(zip(names, ref_grads)):
         if rg is None or rg.abs().max() < 1e-9:
             continue
+        if g64 is not None:
+            l2_ref, mx_ref = dist(rg, g64[i])
+            if l2_ref > 2e-3 or mx_ref > 1e-2:
+                # the fp32 oracle itself misses the band against float64 here (a gradient through the TPS grid): judged against float64,
+                # at most 3x as far from it as the fp32 oracle (the rule of tests/test_model_gpu.py::test_loop_a_trba_gradients_vs_oracle)
+                l2, mx = dist(mine[n].grad, g64[i])
+                assert l2 <= 3.0 * l2_ref and mx <= 3.0 * mx_ref, f"{n}: HIP vs f64 {l2:.2e} / {mx:.2e}, torch-f32 vs f64 {l2_ref:.2e} / {mx_ref:.2e}"
+                continue
         _grad_check(n, mine[n].grad, rg, rel_l2=2e-3, rel_max=1e-2)
 
 
 # ---- 6. reduced mode (at 48 x 320 the 6-row maps have no plain-fp16 Winograd form and fall back, as at 48 x 256) ---------
 @pytest.mark.parametrize("kind", ["crnn", "trba"])
 @pytest.mark.parametrize("imgH,imgW", [(32, 128), (48, 320)])
-def test_reduced_mode_loop_b(kind, imgH, imgW):
+def test_reduced_mode_loop_b(kind, imgH, imgW, classes=None):
     from mrn_amd import ops
-    classes = CLASSES[kind]
+    classes = classes or CLASSES[kind]
     B = 8
     opt, net, sd = build_mrn(kind, imgH, imgW, classes, 19)
     net.train()
