@@ -155,6 +155,15 @@ int mrn_pack_weight_wino_hl32(const float* w_ohwi, void* out, int Cout, int Cin,
 int mrn_bn_apply_wino_grouped_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
                                   const float* shift, float* out_f32, void* out_hl32, void* out_wino, int G, int B, int H, int W,
                                   int C, int R, int relu, const float* prescale, void* stream);
+/* the closing pass of a BasicBlock with `downsample` (modules/feature_extraction.py:171-197, BasicBlock.forward: out += residual, where
+ * residual = downsample(x) = BatchNorm2d(conv1x1(x))): `residual` is the RAW fp32 output of the 1x1 convolution and res_scale / res_shift
+ * [G][C] the affine of its BatchNorm (mrn_bn_finalize_grouped_f32 / mrn_bn_eval_affine_grouped_f32); the pass adds residual * res_scale[g]
+ * + res_shift[g] -- the same fma, in the same order, as a separate mrn_bn_apply_grouped_f32 over the branch, which is no longer run.
+ * res_scale / res_shift NULL: mrn_bn_apply_wino_grouped_f32.  Not with residual_hl32. */
+int mrn_bn_apply_wino_grouped_res_affine_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
+                                             const float* shift, float* out_f32, void* out_hl32, void* out_wino, int G, int B, int H,
+                                             int W, int C, int R, int relu, const float* prescale, const float* res_scale,
+                                             const float* res_shift, void* stream);
 /* ... and MaxPool2d (mrn_maxpool_grouped_f32: BatchNorm-apply + ReLU fused on the input) as such a producer: the pooled map's groups of
  * R columns through B^T -> out_wino [G][B][Ho][ceil(Wo/R)][R+2][C/32][128 B]; the plain pooled fp32 / HL32 result optionally */
 int mrn_maxpool_wino_grouped_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32, void* out_hl32,
@@ -194,6 +203,12 @@ int mrn_pack_weight_wino_d16(const float* w_ohwi, void* out, int Cout, int Cin, 
 int mrn_bn_apply_wino_grouped_d16_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
                                       const float* shift, float* out_f32, void* out_hl32, void* out_wino_d16, int G, int B, int H,
                                       int W, int C, int relu, const float* prescale, int bf16, void* stream);
+/* ... with the pending BatchNorm affine of the downsample shortcut on the fp32 residual, as mrn_bn_apply_wino_grouped_res_affine_f32
+ * (modules/feature_extraction.py:171-197, BasicBlock.forward with `downsample`) */
+int mrn_bn_apply_wino_grouped_d16_res_affine_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
+                                                 const float* shift, float* out_f32, void* out_hl32, void* out_wino_d16, int G, int B,
+                                                 int H, int W, int C, int relu, const float* prescale, int bf16,
+                                                 const float* res_scale, const float* res_shift, void* stream);
 int mrn_maxpool_wino_grouped_d16_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32, void* out_hl32,
                                      void* out_wino_d16, int G, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph,
                                      int pw, int bf16, void* stream);
@@ -255,6 +270,13 @@ int mrn_bn_eval_affine_grouped_f32(const void* const* ptrs, int G, int C, float 
 int mrn_bn_apply_grouped_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
                              const float* shift, float* out_f32, void* out_hl32, int G, int64_t rows_per_group, int C,
                              int relu, void* stream);
+/* mrn_bn_apply_grouped_f32 as the closing pass of a BasicBlock with `downsample` (modules/feature_extraction.py:171-197,
+ * BasicBlock.forward) on maps the Winograd form does not take: residual = the raw fp32 output of the 1x1 downsample convolution,
+ * res_scale / res_shift [G][C] = the affine of its BatchNorm, applied here as residual * res_scale[g] + res_shift[g] before the add
+ * (see mrn_bn_apply_wino_grouped_res_affine_f32).  res_scale / res_shift NULL: mrn_bn_apply_grouped_f32.  Not with residual_hl32. */
+int mrn_bn_apply_grouped_res_affine_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
+                                        const float* shift, float* out_f32, void* out_hl32, int G, int64_t rows_per_group, int C,
+                                        int relu, const float* res_scale, const float* res_shift, void* stream);
 int mrn_maxpool_grouped_f32(const float* x, const float* scale, const float* shift, int relu, float* out_f32,
                             void* out_hl32, int G, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                             void* stream);

@@ -171,9 +171,14 @@ __device__ __forceinline__ F8 load_hl(const unsigned char* hl, long row, int C, 
   return v;
 }
 
-// out = act(y * scale[g][c] + shift[g][c] (+ res)); one lane = 8 channels; the residual comes as fp32 or as an HL32 image
+// out = act(y * scale[g][c] + shift[g][c] (+ res)); one lane = 8 channels; the residual comes as fp32 or as an HL32 image.
+// res_scale / res_shift [G][C] (or NULL): the fp32 residual is the RAW output of the block's 1x1 downsample conv and its BatchNorm
+// affine is applied here, res * res_scale[g][c] + res_shift[g][c] -- the same fma the separate pass ran, without its round trip
+// (AFFINE: an instantiation of its own, so that the pass without it stays the code it was)
+template <bool AFFINE>
 __global__ __launch_bounds__(256) void bn_apply_grouped_kernel(const float* __restrict__ y, const float* __restrict__ res,
                                                                const unsigned char* __restrict__ res_hl,
+                                                               const float* __restrict__ res_scale, const float* __restrict__ res_shift,
                                                                const float* __restrict__ scale, const float* __restrict__ shift,
                                                                float* __restrict__ out, unsigned char* __restrict__ out_hl,
                                                                long rows_per_group, long n8, int C, int relu) {
@@ -192,7 +197,15 @@ __global__ __launch_bounds__(256) void bn_apply_grouped_kernel(const float* __re
       }
     }
     if (res || res_hl) {
-      const F8 r = res ? load8(res + i * 8) : load_hl(res_hl, row, C, c8);
+      F8 r = res ? load8(res + i * 8) : load_hl(res_hl, row, C, c8);
+      if constexpr (AFFINE) {
+        const F8 rs = load8(res_scale + (long)g * C + c8 * 8), rt = load8(res_shift + (long)g * C + c8 * 8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          r.a[e] = r.a[e] * rs.a[e] + rt.a[e];
+          r.b[e] = r.b[e] * rs.b[e] + rt.b[e];
+        }
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v.a[e] += r.a[e];
@@ -222,10 +235,12 @@ __global__ __launch_bounds__(256) void bn_apply_grouped_kernel(const float* __re
 // R*q - 1 .. R*q + R (zero outside the row: the convolution's padding), applies the input transform B^T in fp32 and writes the
 // R + 2 components as HL32 lines [image row][group][component][C/32][128 B]; the plain fp32 / HL32 results of the group's own R
 // columns are written too when asked for (identity-shortcut source of the next block).  Neighbouring groups re-read two
-// columns each (cache hits: they are processed by neighbouring waves).
-template <int R>
+// columns each (cache hits: they are processed by neighbouring waves).  res_scale / res_shift: as bn_apply_grouped_kernel.
+template <int R, bool AFFINE>
 __global__ __launch_bounds__(256) void bn_apply_wino_grouped_kernel(const float* __restrict__ y, const float* __restrict__ res,
                                                                     const unsigned char* __restrict__ res_hl,
+                                                                    const float* __restrict__ res_scale,
+                                                                    const float* __restrict__ res_shift,
                                                                     const float* __restrict__ scale, const float* __restrict__ shift,
                                                                     float* __restrict__ out, unsigned char* __restrict__ out_hl,
                                                                     unsigned char* __restrict__ out_v, long imgrows_per_group, int W,
@@ -245,6 +260,11 @@ __global__ __launch_bounds__(256) void bn_apply_wino_grouped_kernel(const float*
       sc = load8(scale + (long)g * C + c8 * 8);
       sh = load8(shift + (long)g * C + c8 * 8);
     }
+    F8 rs, rt;
+    if constexpr (AFFINE) {
+      rs = load8(res_scale + (long)g * C + c8 * 8);
+      rt = load8(res_shift + (long)g * C + c8 * 8);
+    }
     F8 d[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
@@ -260,7 +280,14 @@ __global__ __launch_bounds__(256) void bn_apply_wino_grouped_kernel(const float*
           }
         }
         if (res || res_hl) {
-          const F8 r = res ? load8(res + (row * C8 + c8) * 8) : load_hl(res_hl, row, C, c8);
+          F8 r = res ? load8(res + (row * C8 + c8) * 8) : load_hl(res_hl, row, C, c8);
+          if constexpr (AFFINE) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              r.a[e] = r.a[e] * rs.a[e] + rt.a[e];
+              r.b[e] = r.b[e] * rs.b[e] + rt.b[e];
+            }
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             v.a[e] += r.a[e];
@@ -708,46 +735,65 @@ MRN_EXPORT int mrn_bn_eval_affine_grouped_f32(const void* const* ptrs, int G, in
 // out = act(y * scale[g] + shift[g] (+ residual)) over [G][rows_per_group][C]; scale/shift may be NULL (identity); the
 // residual is given as fp32 (residual) or as an HL32 image (residual_hl32: hi + lo is added, 22 significand bits);
 // out_f32 and / or out_hl32 (C % 32 == 0) receive the result; out_f32 may alias y.  relu: 0 / 1.
-MRN_EXPORT int mrn_bn_apply_grouped_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
-                                        const float* shift, float* out_f32, void* out_hl32, int G, int64_t rows_per_group,
-                                        int C, int relu, void* stream) {
+// res_scale / res_shift [G][C] (both or neither; only with the fp32 residual): the residual is taken as residual * res_scale[g] +
+// res_shift[g] -- the pending BatchNorm affine of a downsample shortcut whose raw conv output is passed as `residual`.
+static int bn_apply_launch(const float* y, const float* residual, const void* residual_hl32, const float* res_scale,
+                           const float* res_shift, const float* scale, const float* shift, float* out_f32, void* out_hl32, int G,
+                           int64_t rows_per_group, int C, int relu, void* stream) {
   MRN_CHECK_ARG(y && (out_f32 || out_hl32) && C % 8 == 0 && (!(out_hl32 || residual_hl32) || C % 32 == 0) &&
                     (!scale == !shift) && !(residual && residual_hl32),
                 "mrn_bn_apply_grouped_f32: bad operands (C=%d)", C);
+  MRN_CHECK_ARG((!res_scale == !res_shift) && (!res_scale || (residual && !residual_hl32)),
+                "mrn_bn_apply_grouped_res_affine_f32: the residual affine needs both vectors and the fp32 residual (C=%d)", C);
   const long n8 = (long)G * rows_per_group * (C / 8);
   if (n8 == 0) return MRN_OK;
   long grid = (n8 + 255) / 256;
   if (grid > 32768) grid = 32768;
-  hipLaunchKernelGGL(bn_apply_grouped_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, y, residual,
-                     (const unsigned char*)residual_hl32, scale, shift,
+  auto kernel = res_scale ? bn_apply_grouped_kernel<true> : bn_apply_grouped_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, y, residual,
+                     (const unsigned char*)residual_hl32, res_scale, res_shift, scale, shift,
                      out_f32, (unsigned char*)out_hl32, (long)rows_per_group, n8, C, relu);
   MRN_LAUNCH_CHECK("bn_apply_grouped");
   return MRN_OK;
 }
 
+MRN_EXPORT int mrn_bn_apply_grouped_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
+                                        const float* shift, float* out_f32, void* out_hl32, int G, int64_t rows_per_group,
+                                        int C, int relu, void* stream) {
+  return bn_apply_launch(y, residual, residual_hl32, nullptr, nullptr, scale, shift, out_f32, out_hl32, G, rows_per_group, C, relu, stream);
+}
+
+MRN_EXPORT int mrn_bn_apply_grouped_res_affine_f32(const float* y, const float* residual, const void* residual_hl32,
+                                                   const float* scale, const float* shift, float* out_f32, void* out_hl32, int G,
+                                                   int64_t rows_per_group, int C, int relu, const float* res_scale,
+                                                   const float* res_shift, void* stream) {
+  return bn_apply_launch(y, residual, residual_hl32, res_scale, res_shift, scale, shift, out_f32, out_hl32, G, rows_per_group, C, relu,
+                         stream);
+}
+
 // mrn_bn_apply_grouped_f32 as the producer of a Winograd F(R,3) convolution (mrn_conv2d_x3_wino_hl32): y [G][B][H][W][C];
 // out_wino [G][B][H][ceil(W/R)][R+2][C/32][128 B] receives B^T applied to out = act(y * scale + shift (+ residual)) per group of R
 // columns (zero padding outside the row); out_f32 (must NOT alias y: neighbouring groups re-read y) / out_hl32 optionally
-// receive the plain result.
-static int bn_apply_wino_launch(const float* y, const float* residual, const void* residual_hl32, const float* scale,
-                                const float* shift, float* out_f32, void* out_hl32, void* out_wino, int G, int B, int H,
-                                int W, int C, int R, int relu, const float* prescale, int dense, void* stream) {
+// receive the plain result.  res_scale / res_shift: as mrn_bn_apply_grouped_res_affine_f32.
+static int bn_apply_wino_launch(const float* y, const float* residual, const void* residual_hl32, const float* res_scale,
+                                const float* res_shift, const float* scale, const float* shift, float* out_f32, void* out_hl32,
+                                void* out_wino, int G, int B, int H, int W, int C, int R, int relu, const float* prescale, int dense,
+                                void* stream) {
   MRN_CHECK_ARG(y && out_wino && C % (dense ? 64 : 32) == 0 && (!scale == !shift) && !(residual && residual_hl32) && (R == 2 || R == 4) &&
                     out_f32 != y && (uintptr_t)out_wino % 128 == 0,
                 "mrn_bn_apply_wino_grouped_f32: bad operands (C=%d R=%d)", C, R);
+  MRN_CHECK_ARG((!res_scale == !res_shift) && (!res_scale || (residual && !residual_hl32)),
+                "mrn_bn_apply_wino_grouped_res_affine_f32: the residual affine needs both vectors and the fp32 residual (C=%d)", C);
   const int Wq = (W + R - 1) / R;
   const long n8 = (long)G * B * H * Wq * (C / 8);
   if (n8 == 0) return MRN_OK;
   long grid = (n8 + 255) / 256;
   if (grid > 32768) grid = 32768;
-  if (R == 4)
-    hipLaunchKernelGGL(bn_apply_wino_grouped_kernel<4>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, y, residual,
-                       (const unsigned char*)residual_hl32, scale, shift, out_f32, (unsigned char*)out_hl32, (unsigned char*)out_wino,
-                       (long)B * H, W, Wq, n8, C, relu, prescale, dense);
-  else
-    hipLaunchKernelGGL(bn_apply_wino_grouped_kernel<2>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, y, residual,
-                       (const unsigned char*)residual_hl32, scale, shift, out_f32, (unsigned char*)out_hl32, (unsigned char*)out_wino,
-                       (long)B * H, W, Wq, n8, C, relu, prescale, dense);
+  auto kernel = R == 4 ? (res_scale ? bn_apply_wino_grouped_kernel<4, true> : bn_apply_wino_grouped_kernel<4, false>)
+                       : (res_scale ? bn_apply_wino_grouped_kernel<2, true> : bn_apply_wino_grouped_kernel<2, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, y, residual, (const unsigned char*)residual_hl32,
+                     res_scale, res_shift, scale, shift, out_f32, (unsigned char*)out_hl32, (unsigned char*)out_wino, (long)B * H, W, Wq,
+                     n8, C, relu, prescale, dense);
   MRN_LAUNCH_CHECK("bn_apply_wino_grouped");
   return MRN_OK;
 }
@@ -755,7 +801,17 @@ static int bn_apply_wino_launch(const float* y, const float* residual, const voi
 MRN_EXPORT int mrn_bn_apply_wino_grouped_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
                                              const float* shift, float* out_f32, void* out_hl32, void* out_wino, int G, int B, int H,
                                              int W, int C, int R, int relu, const float* prescale, void* stream) {
-  return bn_apply_wino_launch(y, residual, residual_hl32, scale, shift, out_f32, out_hl32, out_wino, G, B, H, W, C, R, relu, prescale, 0, stream);
+  return bn_apply_wino_launch(y, residual, residual_hl32, nullptr, nullptr, scale, shift, out_f32, out_hl32, out_wino, G, B, H, W, C, R, relu,
+                              prescale, 0, stream);
+}
+
+MRN_EXPORT int mrn_bn_apply_wino_grouped_res_affine_f32(const float* y, const float* residual, const void* residual_hl32,
+                                                        const float* scale, const float* shift, float* out_f32, void* out_hl32,
+                                                        void* out_wino, int G, int B, int H, int W, int C, int R, int relu,
+                                                        const float* prescale, const float* res_scale, const float* res_shift,
+                                                        void* stream) {
+  return bn_apply_wino_launch(y, residual, residual_hl32, res_scale, res_shift, scale, shift, out_f32, out_hl32, out_wino, G, B, H, W, C, R,
+                              relu, prescale, 0, stream);
 }
 
 // mrn_bn_apply_wino_grouped_f32 for the reduced-precision mode (one fp16 product per term): out_wino_d16 [G][B][H][ceil(W/4)][6][C/64][128 B]
@@ -764,7 +820,17 @@ MRN_EXPORT int mrn_bn_apply_wino_grouped_f32(const float* y, const float* residu
 MRN_EXPORT int mrn_bn_apply_wino_grouped_d16_f32(const float* y, const float* residual, const void* residual_hl32, const float* scale,
                                                  const float* shift, float* out_f32, void* out_hl32, void* out_wino_d16, int G, int B, int H,
                                                  int W, int C, int relu, const float* prescale, int bf16, void* stream) {
-  return bn_apply_wino_launch(y, residual, residual_hl32, scale, shift, out_f32, out_hl32, out_wino_d16, G, B, H, W, C, 4, relu, prescale, bf16 ? 2 : 1, stream);
+  return bn_apply_wino_launch(y, residual, residual_hl32, nullptr, nullptr, scale, shift, out_f32, out_hl32, out_wino_d16, G, B, H, W, C, 4,
+                              relu, prescale, bf16 ? 2 : 1, stream);
+}
+
+MRN_EXPORT int mrn_bn_apply_wino_grouped_d16_res_affine_f32(const float* y, const float* residual, const void* residual_hl32,
+                                                            const float* scale, const float* shift, float* out_f32, void* out_hl32,
+                                                            void* out_wino_d16, int G, int B, int H, int W, int C, int relu,
+                                                            const float* prescale, int bf16, const float* res_scale,
+                                                            const float* res_shift, void* stream) {
+  return bn_apply_wino_launch(y, residual, residual_hl32, res_scale, res_shift, scale, shift, out_f32, out_hl32, out_wino_d16, G, B, H, W,
+                              C, 4, relu, prescale, bf16 ? 2 : 1, stream);
 }
 
 // MaxPool2d over x [G][B][H][W][C] with the BatchNorm-apply (+ ReLU) of group g fused on the input (scale/shift [G][C] or NULL)

@@ -29,6 +29,9 @@ EVAL_BN_FOLD = os.environ.get("MRN_EVAL_BN_FOLD", "1") != "0"      # eval-mode B
 SVTR_GROUPED_EMBED = os.environ.get("MRN_SVTR_EMBED", "grouped") == "grouped"      # SVTR PatchEmbed of the frozen experts in lock-step
 TPS_WINO = os.environ.get("MRN_TPS_WINO", "1") == "1"          # TPS localisation network: convs 3 and 4 on the Winograd form
 EVAL_WINO = os.environ.get("MRN_EVAL_WINO", "1") != "0"
+# the BatchNorm of a BasicBlock's 1x1 downsample shortcut applied by the block's closing pass instead of a pass of its own (A/B switch:
+# 0 = the branch is materialised by its own BatchNorm-apply pass, 8 B / element more traffic, same bits)
+SHORTCUT_BN_FOLD = os.environ.get("MRN_SHORTCUT_BN_FOLD", "1") != "0"
 RESIDUAL_FROM_F32 = bool(int(os.environ.get("MRN_RESIDUAL_F32", "0")))      # True: keep an fp32 copy of every identity-shortcut source (one extra 4 B/element write)
 
 
@@ -40,9 +43,10 @@ def conv_out_rows(H, pool):
 class Act:
     """A [G,B,H,W,C] activation stack: fp32 tensor and / or HL32 bytes.  shared=True: one [B,H,W,C] input for all groups."""
 
-    def __init__(self, shape, f32=None, hl=None, shared=False, wino=None, wino_R=0):
+    def __init__(self, shape, f32=None, hl=None, shared=False, wino=None, wino_R=0, affine=None):
         self.shape = tuple(shape)          # (G, B, H, W, C)
         self.f32 = f32
+        self.affine = affine               # pending BatchNorm (scale, shift) [G,C]: f32 is the RAW conv output (layer(defer_affine=True))
         self.hl = hl
         self.shared = shared
         self.wino = wino                   # Winograd-domain operand bytes [G][B][H][ceil(W/R)][R+2][C/32][128] (ops.bn_apply_wino_grouped)
@@ -161,12 +165,20 @@ class BackboneGroup(_GroupedLinear):
 
     # ---- one conv (+BN) (+residual) (+ReLU) (+pool) layer for all groups ----------------------------------------------
     def layer(self, x, convs, bns=None, relu=True, residual=None, pool=None, want_f32=False, want_hl=True, want_wino=0, gelu=False,
-              height_mean=False):
+              height_mean=False, defer_affine=False):
         """want_wino = R: the result also as the Winograd-domain operand of a following 3x3 conv (only from the BatchNorm-apply
         pass, i.e. with bns and no pool); a layer whose INPUT carries x.wino and qualifies (wino_for) runs as F(R,3).
         gelu: BatchNorm -> GELU instead of ReLU (SVTR PatchEmbed; plain BatchNorm-apply pass only).
         height_mean: the last layer of the visual stage -- a map of more than one row leaves as its mean over the rows (reference
-        modules/model.py:92), taken by the pass that applies the BatchNorm + ReLU to the raw conv output: a [G,B,1,W,C] Act"""
+        modules/model.py:92), taken by the pass that applies the BatchNorm + ReLU to the raw conv output: a [G,B,1,W,C] Act.
+        defer_affine: the downsample branch of a BasicBlock -- instead of running its BatchNorm-apply pass the layer returns the raw
+        conv output with the (scale, shift) pending (Act.affine); the pass of the layer that takes it as `residual` applies them.
+        Only a bare BatchNorm qualifies (no ReLU, pool, HL32 / Winograd operand, height mean or residual of its own); an eval-mode
+        BatchNorm the one-launch conv epilogue takes (EVAL_BN_FOLD) has no separate pass and comes back materialised as before"""
+        if defer_affine and (bns is None or relu or pool is not None or want_hl or want_wino or height_mean or gelu or residual is not None
+                             or not want_f32):
+            raise ValueError("layer(defer_affine=True) takes a BatchNorm layer with relu=False, want_f32=True and no pool, want_hl, "
+                             "want_wino, height_mean, gelu or residual")
         if gelu:
             assert bns is not None and bns[0].training and pool is None and not want_wino and residual is None
             relu = True
@@ -183,6 +195,7 @@ class BackboneGroup(_GroupedLinear):
         stats = None
         res = residual.f32 if residual is not None else None
         res_hl = residual.hl if residual is not None and res is None else None
+        res_affine = residual.affine if residual is not None else None
         use_wino = x.wino is not None and x.wino_R == self.wino_for(c0, bns, H)
         if want_wino and not ops.wino_rows_fit(conv_out_rows(Ho, pool)):
             want_wino, want_hl = 0, True             # (the consumer runs on the plain operand: a 6-row map in the reduced mode, imgH = 48)
@@ -193,8 +206,13 @@ class BackboneGroup(_GroupedLinear):
         #  epilogue and the running-statistics affine on the pooled map beat the one-launch fold + a pooling pass over the full map)
         patch_pool = (pool == ((2, 2), (2, 2), (0, 0)) and Ho % 2 == 0 and Wo % 2 == 0
                       and ops.patch_conv_supported(ksize, stride, padding, Cin, Cout))
-        if (EVAL_BN_FOLD and bns is not None and not training and Cin % 32 == 0 and Cout >= 64 and Cout % 32 == 0
-                and (want_hl or res_hl is None) and not use_wino and not want_wino and not patch_pool and not height_mean):
+        eval_fold = (EVAL_BN_FOLD and bns is not None and not training and Cin % 32 == 0 and Cout >= 64 and Cout % 32 == 0
+                     and (want_hl or res_hl is None) and not use_wino and not want_wino and not patch_pool and not height_mean)
+        if res_affine is not None and (eval_fold or pool is not None or height_mean):
+            # this layer does not end in a BatchNorm-apply pass that takes the pending affine: the shortcut gets its own pass after all
+            ops.bn_apply_grouped(res, res_affine[0], res_affine[1], relu=False, want_f32=True, want_hl=False)
+            residual.affine = res_affine = None
+        if eval_fold:
             # frozen experts in EVAL mode (DERNet's old extractors, LwF's previous network, validation): the BatchNorm is a fixed
             # per-channel affine, so conv -> BN -> (+ identity) -> ReLU -> operand split is ONE launch: the affine, the shortcut
             # and the activation run in the conv epilogue, which writes the HL32 operand of the next layer directly
@@ -292,12 +310,14 @@ class BackboneGroup(_GroupedLinear):
             return Act((G, B, 1, Wo, Cout), None if f32 is None else f32.view(G, B, 1, Wo, Cout), hl)
         if scale is None and res is None and res_hl is None and not post_relu and not want_hl and not want_wino:
             return Act((G, B, Ho, Wo, Cout), y, None)
+        if defer_affine:                             # (the statistics are final and the running buffers updated: only the apply pass waits)
+            return Act((G, B, Ho, Wo, Cout), y, None, affine=(scale, shift))
         if want_wino:
             f32, hl, v = ops.bn_apply_wino_grouped(y, scale, shift, want_wino, relu=post_relu, residual=res, residual_hl=res_hl,
-                                                   want_f32=want_f32, want_hl=want_hl)
+                                                   want_f32=want_f32, want_hl=want_hl, residual_affine=res_affine)
             return Act((G, B, Ho, Wo, Cout), f32, hl, wino=v, wino_R=want_wino)
         f32, hl = ops.bn_apply_grouped(y, scale, shift, relu=2 if (gelu and post_relu) else post_relu, residual=res, want_f32=want_f32,
-                                       want_hl=want_hl, residual_hl=res_hl)
+                                       want_hl=want_hl, residual_hl=res_hl, residual_affine=res_affine)
         return Act((G, B, Ho, Wo, Cout), f32, hl)
 
     # ---- network programs ---------------------------------------------------------------------------------------
@@ -307,8 +327,9 @@ class BackboneGroup(_GroupedLinear):
         w2 = self.wino_for(b0.conv2, [b.bn2 for b in blocks])
         out = self.layer(x, [b.conv1 for b in blocks], [b.bn1 for b in blocks], want_wino=w2, want_hl=not w2)
         if b0.downsample is not None:
+            # (the branch's BatchNorm is applied by the closing pass below, which reads the raw 1x1 conv output as its residual)
             res = self.layer(x, [b.downsample[0] for b in blocks], [b.downsample[1] for b in blocks], relu=False,
-                             want_f32=True, want_hl=False)
+                             want_f32=True, want_hl=False, defer_affine=SHORTCUT_BN_FOLD)
         else:
             res = x
             assert res.f32 is not None or res.hl is not None

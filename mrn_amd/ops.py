@@ -708,9 +708,10 @@ def pack_weights_wino(ws, R, scale=None, dense=None):
 
 
 def bn_apply_wino_grouped(y, scale, shift, R, relu=True, residual=None, residual_hl=None, want_f32=False, want_hl=False, prescale=None,
-                          dense=None):
+                          dense=None, residual_affine=None):
     """y [G,B,H,W,C] fp32 -> (fp32 result (a NEW tensor) or None, HL32 bytes or None, Winograd-domain operand bytes
-    [G][B][H][ceil(W/R)][R+2][C/32][128]); dense (None: wino_dense()): the operand as plain fp16 [..][R+2][C/64][128]"""
+    [G][B][H][ceil(W/R)][R+2][C/32][128]); dense (None: wino_dense()): the operand as plain fp16 [..][R+2][C/64][128].
+    residual_affine = (scale, shift) [G,C]: `residual` is a raw downsample-conv output whose BatchNorm affine is applied in this pass"""
     G, B, H, W, C = y.shape
     Wq = (W + R - 1) // R
     dense = wino_dense() if dense is None else dense
@@ -719,7 +720,15 @@ def bn_apply_wino_grouped(y, scale, shift, R, relu=True, residual=None, residual
     out_hl = torch.empty(y.numel() * 4, device=y.device, dtype=torch.uint8) if want_hl else None
     v = torch.empty(G * B * H * Wq * (R + 2) * C * eb, device=y.device, dtype=torch.uint8)
     t0 = CONV_TIMER.begin("bnw") if CONV_TIMER is not None else None
-    if dense:
+    if residual_affine is not None:
+        rs, rt = _residual_affine(residual_affine, residual, G, C)
+        if dense:
+            call("mrn_bn_apply_wino_grouped_d16_res_affine_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift), _p(out),
+                 _p(out_hl), _p(v), G, B, H, W, C, int(bool(relu)), _p(prescale), int(REDUCED_BF16), _p(rs), _p(rt), _stream())
+        else:
+            call("mrn_bn_apply_wino_grouped_res_affine_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift), _p(out),
+                 _p(out_hl), _p(v), G, B, H, W, C, R, int(bool(relu)), _p(prescale), _p(rs), _p(rt), _stream())
+    elif dense:
         call("mrn_bn_apply_wino_grouped_d16_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift), _p(out), _p(out_hl), _p(v),
              G, B, H, W, C, int(bool(relu)), _p(prescale), int(REDUCED_BF16), _stream())
     else:
@@ -1105,15 +1114,30 @@ def bn_eval_affine_grouped(ptr_table, G, C, eps):
     return scale, shift
 
 
-def bn_apply_grouped(y, scale, shift, relu=True, residual=None, want_f32=True, want_hl=False, residual_hl=None):
-    """y [G,...,C] fp32 -> (fp32 result (in place) or None, HL32 bytes or None)"""
+def _residual_affine(residual_affine, residual, G, C):
+    """the pending (scale, shift) [G,C] of a downsample shortcut, checked against the fp32 residual it belongs to"""
+    rs, rt = residual_affine
+    assert residual is not None, "residual_affine needs the fp32 residual"
+    assert tuple(rs.shape) == (G, C) and tuple(rt.shape) == (G, C) and rs.dtype == rt.dtype == torch.float32
+    assert rs.is_contiguous() and rt.is_contiguous()
+    return rs, rt
+
+
+def bn_apply_grouped(y, scale, shift, relu=True, residual=None, want_f32=True, want_hl=False, residual_hl=None, residual_affine=None):
+    """y [G,...,C] fp32 -> (fp32 result (in place) or None, HL32 bytes or None).
+    residual_affine = (scale, shift) [G,C]: `residual` is a raw downsample-conv output whose BatchNorm affine is applied in this pass"""
     G, C = y.shape[0], y.shape[-1]
     rows = y.numel() // (G * C)
     out_hl = torch.empty(y.numel() * 4, device=y.device, dtype=torch.uint8) if want_hl else None
     t0 = CONV_TIMER.begin() if CONV_TIMER is not None else None
-    call("mrn_bn_apply_grouped_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift), _p(y) if want_f32 else None,
-         _p(out_hl), G, rows,
-         C, 2 if relu == 2 else int(bool(relu)), _stream())          # (relu = 2: GELU)
+    if residual_affine is not None:
+        rs, rt = _residual_affine(residual_affine, residual, G, C)
+        call("mrn_bn_apply_grouped_res_affine_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift),
+             _p(y) if want_f32 else None, _p(out_hl), G, rows, C, 2 if relu == 2 else int(bool(relu)), _p(rs), _p(rt), _stream())
+    else:
+        call("mrn_bn_apply_grouped_f32", _p(y), _p(residual), _p(residual_hl), _p(scale), _p(shift), _p(y) if want_f32 else None,
+             _p(out_hl), G, rows,
+             C, 2 if relu == 2 else int(bool(relu)), _stream())          # (relu = 2: GELU)
     if t0 is not None:       # algorithmic bytes: every input / output element once (fp32 and HL32 are both 4 B / element)
         n_io = 1 + int(residual is not None or residual_hl is not None) + int(want_f32) + int(want_hl)
         CONV_TIMER.end(t0, 0.0, "hbm/bn_apply_grouped", 4.0 * y.numel() * n_io)
