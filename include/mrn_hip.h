@@ -14,7 +14,8 @@
  *   - return 0 on success, <0 library error, >0 hipError_t; text via mrn_last_error() (thread-local)
  *   - activations are fp32, NHWC (channels innermost); "rows" means all leading dims flattened
  * Compiled-in limits (every shipped config of the reference sits inside them; a call outside returns an error, never a wrong
- * result): recurrent kernels (LSTM layer, attention decoder) hidden_size == 256 (config/*.py: hidden_size=256), decoder context
+ * result): LSTM layer kernels (mrn_lstm_layer_*) hidden_size 128, 256 or 512; attention decoder (mrn_attn_decoder_*) hidden_size == 256
+ * (config/*.py: hidden_size=256; mrn_amd/modules/hidden_size.py states the rule the models refuse by), decoder context
  * width D a multiple of 16 (forward) / of 256 (backward: DERNet concatenates 256-wide extractors); router fan-in / gate tail at most
  * 8 experts (the reference trains 6 languages); TPS at most 61 fiducials (reference: 20); grouped-conv kernels Cin % 32 == 0 and
  * kh*kw <= 32 (other layers run on the exact-fp32 kernels, Cin % 4 == 0).
@@ -366,7 +367,9 @@ int mrn_tps_grid_sample_f32(const float* img_nhwc, const float* cprime, const fl
 /* One (bi)directional LSTM layer given xproj = x W_ih^T + b_ih laid out [B][T][ndir*4*hidden]
  * (gate order i,f,g,o), b_hh [ndir*4*hidden] or NULL; out [B][T][ndir*hidden].  w_hh is [ndir][4*hidden][hidden] in the
  * FRAGMENT-MAJOR order the kernel streams (one contiguous 1 KiB line per wave load):
- *   packed[dir][w][g][q][lane][r] = W[dir][g*hidden + 16w + (lane&15)][16q + 4(lane>>4) + r],  w<16, g<4, q<hidden/16.
+ *   packed[dir][w][g][q][lane][r] = W[dir][g*hidden + 16w + (lane&15)][16q + 4(lane>>4) + r],  w<hidden/16, g<4, q<hidden/16.
+ * hidden is 128, 256 or 512 in every mrn_lstm_layer_* entry point (8 waves of one 16-unit tile w each at 128, 16 waves at 256, 16 waves
+ * that walk tiles w and w + 16 inside a step at 512); any other value is an argument error.
  * modules/sequence_modeling.py:7-21 (nn.LSTM(bidirectional=True, batch_first=True)). */
 int mrn_lstm_layer_fwd_f32(const float* xproj, const float* w_hh, const float* b_hh, float* out, float* gates_out,
                            float* c_out, int B, int T, int hidden, int ndir, void* stream);
@@ -400,7 +403,7 @@ int mrn_lstm_layer_fwd_grouped_f32(const void* const* xproj, const void* const* 
                                    const void* const* out, int groups, int B, int T, int hidden, int ndir, void* stream);
 /* Inference-only variant for the frozen experts: the recurrent product as split-fp16 x3 on v_mfma_f32_16x16x32_f16
  * (h = hi + lo in LDS, W_hh pre-split with a power-of-two prescale into a fragment-major fp16 stream of the same size).
- * w_hh[g]: [ndir][16][4][H/32][64 lanes][hi 8 | lo 8] fp16; w_inv[g]: device float[ndir] = 1 / prescale. */
+ * w_hh[g]: [ndir][H/16][4][H/32][64 lanes][hi 8 | lo 8] fp16; w_inv[g]: device float[ndir] = 1 / prescale.  H = 128, 256 or 512. */
 int mrn_lstm_layer_fwd_x3_grouped(const void* const* xproj, const void* const* w_hh, const void* const* w_inv,
                                   const void* const* b_hh, const void* const* out, int groups, int B, int T, int hidden,
                                   int ndir, void* stream);

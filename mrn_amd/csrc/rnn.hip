@@ -19,6 +19,23 @@ constexpr int BT = 16;         // samples per workgroup
 constexpr int HLD = HID + 4;   // padded LDS row
 constexpr int NW = 16;         // waves per workgroup: wave w owns hidden units [16w, 16w+16) of every gate
 constexpr int NTH = NW * 64;   // 1024 threads -- many waves in flight hide the L2 latency of the weight stream
+// (the five constants above are the attention decoder's, which runs hidden = 256 only.)
+
+// The LSTM layer kernels are templates over the hidden size HS in {128, 256, 512}.  A 16-unit tile of every gate belongs to one wave:
+//   HS = 128   8 waves (512 threads), one unit tile each
+//   HS = 256  16 waves (1024 threads), one unit tile each
+//   HS = 512  16 waves, wave w walks unit tiles w and w + 16 one after the other inside a step (NP = 2 passes: the four gate accumulators
+//             are reused, cell state and bias are held per pass).  Both passes read h of the step from LDS buffer `cur` and write the new h
+//             to buffer `cur ^ 1`, so no pass ever sees a half-updated h; one barrier per step as at the other sizes.
+template <int HS>
+struct LstmGeom {
+  static_assert(HS == 128 || HS == 256 || HS == 512, "LSTM layer kernels: hidden size 128, 256 or 512");
+  static constexpr int NW = HS >= 256 ? 16 : HS / 16;   // waves per workgroup
+  static constexpr int NP = HS / (16 * NW);             // unit tiles (passes) per wave and step
+  static constexpr int NTH = NW * 64;
+  static constexpr int HLD = HS + 4;                    // padded fp32 LDS row
+  static constexpr int LDH = HS + 8;                    // padded fp16 LDS row (halves)
+};
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -134,10 +151,15 @@ struct LstmGroup {
   int tiles, B, T, ndir, nsets, pinned;
 };
 
-__global__ __launch_bounds__(NTH) void lstm_layer_kernel(const LstmGroup grp) {
-  __shared__ __attribute__((aligned(16))) float h_lds[2][BT * HLD];
-  // set = (group, direction) owns one W_hh stream (1 MiB); all tiles of a set run on ONE XCD (block b lands on XCD b % 8)
-  // so the stream stays resident in that XCD's 4 MiB L2 instead of every XCD cycling through every set's weights
+template <int HS>
+__global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_kernel(const LstmGroup grp) {
+  constexpr int HID = HS, NW = LstmGeom<HS>::NW, NP = LstmGeom<HS>::NP, NTH = LstmGeom<HS>::NTH, HLD = LstmGeom<HS>::HLD;
+  // two h buffers of [BT][HLD] floats: static up to 256, dynamic at 512 (66 048 bytes, past the 64 KiB of a static allocation)
+  extern __shared__ __attribute__((aligned(16))) float lstm_f32_dyn[];
+  __shared__ __attribute__((aligned(16))) float h_static[HS <= 256 ? 2 * BT * HLD : 4];
+  float* const h_lds0 = HS <= 256 ? h_static : lstm_f32_dyn;
+  // set = (group, direction) owns one W_hh stream (4 * HS * HS floats: 1 MiB at 256); all tiles of a set run on ONE XCD (block b lands on
+  // XCD b % 8) so the stream stays resident in that XCD's 4 MiB L2 instead of every XCD cycling through every set's weights
   // (only while a set's tiles fit the 32 CUs of an XCD; larger batches keep the plain block order)
   const int set = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
   if (set >= grp.nsets) return;
@@ -154,45 +176,64 @@ __global__ __launch_bounds__(NTH) void lstm_layer_kernel(const LstmGroup grp) {
   const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
   const float* W = w_hh + (long)dir * 4 * HID * HID;
   const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;               // this lane's hidden unit
+  const int j0 = wave * 16 + col;              // this lane's hidden unit of pass 0 (pass p: + 16 * NW * p)
 
-  for (int i = t_; i < BT * HLD; i += NTH) h_lds[0][i] = 0.f;
-  float c[4] = {0.f, 0.f, 0.f, 0.f}, bh[4];
+  for (int i = t_; i < BT * HLD; i += NTH) h_lds0[i] = 0.f;
+  float c[NP][4], bh[NP][4];
 #pragma unroll
-  for (int g = 0; g < 4; ++g) bh[g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j] : 0.f;
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      c[p][g] = 0.f;
+      bh[p][g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j0 + 16 * NW * p] : 0.f;
+    }
   __syncthreads();
 
+  // Two passes: the sample index goes through an empty asm inside the step, so the row addresses of the five arrays are formed per step
+  // (a few VALU ops) instead of being hoisted as 64-bit pointers per row, array and pass -- hoisted, they put the kernel 13 registers over
+  // the 128 of a 1024-thread workgroup.  One pass (128, 256): the plain index, the kernel as it was.
+  auto row_of = [](int b) -> int {
+    if constexpr (NP > 1) asm volatile("" : "+v"(b));
+    return b;
+  };
   for (int step = 0; step < T; ++step) {
     const int t = dir == 0 ? step : T - 1 - step;
     const int cur = step & 1;
-    // input projections of this step: issued first, they land while the recurrent product runs
-    float xg[4][4];
+    const float* h_cur = h_lds0 + cur * (BT * HLD);
+    float* h_new = h_lds0 + (cur ^ 1) * (BT * HLD);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int b = b0 + rbase + r;
-      const float* xp = xproj + ((long)(b < B ? b : 0) * T + t) * (ndir * 4 * HID) + dir * 4 * HID + j;
+    for (int p = 0; p < NP; ++p) {
+      const int JP = 16 * NW * p;                // pass p's units sit JP floats behind pass 0's in every row: a constant on pass 0's addresses
+      // input projections of this step: issued first, they land while the recurrent product runs
+      float xg[4][4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) xg[g][r] = xp[g * HID];
-    }
-    f32x4 acc[4];
+      for (int r = 0; r < 4; ++r) {
+        const int b = b0 + rbase + r;
+        const float* xp = xproj + ((long)row_of(b < B ? b : 0) * T + t) * (ndir * 4 * HID) + dir * 4 * HID + j0;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    mma_rows<4>(acc, h_lds[cur], HLD, W, HID, wave, lane);
-    float h[4], act[4][4];
-    lstm_pointwise(acc, xg, bh, c, h, act);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = rbase + r, b = b0 + row;
-      if (b < B) {
-        out[((long)b * T + t) * (ndir * HID) + dir * HID + j] = h[r];
-        if (gates_out) {
-          const long base = ((long)b * T + t) * ndir + dir;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) gates_out[base * 4 * HID + g * HID + j] = act[g][r];
-          c_out[base * HID + j] = c[r];
-        }
+        for (int g = 0; g < 4; ++g) xg[g][r] = xp[g * HID + JP];
       }
-      h_lds[cur ^ 1][row * HLD + j] = b < B ? h[r] : 0.f;
+      f32x4 acc[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+      mma_rows<4>(acc, h_cur, HLD, W, HID, wave + NW * p, lane);
+      float h[4], act[4][4];
+      lstm_pointwise(acc, xg, bh[p], c[p], h, act);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rbase + r, b = b0 + row;
+        if (b < B) {
+          const int bs = row_of(b);
+          (out + ((long)bs * T + t) * (ndir * HID) + dir * HID + j0)[JP] = h[r];
+          if (gates_out) {
+            const long base = ((long)bs * T + t) * ndir + dir;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) (gates_out + base * 4 * HID + j0)[g * HID + JP] = act[g][r];
+            (c_out + base * HID + j0)[JP] = c[p][r];
+          }
+        }
+        (h_new + row * HLD + j0)[JP] = b < B ? h[r] : 0.f;
+      }
     }
     __syncthreads();
   }
@@ -363,13 +404,14 @@ struct LstmX3Group {
 // Every global access is a buffer instruction (resource + scalar offset + a 32-bit lane offset).  Both changes are round 6's: the form
 // with 64-bit row and fragment pointers in vector registers ran at the 128-register cap; this one takes 100 and is 12-24 % faster
 // (G = 1 13.3 -> 11.8 us / step, G = 3 17.9 -> 14.8, G = 6 20.3 -> 15.3).
-template <int RB>
-__global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group grp) {
+template <int HS, int RB>
+__global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_x3_kernel(const LstmX3Group grp) {
+  constexpr int HID = HS, NW = LstmGeom<HS>::NW, NP = LstmGeom<HS>::NP, NTH = LstmGeom<HS>::NTH, LDH = LstmGeom<HS>::LDH;
   constexpr int BTX = BT * RB;
   extern __shared__ __attribute__((aligned(16))) unsigned char lstm_lds[];
   _Float16* const h_hi = reinterpret_cast<_Float16*>(lstm_lds);        // [2][BTX * LDH]
   _Float16* const h_lo = h_hi + 2 * BTX * LDH;                         // [2][BTX * LDH]
-  // pinned == 1: all tiles of a (expert, direction) set run on XCD (set % 8), whose L2 then holds that set's 1 MiB of W_hh.
+  // pinned == 1: all tiles of a (expert, direction) set run on XCD (set % 8), whose L2 then holds that set's W_hh stream (4 * HS * HS * 4 bytes: 1 MiB at 256).
   // pinned == 2: the (set, tile) pairs in set-major order are cut into eight equal runs, one per XCD (workgroup b runs on XCD b % 8): every
   // L2 serves the same number of workgroups and at most two or three sets' weights.  The step time follows the number of workgroups
   // streaming through one L2 (13.1 us at 4, 17.4 at 16, 21.9 at 32): 12 sets = 24 per XCD instead of 32 / 16, 6 sets = 12 instead of 16 / 0.
@@ -398,13 +440,13 @@ __global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group gr
   const float inv = grp.g[gi].w_inv[dir];
   const float pre = 1.f / inv;                                                 // the prescale itself (a power of two: exact)
   const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;
+  const int j = wave * 16 + col;                 // this lane's hidden unit of pass 0 (pass p: + 16 * NW * p)
 
   for (int i = t_; i < BTX * LDH; i += NTH) {
     h_hi[i] = (_Float16)0.f;
     h_lo[i] = (_Float16)0.f;
   }
-  float c[RB][4], bh[4];
+  float c[NP][RB][4], bh[NP][4];
   // per-lane BYTE offsets of this lane's rows in xproj / the gate saves ([B][T][ndir][4H]); the (t, direction) part of an address is
   // wave-uniform and goes into the scalar base, and the [B][T][ndir][H] arrays' offsets follow from the same registers -- eight
   // loop-invariant registers instead of a 64-bit pointer per row and array (which the compiler hoisted and, at RB = 2, spilled).
@@ -415,11 +457,14 @@ __global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group gr
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int b = b0 + rb * BT + rbase + r;
-      c[rb][r] = 0.f;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) c[p][rb][r] = 0.f;
       xoff[rb][r] = ((unsigned)(b < B ? b : 0) * (unsigned)(T * ndir * 4 * HID) + (unsigned)j) * 4u;
     }
 #pragma unroll
-  for (int g = 0; g < 4; ++g) bh[g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j] : 0.f;
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bh[p][g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j + 16 * NW * p] : 0.f;
   __syncthreads();
 
   // fragment-major weight stream of this wave: [g][q][lane][hi 8 | lo 8 halves] (mma_rows_h's layout)
@@ -429,9 +474,8 @@ __global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group gr
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 4 * HID * HID * 4, 0x00020000);
   const int wwave = __builtin_amdgcn_readfirstlane(wave) * (4 * Q * 64 * 32);
   const int wlane = lane * 32;
-  auto wfrag = [&](int g, int q, int plane) -> f16v8 {
-    return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + ((g * Q + q) * 128 + plane) * 16, 0));
-  };
+  constexpr int WPASS = NW * (4 * Q * 64 * 32);        // bytes between the unit tiles of two passes of a wave
+  constexpr int UPASS = 16 * NW * 4;                  // bytes between their hidden units in a row of floats
   const unsigned xbytes = (unsigned)B * (unsigned)(T * ndir * 4 * HID) * 4u;
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xproj, 0, xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, xbytes / 4, 0x00020000);
@@ -442,76 +486,83 @@ __global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group gr
   for (int step = 0; step < T; ++step) {
     const int t = dir == 0 ? step : T - 1 - step;
     const int cur = step & 1;
-    f32x4 acc[RB][4];
     const int tq = (t * ndir + dir) * HID * 4;                                     // (wave-uniform) byte offset in a [..][T][ndir][H] row
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          acc[rb][g][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)xoff[rb][r], 4 * tq + g * HID * 4, 0)) * pre;
-      }
-    {
-      const _Float16* ah = h_hi + cur * BTX * LDH + n * LDH + kg * 8;
-      const _Float16* al = h_lo + cur * BTX * LDH + n * LDH + kg * 8;
-      // RB = 1: the hi and lo fragments of k-step q + 1 are fetched before the MFMAs of step q issue.  RB = 2 has registers for the next hi
-      // fragments only: the lo fragments of step q are fetched at its top and used by its LAST product group
-      constexpr bool PF_LO = RB == 1;
-      f16v8 wh[4], wl[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        wh[g] = wfrag(g, 0, 0);
-        if (PF_LO) wl[g] = wfrag(g, 0, 1);
-      }
-#pragma unroll 1
-      for (int q = 0; q < Q; ++q) {
-        f16v8 nh[4], nl[4];
-        const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          if (!PF_LO) wl[g] = wfrag(g, q, 1);
-          nh[g] = wfrag(g, qn, 0);
-          if (PF_LO) nl[g] = wfrag(g, qn, 1);
-        }
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + rb * BT * LDH + q * 32), xl = *reinterpret_cast<const f16v8*>(al + rb * BT * LDH + q * 32);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[rb][g], 0, 0, 0);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[rb][g], 0, 0, 0);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[rb][g], 0, 0, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          wh[g] = nh[g];
-          if (PF_LO) wl[g] = nl[g];
-        }
-      }
-    }
     _Float16* const nhi = h_hi + (cur ^ 1) * BTX * LDH;
     _Float16* const nlo = h_lo + (cur ^ 1) * BTX * LDH;
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
+    for (int p = 0; p < NP; ++p) {
+      // pass p: unit tile wave + NW * p -- its weight fragments, its columns of every row (a scalar offset on top of pass 0's)
+      auto wfrag = [&](int g, int q, int plane) -> f16v8 {
+        return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + p * WPASS + ((g * Q + q) * 128 + plane) * 16, 0));
+      };
+      f32x4 acc[RB][4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) acc[rb][g] *= inv;        // undo the power-of-two weight prescale (exact): x-projection + W_hh . h
-      float h[4], act[4][4];
-      lstm_pointwise0(acc[rb], bh, c[rb], h, act);
+      for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rb * BT + rbase + r, b = b0 + row;
-        if (b < B) {
-          const int ooff = (int)(((xoff[rb][r] - 4u * (unsigned)j) >> 2) + 4u * (unsigned)j);       // the same row of a [B][T][ndir][H] array
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h[r]), ro, ooff, tq, 0);
-          if (gates_out) {
+        for (int r = 0; r < 4; ++r) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, act[g][r]), rg, (int)xoff[rb][r], 4 * tq + g * HID * 4, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rb][r]), rc, ooff, tq, 0);
+          for (int g = 0; g < 4; ++g)
+            acc[rb][g][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)xoff[rb][r], 4 * tq + g * HID * 4 + p * UPASS, 0)) * pre;
+        }
+      {
+        const _Float16* ah = h_hi + cur * BTX * LDH + n * LDH + kg * 8;
+        const _Float16* al = h_lo + cur * BTX * LDH + n * LDH + kg * 8;
+        // RB = 1: the hi and lo fragments of k-step q + 1 are fetched before the MFMAs of step q issue.  RB = 2 has registers for the next hi
+        // fragments only: the lo fragments of step q are fetched at its top and used by its LAST product group
+        constexpr bool PF_LO = RB == 1;
+        f16v8 wh[4], wl[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          wh[g] = wfrag(g, 0, 0);
+          if (PF_LO) wl[g] = wfrag(g, 0, 1);
+        }
+#pragma unroll 1
+        for (int q = 0; q < Q; ++q) {
+          f16v8 nh[4], nl[4];
+          const int qn = (q + 1 < Q) ? q + 1 : q;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            if (!PF_LO) wl[g] = wfrag(g, q, 1);
+            nh[g] = wfrag(g, qn, 0);
+            if (PF_LO) nl[g] = wfrag(g, qn, 1);
+          }
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb) {
+            const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + rb * BT * LDH + q * 32), xl = *reinterpret_cast<const f16v8*>(al + rb * BT * LDH + q * 32);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[rb][g], 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[rb][g], 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[rb][g], 0, 0, 0);
+          }
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            wh[g] = nh[g];
+            if (PF_LO) wl[g] = nl[g];
           }
         }
-        store_h_split(nhi, nlo, row * LDH + j, b < B ? h[r] : 0.f);
+      }
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[rb][g] *= inv;        // undo the power-of-two weight prescale (exact): x-projection + W_hh . h
+        float h[4], act[4][4];
+        lstm_pointwise0(acc[rb], bh[p], c[p][rb], h, act);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = rb * BT + rbase + r, b = b0 + row;
+          if (b < B) {
+            const int ooff = (int)(((xoff[rb][r] - 4u * (unsigned)j) >> 2) + 4u * (unsigned)j);       // the same row of a [B][T][ndir][H] array
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h[r]), ro, ooff, tq + p * UPASS, 0);
+            if (gates_out) {
+#pragma unroll
+              for (int g = 0; g < 4; ++g) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, act[g][r]), rg, (int)xoff[rb][r], 4 * tq + g * HID * 4 + p * UPASS, 0);
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[p][rb][r]), rc, ooff, tq + p * UPASS, 0);
+            }
+          }
+          store_h_split(nhi, nlo, row * LDH + j + 16 * NW * p, b < B ? h[r] : 0.f);
+        }
       }
     }
     __syncthreads();
@@ -519,12 +570,12 @@ __global__ __launch_bounds__(NTH) void lstm_layer_x3_kernel(const LstmX3Group gr
 }
 
 // one launch of a filled group
-template <int RB>
+template <int HS, int RB>
 static int lstm_x3_launch_rb(LstmX3Group& grp, int n, bool may_pin, hipStream_t stream) {
-  constexpr size_t lds = (size_t)4 * BT * RB * LDH * sizeof(_Float16);
+  constexpr size_t lds = (size_t)4 * BT * RB * LstmGeom<HS>::LDH * sizeof(_Float16);
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute((const void*)lstm_layer_x3_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)lstm_layer_x3_kernel<HS, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     once = true;
   }
   grp.tiles = ceil_div(grp.B, BT * RB);
@@ -540,12 +591,15 @@ static int lstm_x3_launch_rb(LstmX3Group& grp, int n, bool may_pin, hipStream_t 
       blocks = grp.nsets * grp.tiles;
     }
   }
-  hipLaunchKernelGGL(lstm_layer_x3_kernel<RB>, dim3(blocks), dim3(NTH), lds, stream, grp);
+  hipLaunchKernelGGL((lstm_layer_x3_kernel<HS, RB>), dim3(blocks), dim3(LstmGeom<HS>::NTH), lds, stream, grp);
   return 0;
 }
-static int lstm_x3_launch(LstmX3Group& all, int n, bool may_pin, hipStream_t stream) {
+template <int HS>
+static int lstm_x3_launch_hs(LstmX3Group& all, int n, bool may_pin, hipStream_t stream) {
+  constexpr int HID = HS;
   static const int forced = getenv("MRN_LSTM_RB") ? atoi(getenv("MRN_LSTM_RB")) : 0;
   // the kernel's row offsets are 32-bit byte offsets into [B][T][ndir][4H] floats: batches beyond that go in chunks of whole tiles
+  // (a row is 4 * HS floats per direction and step, so at 512 the chunk boundary falls at half the batch of 256)
   const long row_bytes = (long)all.T * all.ndir * 4 * HID * 4;
   const long fit = 0xffffffffL / row_bytes / (2 * BT) * (2 * BT);
   MRN_CHECK_ARG(fit >= 2 * BT, "lstm x3 layer: T=%d is beyond the kernel's 32-bit row offsets", all.T);
@@ -559,10 +613,19 @@ static int lstm_x3_launch(LstmX3Group& all, int n, bool may_pin, hipStream_t str
       if (q.gates_out) q.gates_out += s0 * (row_bytes / 4);
       if (q.c_out) q.c_out += s0 * (row_bytes / 16);
     }
-    const int rc = forced == 2 ? lstm_x3_launch_rb<2>(grp, n, may_pin, stream) : lstm_x3_launch_rb<1>(grp, n, may_pin, stream);
+    int rc;
+    if constexpr (HS <= 256) rc = forced == 2 ? lstm_x3_launch_rb<HS, 2>(grp, n, may_pin, stream) : lstm_x3_launch_rb<HS, 1>(grp, n, may_pin, stream);
+    else rc = lstm_x3_launch_rb<HS, 1>(grp, n, may_pin, stream);     // (RB = 2 with two passes spills at the 128-register cap: not built)
     if (rc) return rc;
   }
   return 0;
+}
+static int lstm_x3_launch(LstmX3Group& all, int n, bool may_pin, int hidden, hipStream_t stream) {
+  switch (hidden) {
+    case 128: return lstm_x3_launch_hs<128>(all, n, may_pin, stream);
+    case 256: return lstm_x3_launch_hs<256>(all, n, may_pin, stream);
+    default: return lstm_x3_launch_hs<512>(all, n, may_pin, stream);
+  }
 }
 
 // (A weight-stationary variant -- W_hh slices in the LDS of 16 workgroups per (expert, direction), h exchanged through L2 every step --
@@ -945,19 +1008,33 @@ __global__ void embed_gather_kernel(const long* __restrict__ idx, const float* _
 
 }  // namespace
 
-static int lstm_launch(LstmGroup& grp, int groups, hipStream_t st) {
+static int lstm_launch(LstmGroup& grp, int groups, int hidden, hipStream_t st) {
   grp.nsets = groups * grp.ndir;
   grp.pinned = grp.nsets > 2 && grp.tiles * ceil_div(grp.nsets, 8) <= 32;   // (a single layer already fits every L2)
   const int blocks = grp.pinned ? 8 * ceil_div(grp.nsets, 8) * grp.tiles : grp.nsets * grp.tiles;
-  hipLaunchKernelGGL(lstm_layer_kernel, dim3(blocks), dim3(NTH), 0, st, grp);
+  switch (hidden) {
+    case 128: hipLaunchKernelGGL(lstm_layer_kernel<128>, dim3(blocks), dim3(LstmGeom<128>::NTH), 0, st, grp); break;
+    case 256: hipLaunchKernelGGL(lstm_layer_kernel<256>, dim3(blocks), dim3(LstmGeom<256>::NTH), 0, st, grp); break;
+    default: {
+      constexpr size_t lds = sizeof(float) * 2 * BT * LstmGeom<512>::HLD;
+      static bool once = false;
+      if (!once) {
+        (void)hipFuncSetAttribute((const void*)lstm_layer_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        once = true;
+      }
+      hipLaunchKernelGGL(lstm_layer_kernel<512>, dim3(blocks), dim3(LstmGeom<512>::NTH), lds, st, grp);
+    }
+  }
   MRN_LAUNCH_CHECK("lstm_layer");
   return MRN_OK;
 }
 
+static inline bool lstm_hidden_ok(int hidden) { return hidden == 128 || hidden == 256 || hidden == 512; }
+
 MRN_EXPORT int mrn_lstm_layer_fwd_f32(const float* xproj, const float* w_hh, const float* b_hh, float* out,
                                       float* gates_out, float* c_out, int B, int T, int hidden, int ndir, void* stream) {
   MRN_CHECK_ARG(xproj && w_hh && out, "mrn_lstm_layer_fwd_f32: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_lstm_layer_fwd_f32: hidden=%d unsupported (library is built for %d)", hidden, HID);
+  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_f32: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
   MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_f32: ndir=%d", ndir);
   MRN_CHECK_ARG((gates_out == nullptr) == (c_out == nullptr), "mrn_lstm_layer_fwd_f32: gates_out / c_out must come together");
   if (B == 0 || T == 0) return MRN_OK;
@@ -965,7 +1042,7 @@ MRN_EXPORT int mrn_lstm_layer_fwd_f32(const float* xproj, const float* w_hh, con
   memset(&grp, 0, sizeof(grp));
   grp.g[0] = LstmParams{xproj, w_hh, b_hh, out, gates_out, c_out};
   grp.tiles = ceil_div(B, BT); grp.B = B; grp.T = T; grp.ndir = ndir;
-  return lstm_launch(grp, 1, (hipStream_t)stream);
+  return lstm_launch(grp, 1, hidden, (hipStream_t)stream);
 }
 
 // `groups` independent layers of identical geometry in one launch.  xproj / w_hh / b_hh / out are HOST arrays of
@@ -974,7 +1051,7 @@ MRN_EXPORT int mrn_lstm_layer_fwd_grouped_f32(const void* const* xproj, const vo
                                               const void* const* out, int groups, int B, int T, int hidden, int ndir,
                                               void* stream) {
   MRN_CHECK_ARG(xproj && w_hh && out && groups >= 1, "mrn_lstm_layer_fwd_grouped_f32: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_lstm_layer_fwd_grouped_f32: hidden=%d unsupported (library is built for %d)", hidden, HID);
+  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_grouped_f32: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
   MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_grouped_f32: ndir=%d", ndir);
   if (B == 0 || T == 0) return MRN_OK;
   for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
@@ -987,20 +1064,20 @@ MRN_EXPORT int mrn_lstm_layer_fwd_grouped_f32(const void* const* xproj, const vo
                             (float*)out[g0 + i], nullptr, nullptr};
     }
     grp.tiles = ceil_div(B, BT); grp.B = B; grp.T = T; grp.ndir = ndir;
-    const int rc = lstm_launch(grp, n, (hipStream_t)stream);
+    const int rc = lstm_launch(grp, n, hidden, (hipStream_t)stream);
     if (rc) return rc;
   }
   return MRN_OK;
 }
 
 // Inference-only LSTM layers of `groups` frozen experts with the recurrent product on the f16 MFMA (split-fp16 x3).
-// w_hh: HOST array of device pointers to the fragment-major fp16 streams ([ndir][16][4][H/32][64][hi 8 | lo 8 halves],
+// w_hh: HOST array of device pointers to the fragment-major fp16 streams ([ndir][H/16][4][H/32][64][hi 8 | lo 8 halves],
 // ops.pack_fragment_major_h), w_inv: HOST array of device float[ndir] = 1 / prescale of each direction's weights.
 MRN_EXPORT int mrn_lstm_layer_fwd_x3_grouped(const void* const* xproj, const void* const* w_hh, const void* const* w_inv,
                                              const void* const* b_hh, const void* const* out, int groups, int B, int T,
                                              int hidden, int ndir, void* stream) {
   MRN_CHECK_ARG(xproj && w_hh && w_inv && out && groups >= 1, "mrn_lstm_layer_fwd_x3_grouped: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_lstm_layer_fwd_x3_grouped: hidden=%d unsupported (library is built for %d)", hidden, HID);
+  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_x3_grouped: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
   MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_x3_grouped: ndir=%d", ndir);
   if (B == 0 || T == 0) return MRN_OK;
   for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
@@ -1013,7 +1090,7 @@ MRN_EXPORT int mrn_lstm_layer_fwd_x3_grouped(const void* const* xproj, const voi
                               b_hh ? (const float*)b_hh[g0 + i] : nullptr, (float*)out[g0 + i]};
     }
     grp.B = B; grp.T = T; grp.ndir = ndir;
-    const int rc = lstm_x3_launch(grp, n, true, (hipStream_t)stream);
+    const int rc = lstm_x3_launch(grp, n, true, hidden, (hipStream_t)stream);
     if (rc) return rc;
     MRN_LAUNCH_CHECK("lstm_layer_x3");
   }
@@ -1026,14 +1103,14 @@ MRN_EXPORT int mrn_lstm_layer_fwd_x3_grouped(const void* const* xproj, const voi
 MRN_EXPORT int mrn_lstm_layer_fwd_x3_save(const float* xproj, const void* w_hh, const float* w_inv, const float* b_hh, float* out,
                                           float* gates_out, float* c_out, int B, int T, int hidden, int ndir, void* stream) {
   MRN_CHECK_ARG(xproj && w_hh && w_inv && out && gates_out && c_out, "mrn_lstm_layer_fwd_x3_save: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_lstm_layer_fwd_x3_save: hidden=%d unsupported (library is built for %d)", hidden, HID);
+  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_x3_save: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
   MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_x3_save: ndir=%d", ndir);
   if (B == 0 || T == 0) return MRN_OK;
   LstmX3Group grp;
   memset(&grp, 0, sizeof(grp));
   grp.g[0] = LstmX3Params{xproj, (const unsigned char*)w_hh, w_inv, b_hh, out, gates_out, c_out};
   grp.B = B; grp.T = T; grp.ndir = ndir;
-  const int rc = lstm_x3_launch(grp, 1, false, (hipStream_t)stream);
+  const int rc = lstm_x3_launch(grp, 1, false, hidden, (hipStream_t)stream);
   if (rc) return rc;
   MRN_LAUNCH_CHECK("lstm_layer_x3_save");
   return MRN_OK;

@@ -647,12 +647,12 @@ class MaxPoolFn(torch.autograd.Function):
 
 
 def _pack_lstm_h(w_f, w_r):
-    packs = [ops.pack_fragment_major_h(w.detach()) for w in (w_f, w_r)]
+    packs = [ops.pack_fragment_major_h(w.detach(), w.shape[1]) for w in (w_f, w_r)]
     return torch.stack([p_[0] for p_ in packs]).contiguous(), torch.cat([p_[1] for p_ in packs]).contiguous()
 
 
 def _pack_lstm_hT(w_f, w_r):
-    packs = [ops.pack_fragment_major_h(w.detach().t().contiguous()) for w in (w_f, w_r)]
+    packs = [ops.pack_fragment_major_h(w.detach().t().contiguous(), w.shape[1]) for w in (w_f, w_r)]
     return torch.stack([p_[0] for p_ in packs]).contiguous(), torch.cat([p_[1] for p_ in packs]).contiguous()
 
 
@@ -675,12 +675,12 @@ class BiLSTMFn(torch.autograd.Function):
             xproj = x3_linear(x2, w_ih, b_ih, w_pack=w_pack).view(*x.shape[:-1], w_ih.shape[0])
         else:
             xproj = ops.linear(x, w_ih, b_ih)
-        if ops.TRAIN_LSTM_X3 and H == 256:
+        if ops.TRAIN_LSTM_X3:
             # recurrent product as split-fp16 x3 (the trained convolutions' arithmetic): half the time per step of the exact-fp32 MFMA
             w_h, w_inv = ops.train_pack("lstm_fwd_x3", (w_hh_f, w_hh_r), _pack_lstm_h)
             out, gates, cseq = ops.lstm_layer_x3_save(xproj, w_h, w_inv, b_hh, H, 2)
         else:
-            w_hh = torch.stack([ops.pack_fragment_major(w_hh_f), ops.pack_fragment_major(w_hh_r)], 0)
+            w_hh = torch.stack([ops.pack_fragment_major(w_hh_f, H), ops.pack_fragment_major(w_hh_r, H)], 0)
             out, gates, cseq = ops.lstm_layer(xproj, w_hh, b_hh, H, 2, save=True)
         ctx.save_for_backward(x, w_ih, w_hh_f, w_hh_r, out, gates, cseq)
         ctx.H = H
@@ -693,11 +693,11 @@ class BiLSTMFn(torch.autograd.Function):
         x, w_ih, w_hh_f, w_hh_r, out, gates, cseq = ctx.saved_tensors
         H = ctx.H
         B, T, _ = out.shape
-        if ops.TRAIN_LSTM_X3 and H == 256:
+        if ops.TRAIN_LSTM_X3:
             w_hT, w_invT = ops.train_pack("lstm_bwd_x3", (ctx.params[1], ctx.params[5]), _pack_lstm_hT)
             dg = ops.lstm_layer_bwd_x3(dout, gates, cseq, w_hT, w_invT, H, 2)                                 # [B,T,2,4H]
         else:
-            w_hhT = torch.stack([ops.pack_fragment_major(w_hh_f.t().contiguous()), ops.pack_fragment_major(w_hh_r.t().contiguous())], 0)
+            w_hhT = torch.stack([ops.pack_fragment_major(w_hh_f.t().contiguous(), H), ops.pack_fragment_major(w_hh_r.t().contiguous(), H)], 0)
             dg = ops.lstm_layer_bwd(dout, gates, cseq, w_hhT, H, 2)          # [B,T,2,4H]
         dg2 = dg.view(B * T, 8 * H)
         dx = linear_dgrad(dg2, w_ih).view(x.shape) if ctx.needs_input_grad[0] else None

@@ -663,7 +663,7 @@ class SequenceGroup(_GroupedLinear):
         return ops.CONV_PRECISION in ("auto", "fp16x3")
 
     def _bilstm(self, idx, x_hl, rows_shape, K, **dst):
-        """BidirectionalLSTM number idx of every extractor: x [G, B*T, K] (HL32) -> [G,B,T,256] fp32 (or the strided `out`)"""
+        """BidirectionalLSTM number idx of every extractor: x [G, B*T, K] (HL32) -> [G,B,T,hidden] fp32 (or the strided `out`)"""
         G = self.G
         B, T = rows_shape
         mods = [e.SequenceModeling[idx] for e in self.extractors]
@@ -675,7 +675,7 @@ class SequenceGroup(_GroupedLinear):
         if ops.RECURRENT_X3:
             # recurrent product on the f16 MFMA: W_hh pre-split into a fragment-major fp16 stream (cached), h split in LDS
             def build():
-                packs = [[ops.pack_fragment_major_h(w) for w in (m.rnn.weight_hh_l0, m.rnn.weight_hh_l0_reverse)] for m in mods]
+                packs = [[ops.pack_fragment_major_h(w, H) for w in (m.rnn.weight_hh_l0, m.rnn.weight_hh_l0_reverse)] for m in mods]
                 return (torch.stack([torch.stack([d[0] for d in p]) for p in packs]).contiguous(),
                         torch.stack([torch.cat([d[1] for d in p]) for p in packs]).contiguous())
             w_h, w_inv = self._cached("hh16_%d" % idx, [w for m in mods for w in (m.rnn.weight_hh_l0, m.rnn.weight_hh_l0_reverse)], build)

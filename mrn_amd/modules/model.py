@@ -23,6 +23,7 @@ from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import check_call, frames
 from .prediction import Attention
 from .sequence_modeling import BidirectionalLSTM
+from .hidden_size import check_hidden
 from .task_count import tasks_supported, unsupported_task_count_message
 from .transformation import TPS_SpatialTransformerNetwork
 
@@ -37,6 +38,7 @@ HEADS_STREAM = os.environ.get("MRN_HEADS_STREAM", "1") == "1"
 class Model_Extractor(nn.Module):
     def __init__(self, opt):
         super().__init__()
+        check_hidden(opt.SequenceModeling, opt.Prediction, opt.hidden_size)      # (before anything is built or launched)
         self.opt = opt
         self.stages = {"Trans": opt.Transformation, "Feat": opt.FeatureExtraction, "Seq": opt.SequenceModeling,
                        "Pred": opt.Prediction}
@@ -174,7 +176,7 @@ class Model(nn.Module):
 
 class DERNet(Model):
     """Dynamically expanding network (reference modules/model.py:203-312): one Model_Extractor per task, features
-    concatenated on the channel axis, main head over all of them, auxiliary head over the newest 256."""
+    concatenated on the channel axis, main head over all of them, auxiliary head over the newest out_dim (= hidden_size)."""
 
     def __init__(self, opt):
         super().__init__(opt)
@@ -302,6 +304,7 @@ class DERNet(Model):
     def update_fc(self, hidden_size, nb_classes, device=None):
         if not tasks_supported(len(self.model) + 1):
             raise NotImplementedError(unsupported_task_count_message("DERNet", len(self.model) + 1))
+        check_hidden(self.opt.SequenceModeling, self.opt.Prediction, self.opt.hidden_size)
         dev = next(self.parameters()).device if len(self.model) else None
         self.model.append(Model_Extractor(self.opt))
         if len(self.model) > 1:
@@ -599,6 +602,7 @@ class MRNNet(nn.Module):
     def update_fc(self, hidden_size, nb_classes):
         if not tasks_supported(len(self.model) + 1):
             raise NotImplementedError(unsupported_task_count_message("MRNNet", len(self.model) + 1))
+        check_hidden(self.opt.SequenceModeling, self.opt.Prediction, self.opt.hidden_size)
         dev = next(self.parameters()).device if len(self.model) else None
         self.model.append(Model(self.opt))
         self.model[-1].new_fc(hidden_size, nb_classes)

@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from .. import ops
 from ._nn import require_no_grad
+from .hidden_size import check_hidden
 
 
 class AttentionCell(nn.Module):
@@ -79,6 +80,7 @@ class Attention(nn.Module):
         """batch_H [B,T,D]; text [B,S] (teacher forcing) or [B] of [SOS] (greedy) -> logits [B,S,num_class].
         `out` may be a preallocated (possibly strided) [B,S,num_class] buffer."""
         from ..functional import AttnDecoderFn, needs_grad
+        check_hidden(None, "Attn", self.hidden_size)          # the decoder kernels are built for 256 only: refuse before any launch
         cell = self.attention_cell
         B = batch_H.shape[0]
         S = batch_max_length + 1

@@ -8,6 +8,7 @@ import torch.nn as nn
 
 from .. import ops
 from ._nn import require_no_grad
+from .hidden_size import check_hidden
 
 
 class BidirectionalLSTM(nn.Module):
@@ -26,7 +27,7 @@ class BidirectionalLSTM(nn.Module):
         if cache is None or cache[0] != key:
             with torch.no_grad():
                 w_ih = torch.cat([ps[0], ps[1]], 0).contiguous()            # [2*4H, in]
-                w_hh = torch.stack([ops.pack_fragment_major(ps[2]), ops.pack_fragment_major(ps[3])], 0).contiguous()
+                w_hh = torch.stack([ops.pack_fragment_major(ps[2], self.hidden_size), ops.pack_fragment_major(ps[3], self.hidden_size)], 0).contiguous()
                 b_ih = torch.cat([ps[4], ps[6]], 0).contiguous()
                 b_hh = torch.cat([ps[5], ps[7]], 0).contiguous()
             cache = (key, (w_ih, w_hh, b_ih, b_hh))
@@ -36,6 +37,7 @@ class BidirectionalLSTM(nn.Module):
     def forward(self, input, out=None):
         """input [B,T,in] -> [B,T,out]; `out` may be a strided [B,T,out] view (zero-copy expert stacking)."""
         from ..functional import BiLSTMFn, LinearFn, needs_grad
+        check_hidden("BiLSTM", "CTC", self.hidden_size)       # the LSTM layer kernels' sizes (128, 256, 512), before any launch
         if needs_grad(self, input):
             r = self.rnn
             rec = BiLSTMFn.apply(input, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0, r.weight_ih_l0_reverse,
@@ -47,7 +49,7 @@ class BidirectionalLSTM(nn.Module):
             return y
         w_ih, w_hh, b_ih, b_hh = self._packed()
         xproj = ops.linear(input, w_ih, b_ih)
-        if ops.RECURRENT_X3 and self.hidden_size == 256:
+        if ops.RECURRENT_X3:
             # inference: the recurrent product as split-fp16 x3, as the lock-step groups run it (half the step time of the exact-fp32 MFMA)
             w_h, w_inv = self._packed_x3()
             rec = ops.lstm_layer_x3_grouped(xproj.unsqueeze(0), w_h, w_inv, b_hh.unsqueeze(0), self.hidden_size, 2)[0]
@@ -62,7 +64,7 @@ class BidirectionalLSTM(nn.Module):
         cache = getattr(self, "_mrn_packed_x3", None)
         if cache is None or cache[0] != key:
             with torch.no_grad():
-                packs = [ops.pack_fragment_major_h(w) for w in ps]
+                packs = [ops.pack_fragment_major_h(w, self.hidden_size) for w in ps]
                 cache = (key, (torch.stack([p_[0] for p_ in packs]).unsqueeze(0).contiguous(),
                                torch.cat([p_[1] for p_ in packs]).unsqueeze(0).contiguous()))
             self._mrn_packed_x3 = cache

@@ -1299,11 +1299,12 @@ def tps_grid_sample(img_nhwc, cprime, inv_delta_c, p_hat, out_hw, want_grid=Fals
 # ---------------------------------------------------------------------------------------------------------
 def pack_fragment_major(w, hidden=256):
     """[G*hidden, K] weight (G gate groups, K % 16 == 0) -> the fragment-major stream order of the recurrent kernels:
-    packed[w][g][q][lane = gg*16 + n][r] = W[g*hidden + 16w + n][16q + 4gg + r]  (pure data movement)."""
+    packed[w][g][q][lane = gg*16 + n][r] = W[g*hidden + 16w + n][16q + 4gg + r]  (pure data movement); the unit-tile index w runs to
+    hidden/16 (the LSTM layer kernels take hidden 128, 256 and 512; the attention decoder's weights are packed at 256)."""
     G = w.shape[0] // hidden
     K = w.shape[1]
-    assert w.shape[0] == G * hidden and hidden == 256 and K % 16 == 0
-    v = w.reshape(G, 16, 16, K // 16, 4, 4)              # g, w, n, q, gg, r
+    assert w.shape[0] == G * hidden and hidden % 16 == 0 and K % 16 == 0
+    v = w.reshape(G, hidden // 16, 16, K // 16, 4, 4)    # g, w, n, q, gg, r
     return v.permute(1, 0, 3, 4, 2, 5).contiguous()      # w, g, q, gg, n, r
 
 
@@ -1343,12 +1344,12 @@ def _ptr_array(ptrs):
 
 def pack_fragment_major_h(w, hidden=256):
     """[G*hidden, K] fp32 weight (K % 32 == 0) -> (fp16 fragment-major split stream for the f16 MFMA recurrent kernels,
-    inverse prescale [1]): packed[w][g][q][lane = kg*16 + n][plane][e] = split(s * W[g*hidden + 16w + n][32q + 8kg + e])"""
+    inverse prescale [1]): packed[w][g][q][lane = kg*16 + n][plane][e] = split(s * W[g*hidden + 16w + n][32q + 8kg + e]), w < hidden/16"""
     G = w.shape[0] // hidden
     K = w.shape[1]
-    assert w.shape[0] == G * hidden and hidden == 256 and K % 32 == 0
+    assert w.shape[0] == G * hidden and hidden % 16 == 0 and K % 32 == 0
     sc = pow2_scale(w.contiguous())
-    v = (w * sc[0]).reshape(G, 16, 16, K // 32, 4, 8).permute(1, 0, 3, 4, 2, 5)     # w, g, q, kg, n, e
+    v = (w * sc[0]).reshape(G, hidden // 16, 16, K // 32, 4, 8).permute(1, 0, 3, 4, 2, 5)     # w, g, q, kg, n, e
     hi = v.half()
     lo = (v - hi.float()).half()
     return torch.stack([hi, lo], dim=5).contiguous(), sc[1:2].clone()                  # [..., n, plane, e]
