@@ -600,6 +600,20 @@ int mrn_argmax_f32(const float* x, int64_t ld, int64_t* out, int64_t rows, int C
 /* greedy decode + confidence in one pass (test.py:211,218-219: preds.max(2); F.softmax(preds, 2).max(2)): idx = first argmax,
    prob = softmax(row)[argmax] */
 int mrn_argmax_prob_f32(const float* x, int64_t ld, int64_t* idx, float* prob, int64_t rows, int C, void* stream);
+/* validation scoring of one batch from mrn_argmax_prob_f32's outputs (test.py:211-265: greedy decode, [EOS] cut, edit distance, exact
+ * match, confidence; tools/utils.py:62-76 CTC collapse, :133-143 attention decode), one wave per sample.  Tokens are canonical
+ * classes (mrn_amd/modules/scoring.py): canon[k] >= 0 is the dictionary index of the single character class k decodes to, -2 a class
+ * that decodes to a multi-character token; a label token of -1 (character not in the dictionary) equals nothing.
+ *   mode 0 (CTC, blank 0): position t is kept when idx[t] != 0 && idx[t] != idx[t-1] (raw indices); confidence = product of all T
+ *   mode 1 (attention):    kept are the positions before the first `eos`; without one, [0, T-1) (the reference's find() == -1);
+ *                          confidence = product of the kept probabilities, 0 when none is kept
+ * tokens [B,T]: kept canonical tokens, front-packed, -1 behind them; result [B,4] = {kept count, unit-cost Levenshtein distance to
+ * label[:label_len], exact match, needs_host}; needs_host = 1 when a scanned token (CTC: kept; attention: before the cut, or all T
+ * without a cut) has canon == -2 -- the other outputs of that sample are then unspecified.  The confidence is a left-to-right fp32
+ * product (np.cumprod order).  Limits: 1 <= T <= 512, 0 <= Lmax <= 256. */
+int mrn_greedy_score_f32(const int64_t* idx, const float* prob, int B, int T, const int32_t* label, const int32_t* label_len, int Lmax,
+                         const int32_t* canon, int C, int mode, int eos, int32_t* tokens, int32_t* result, float* confidence,
+                         void* stream);
 
 /* ---- MRN fan-in and gate tail (modules/model.py:361-423) --------------------------------------------------- */
 

@@ -26,6 +26,8 @@ _CTYPES = {
     "int64_t*": ctypes.c_void_p,
     "const int*": ctypes.c_void_p,
     "int*": ctypes.c_void_p,
+    "const int32_t*": ctypes.c_void_p,
+    "int32_t*": ctypes.c_void_p,
     "const void*": ctypes.c_void_p,
     "const void* const*": ctypes.c_void_p,
     "const char*": ctypes.c_char_p,

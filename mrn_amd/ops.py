@@ -1499,6 +1499,26 @@ def argmax_prob_lastdim(x):
     return idx.view(x.shape[:-1]), prob.view(x.shape[:-1])
 
 
+def greedy_score(idx, prob, label, label_len, canon, mode, eos=0):
+    """validation scoring of one batch from argmax_prob_lastdim's outputs [B,T] (include/mrn_hip.h: mrn_greedy_score_f32):
+    label int32 [B,Lmax] canonical tokens, label_len int32 [B], canon int32 [C]; mode 0 = CTC collapse, 1 = attention cut at `eos`
+    -> (tokens int32 [B,T] front-packed, result int32 [B,4] = {kept, edit distance, exact match, needs_host}, confidence fp32 [B],
+    packed int32 [5B]: the buffer result and confidence are views of).
+    The limits (modules/scoring.py) are the caller's to keep: outside them the call is an error, never a host fallback"""
+    for t, dt in ((idx, torch.int64), (prob, torch.float32), (label, torch.int32), (label_len, torch.int32), (canon, torch.int32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("greedy_score needs contiguous CUDA (HIP) tensors (int64 indices, fp32 probabilities, int32 labels / "
+                               "lengths / table); there is no CPU fallback")
+    B, T = idx.shape
+    assert prob.shape == idx.shape and label.dim() == 2 and label.shape[0] == B and label_len.shape == (B,) and canon.dim() == 1
+    tokens = torch.empty(B, T, device=idx.device, dtype=torch.int32)
+    packed = torch.empty(B * 5, device=idx.device, dtype=torch.int32)        # one buffer, so that one copy brings both to the host
+    result, confidence = packed[:B * 4].view(B, 4), packed[B * 4:].view(torch.float32)
+    call("mrn_greedy_score_f32", _p(idx), _p(prob), B, T, _p(label), _p(label_len), label.shape[1], _p(canon), canon.shape[0],
+         int(mode), int(eos), _p(tokens), _p(result), _p(confidence), _stream())
+    return tokens, result, confidence, packed
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     """LayerNorm over the last dim of (strided) rows -> (y, mean, rstd)"""
     x2 = rows2d(x)

@@ -1,7 +1,11 @@
 """validation(): greedy-decode evaluation with the reference's return convention and scoring rules (reference
 test.py:139-279).  Accuracy = exact match against the RAW label string (a predicted [UNK] never counts as correct,
 test.py:232-236), norm_ED = ICDAR-2019 normalised edit distance, confidence = product of the per-step max-probabilities.
-(the forward / decoding path runs on the HIP kernels; string scoring is host work as in the reference.)
+(the forward / decoding path runs on the HIP kernels.)  Scoring runs on the device too: one
+mrn_greedy_score_f32 launch per batch (CTC collapse / [EOS] cut, edit distance, exact match, confidence) on integer tokens, with
+the same eight return values, bit for bit, as the reference's per-sample string loop.  That loop is kept as the host path: for a
+batch outside the kernel's limits (modules/scoring.py), for predictions that are not on the GPU, for the samples the kernel flags
+(a predicted [UNK] / [PAD] / [SOS] where it counts), and for everything under MRN_VALIDATION_SCORING=host.
 
 Reference quirks reproduced on purpose (pinned by tests/golden/validation.npz):
   * attention head: the prediction is cut at prd.find("[EOS]"); when there is NO [EOS] find() returns -1, so the LAST
@@ -16,6 +20,9 @@ import torch
 
 from . import functional as Fn
 from . import ops
+from .modules import scoring as S
+
+SCORE_TIMER = None     # a list here collects, per batch, the host seconds from the loss being on the host to the scores being there
 
 
 def edit_distance(a, b):
@@ -51,13 +58,65 @@ def _forward(model, image, opt, converter, val_choose):
     return out["logits"] if "logits" in out else out["predict"]
 
 
+def _ned_term(n_gt, n_prd, distance):
+    """one sample's ICDAR-2019 normalised edit distance term (test.py:243-250), or None when there is nothing to add"""
+    if n_gt == 0 or n_prd == 0:
+        return None
+    if n_gt > n_prd:
+        return 1 - distance() / n_gt
+    return 1 - distance() / n_prd
+
+
+def _host_scores(labels, preds_str, probs, attn, ned):
+    """the reference's per-sample loop on strings (test.py:222-260) -> per sample (NED term or None, exact match, confidence)"""
+    out = []
+    for gt, prd, prd_max_prob in zip(labels, preds_str, probs):
+        if attn:
+            eos = prd.find("[EOS]")
+            prd = prd[:eos]                 # find() == -1 (no [EOS]): drops the last character, as the reference does
+            prd_max_prob = prd_max_prob[:eos]
+        term = _ned_term(len(gt), len(prd), lambda: edit_distance(prd, gt)) if ned else None
+        conf = float(np.cumprod(prd_max_prob.astype(np.float32))[-1]) if len(prd_max_prob) else 0
+        out.append((term, prd == gt, conf))
+    return out
+
+
+def _device_scores(labels, preds_index, preds_max_prob, converter, canon, attn, ned, width):
+    """one H2D copy of the canonical labels, one launch, one D2H copy of result + confidence; the samples the kernel flags are
+    scored by _host_scores from one fetch of the batch's indices / probabilities -> (per-sample scores, kept tokens, host strings)"""
+    B, T = preds_index.shape
+    lab, lab_len = S.canonical_labels(converter, labels, width)
+    host = torch.from_numpy(np.concatenate([lab_len, lab.reshape(-1)])).pin_memory().to(preds_index.device, non_blocking=True)
+    tokens, _, _, packed = ops.greedy_score(preds_index.contiguous(), preds_max_prob.contiguous(), host[B:].view(B, width), host[:B],
+                                            canon, S.MODE_ATTN if attn else S.MODE_CTC, converter.dict["[EOS]"] if attn else 0)
+    packed = packed.cpu().numpy()
+    result, conf = packed[:B * 4].reshape(B, 4).tolist(), packed[B * 4:].view(np.float32)
+    flagged = [b for b in range(B) if result[b][3]]
+    host_rows = {}
+    if flagged:
+        index, probs = preds_index.cpu().numpy(), preds_max_prob.cpu().numpy()
+        strings = converter.decode(index[flagged], [T] * len(flagged))
+        scored = _host_scores([labels[b] for b in flagged], strings, probs[flagged], attn, ned)
+        host_rows = {b: (sc, st) for b, sc, st in zip(flagged, scored, strings)}
+    out = []
+    for b in range(B):
+        if b in host_rows:
+            out.append(host_rows[b][0])
+            continue
+        n_prd, dist, match, _ = result[b]
+        term = _ned_term(int(lab_len[b]), n_prd, lambda: dist) if ned else None
+        out.append((term, bool(match), float(conf[b]) if not attn or n_prd else 0))    # attention: kept tokens = kept probabilities
+    return out, (tokens, result), {b: st for b, (_, st) in host_rows.items()}
+
+
 def validation(model, criterion, evaluation_loader, converter, opt, val_choose="val", tqdm_position=1):
     n_correct, norm_ED, length_of_data, infer_time = 0, 0.0, 0, 0.0
     loss_sum, loss_n = 0.0, 0
     preds_str, confidence_score_list, labels = [], [], []
     params = list(model.parameters()) if hasattr(model, "parameters") else []
     dev = params[0].device if params else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-    attn = "Attn" in opt.Prediction
+    attn, ned = "Attn" in opt.Prediction, getattr(opt, "NED", False)
+    canon, last = None, None
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
         length_of_data += batch_size
@@ -78,26 +137,38 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
             cost = Fn.ctc_loss(preds.contiguous() if preds.stride(-1) != 1 else preds, labels_index, labels_length)
         loss_sum += float(cost)
         loss_n += 1
+        if SCORE_TIMER is not None:
+            t_score = time.perf_counter()
         preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                         # :211, :218-219
-        preds_str = converter.decode(preds_index.cpu().numpy(), [preds.size(1)] * batch_size)
-        probs = preds_max_prob.cpu().numpy()
+        T = preds.size(1)
+        width = max((len(gt) for gt in labels), default=0)
+        if preds_index.is_cuda and S.device_scoring_supported(converter, opt.Prediction, T, width):
+            if canon is None:               # once per call, never kept on the converter: MRN rebuilds its character set per task
+                canon = torch.from_numpy(S.canonical_table(converter, opt.Prediction)).to(preds_index.device)
+            scores, kept, host_strings = _device_scores(labels, preds_index, preds_max_prob, converter, canon, attn, ned, width)
+            last = (preds_index, kept, host_strings)
+        else:
+            preds_str = converter.decode(preds_index.cpu().numpy(), [T] * batch_size)
+            scores = _host_scores(labels, preds_str, preds_max_prob.cpu().numpy(), attn, ned)
+            last = None
         confidence_score_list = []
-        for gt, prd, prd_max_prob in zip(labels, preds_str, probs):
-            if attn:
-                eos = prd.find("[EOS]")
-                prd = prd[:eos]                 # find() == -1 (no [EOS]): drops the last character, as the reference does
-                prd_max_prob = prd_max_prob[:eos]
-            if getattr(opt, "NED", False):
-                if len(gt) == 0 or len(prd) == 0:
-                    norm_ED += 0
-                elif len(gt) > len(prd):
-                    norm_ED += 1 - edit_distance(prd, gt) / len(gt)
-                else:
-                    norm_ED += 1 - edit_distance(prd, gt) / len(prd)
-            if prd == gt:
+        for term, correct, conf in scores:  # the reference's accumulation, sample by sample in its order
+            if term is not None:
+                norm_ED += term
+            if correct:
                 n_correct += 1
-            confidence_score_list.append(float(np.cumprod(prd_max_prob.astype(np.float32))[-1]) if len(prd_max_prob) else 0)
-    ned_score = norm_ED / float(length_of_data) * 100 if getattr(opt, "NED", False) else None
+            confidence_score_list.append(conf)
+        if SCORE_TIMER is not None:
+            SCORE_TIMER.append(time.perf_counter() - t_score)
+    if last is not None:                    # the reference returns the LAST batch's strings only: decode nothing else
+        preds_index, (tokens, result), host_strings = last
+        if attn:                            # the returned strings are the unpruned decode of all T steps (test.py:213,274)
+            preds_str = converter.decode(preds_index.cpu().numpy(), [preds_index.size(1)] * preds_index.size(0))
+        else:
+            tokens = tokens.cpu().numpy()
+            preds_str = [host_strings[b] if b in host_strings else "".join(converter.character[k] for k in tokens[b, :result[b][0]])
+                         for b in range(len(result))]
+    ned_score = norm_ED / float(length_of_data) * 100 if ned else None
     score = n_correct / float(length_of_data) * 100
     valid_loss = loss_sum / max(loss_n, 1)
     return valid_loss, score, ned_score, preds_str, confidence_score_list, labels, infer_time, length_of_data
