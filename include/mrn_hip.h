@@ -469,6 +469,47 @@ int mrn_attn_decoder_fwd_x3_grouped(const void* const* Hb, const void* const* Hp
                                     const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
                                     const void* const* w_inv, const void* const* b_hh, const void* const* hid, int64_t hid_stride_b,
                                     int64_t hid_stride_s, int groups, int B, int T, int D, int S, int hidden, void* stream);
+/* Greedy decoding on the attention head (modules/prediction.py:70-86): all S steps in ONE launch, the argmax of every step's
+ * generator output fed back inside the workgroup that owns the sample.  Arguments as mrn_attn_decoder_fwd_f32, except:
+ *   etab [num_class][4*hidden] = char_embeddings.weight . W_ih[:, D:]^T + b_ih replaces eproj (row `token` seeds the gates);
+ *   start_token: DEVICE pointer to the int64 start token (a token >= num_class or < 0 decodes as 0, Attention.cut_unknown);
+ *   w_gen: the generator weight [num_class][hidden], rows zero-padded to a multiple of 16, fragment-major with ONE gate group
+ *          (ops.pack_fragment_major(w, hidden=padded rows)), b_gen [num_class];
+ *   logits [B][S][num_class] with free strides logits_stride_b / logits_stride_s (floats; the class dim is contiguous);
+ *   tokens_out: optional [B][S] int64, the first index of every step's maximum (as mrn_argmax_f32).
+ * hidden == 256; D % 16 == 0.  No carried state, no training saves: inference only. */
+int mrn_attn_greedy_decode_f32(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
+                               const float* w_h2h, const float* b_h2h, const float* w_score, const float* w_ih_ctx,
+                               const float* w_hh, const float* b_hh, const float* w_gen, const float* b_gen, int num_class,
+                               float* logits, int64_t logits_stride_b, int64_t logits_stride_s, int64_t* tokens_out, int B, int T,
+                               int D, int S, int hidden, void* stream);
+/* modules/prediction.py:70-86 with the four products (h2h, W_ih[:, :D], W_hh, generator) as split-fp16 x3: the weight arguments are the
+ * fragment-major fp16 hi / lo streams of ops.pack_fragment_major_h, w_inv a device float[4] = 1 / prescale of w_h2h, w_ih_ctx, w_hh,
+ * w_gen.  D % 32 == 0. */
+int mrn_attn_greedy_decode_x3(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
+                              const void* w_h2h, const float* b_h2h, const float* w_score, const void* w_ih_ctx,
+                              const void* w_hh, const float* w_inv, const float* b_hh, const void* w_gen, const float* b_gen,
+                              int num_class, float* logits, int64_t logits_stride_b, int64_t logits_stride_s,
+                              int64_t* tokens_out, int B, int T, int D, int S, int hidden, void* stream);
+/* modules/prediction.py:70-86 for `groups` experts of one geometry (B, T, D, S) in one launch per 8 experts, every expert with its own
+ * class count: the pointer arguments are HOST arrays of `groups` device pointers (b_hh and tokens_out may be NULL), num_class a HOST
+ * array of `groups` ints, logits_stride_b / logits_stride_s HOST arrays of `groups` strides (padded rows differ with the class count);
+ * the start token is shared. */
+int mrn_attn_greedy_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                       const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                       const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                       const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                       const int* num_class, const void* const* logits, const int64_t* logits_stride_b,
+                                       const int64_t* logits_stride_s, const void* const* tokens_out, int groups, int B, int T,
+                                       int D, int S, int hidden, void* stream);
+/* modules/prediction.py:70-86, grouped and split-fp16 x3 (w_inv: HOST array of pointers to device float[4]) */
+int mrn_attn_greedy_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                      const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                      const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                      const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                      const void* const* b_gen, const int* num_class, const void* const* logits,
+                                      const int64_t* logits_stride_b, const int64_t* logits_stride_s, const void* const* tokens_out,
+                                      int groups, int B, int T, int D, int S, int hidden, void* stream);
 /* out[b][s][:] = table[cut_unknown(idx[b][s])][:]  (modules/prediction.py:35-36,61) */
 int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, const float* table, float* out, int B, int S,
                          int E, int num_class, void* stream);

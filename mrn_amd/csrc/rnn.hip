@@ -995,6 +995,336 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Greedy decoding (reference modules/prediction.py:70-86), all S steps of all experts in one launch: the step of attn_decoder_kernel
+// with the token fed back inside the workgroup.  A workgroup's samples never need another workgroup's result, so this is a plain
+// persistent loop with workgroup barriers only.  Per step:
+//   (0) token: the caller's start token at step 0, then the previous step's argmax (LDS); a token >= num_class counts as 0
+//       (Attention.cut_unknown).  The embedding half of the LSTMCell input is row `token` of etab [num_class][4*HID] =
+//       char_embeddings.weight . W_ih[:, D:]^T + b_ih, which seeds the gate accumulators where eproj does in attn_decoder_kernel
+//   (1)-(6) as attn_decoder_kernel, the same arithmetic in the same order (chunked context in the WIDE form)
+//   (7) logits[b][step][:] = h . W_gen^T + b_gen: class tile n (16 classes) belongs to wave n % 16, K = 256 comes from the h planes
+//       in LDS, W_gen is a one-gate-group fragment-major stream whose rows are zero-padded to a multiple of 16 (padded columns are
+//       neither stored nor compared)
+//   (8) argmax: a running best per lane over its tiles, shuffles over the 16 class columns, then the 16 waves through LDS; the
+//       comparison of rowops.hip argmax_kernel (first index of the maximum, a NaN beats a number, an all-NaN row gives 0)
+// ---------------------------------------------------------------------------------------------
+struct GreedyParams {
+  AttnDecParams a;                  // Hb, Hproj, the recurrent streams, w_inv (x3: float[4], the generator's last), B / T / D / S
+  const float* etab;                // [num_class][4*HID]
+  const int64_t* start;             // device: the start token
+  const float* w_gen;               // fragment-major [ceil(num_class / 16)][1][K-steps][64 lanes] (fp32, or fp16 hi / lo in the x3 form)
+  const float* b_gen;               // [num_class]
+  float* logits;                    // [B][S][num_class], free row strides
+  int64_t* tokens_out;              // optional [B][S]
+  long logits_stride_b, logits_stride_s;
+  int num_class;
+};
+struct GreedyGroup {
+  GreedyParams g[MAX_GROUPS];
+  int tiles, groups, pinned, vb;
+};
+constexpr int GREEDY_LDS_EXTRA = 4 * (BT + 2 * NW * BT);     // 16 tokens + 16 x 16 (value, index) pairs
+
+__device__ __forceinline__ bool argmax_take(float ov, int oi, float best, int bi) {
+  return (ov > best) || (ov == best && oi < bi) || (ov != ov && best == best);
+}
+
+template <bool X3, bool WIDE>
+__global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int gi, tile_;                  // (group, tile) placement: as attn_decoder_kernel
+  if (grp.pinned == 2) {
+    const int per = grp.groups * grp.tiles / 8;
+    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+    gi = pair / grp.tiles;
+    tile_ = pair - gi * grp.tiles;
+  } else {
+    gi = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
+    tile_ = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
+  }
+  if (gi >= grp.groups) return;
+  const GreedyParams& gp = grp.g[gi];
+  const AttnDecParams& p = gp.a;
+  const int D = p.D, T = p.T, C = gp.num_class;
+  const int ntile = (C + 15) / 16;
+  const int DC = WIDE ? CTX_CHUNK : D;
+  const int CLD = DC + 4;
+  const int CLDH = DC + 8;
+  float* h_lds = lds;                      // the LDS map of attn_decoder_kernel ...
+  float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;
+  float* ctx_lds = hp_lds + BT * HLD;
+  float* e_lds = X3 ? ctx_lds + (2 * BT * CLDH) / 2 : ctx_lds + BT * CLD;
+  float* sw_lds = e_lds + BT * T;
+  int* tok_lds = reinterpret_cast<int*>(sw_lds + HID);       // ... + [BT] tokens, [NW][BT] best values, [NW][BT] best indices
+  float* red_v = reinterpret_cast<float*>(tok_lds + BT);
+  int* red_i = reinterpret_cast<int*>(red_v + NW * BT);
+  _Float16* h_hi = reinterpret_cast<_Float16*>(h_lds);
+  _Float16* h_lo = h_hi + BT * LDH;
+  _Float16* c_hi = reinterpret_cast<_Float16*>(ctx_lds);
+  _Float16* c_lo = c_hi + BT * CLDH;
+  const float inv_h2h = X3 ? p.w_inv[0] : 1.f, inv_ih = X3 ? p.w_inv[1] : 1.f, inv_hh = X3 ? p.w_inv[2] : 1.f;
+  const float inv_gen = X3 ? p.w_inv[3] : 1.f;
+  const __amdgpu_buffer_rsrc_t r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * D * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? ntile * 16 * HID * 4 : 0, 0x00020000);
+
+  const int vb = grp.vb;
+  const int b0 = tile_ * vb;
+  const int Bend = min(p.B, b0 + vb);
+  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
+  const int col = lane & 15, rbase = (lane >> 4) * 4;
+  const int j = wave * 16 + col;
+
+  if constexpr (X3) {
+    for (int i = t_; i < BT * LDH; i += NTH) store_h_split(h_hi, h_lo, i, 0.f);
+    for (int i = t_; i < BT * HLD + BT * CLDH + BT * T; i += NTH) hp_lds[i] = 0.f;   // hp, ctx planes, e: rows >= vb stay zero
+  } else {
+    for (int i = t_; i < BT * HLD; i += NTH) h_lds[i] = 0.f;
+    for (int i = t_; i < BT * (HLD + CLD + T); i += NTH) hp_lds[i] = 0.f;
+  }
+  for (int i = t_; i < HID; i += NTH) sw_lds[i] = p.w_score[i];
+  if (t_ < BT) {
+    const long k = gp.start[0];
+    tok_lds[t_] = (k >= C || k < 0) ? 0 : (int)k;
+  }
+  float bh[4], c[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < 4; ++g) bh[g] = p.b_hh ? p.b_hh[g * HID + j] : 0.f;
+  const float bj = p.b_h2h[j];
+  __syncthreads();
+
+  for (int step = 0; step < p.S; ++step) {
+    // (1) hp = h2h(h) + bias
+    {
+      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_h2h, HID, wave, lane);
+      else mma_rows<1>(acc, h_lds, HLD, p.w_h2h, HID, wave, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hp_lds[(rbase + r) * HLD + j] = acc[0][r] * inv_h2h + bj;
+    }
+    __syncthreads();
+    // (2) e[b][t] = score . tanh(Hproj[b][t] + hp[b])
+    {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(sw_lds + lane * 4);
+      const int npair = vb * T;
+      constexpr int U = 4;
+      for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
+        f32x4 hv[U];
+        int rows[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int pr = pr0 + u;
+          const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
+          rows[u] = row;
+          const int b = b0 + row;
+          hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (pr < npair && b < Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
+        }
+        float sacc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const f32x4 pv = *reinterpret_cast<const f32x4*>(hp_lds + rows[u] * HLD + lane * 4);
+          float s = 0.f;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
+          sacc[u] = s;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
+        }
+        if (lane < U && pr0 + lane < npair) {
+          float v = sacc[0];
+#pragma unroll
+          for (int u = 1; u < U; ++u) v = lane == u ? sacc[u] : v;
+          e_lds[pr0 + lane] = (b0 + (pr0 + lane) / T < p.B) ? v : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    // (3) softmax over t, one wave per sample
+    if (wave < vb) {
+      const int row = wave;
+      float m = -INFINITY;
+      for (int t = lane; t < T; t += 64) m = fmaxf(m, e_lds[row * T + t]);
+      m = wave_max(m);
+      float sum = 0.f;
+      for (int t = lane; t < T; t += 64) {
+        const float v = expf(e_lds[row * T + t] - m);
+        e_lds[row * T + t] = v;
+        sum += v;
+      }
+      sum = wave_sum(sum);
+      const float inv = 1.f / sum;
+      for (int t = lane; t < T; t += 64) e_lds[row * T + t] *= inv;
+    }
+    __syncthreads();
+    // (0) the token's row of etab: the initial value of the gate accumulators (lands during phase (4))
+    f32x4 acc5[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* ep = gp.etab + (long)tok_lds[rbase + r] * (4 * HID) + j;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
+    }
+    // (4) context[b][:] = sum_t alpha[b][t] * Hb[b][t][:]   (WIDE: chunk by chunk in (5))
+    if constexpr (!WIDE) {
+      for (int it = t_; it < vb * (D / 4); it += NTH) {
+        const int row = it / (D / 4), c4 = it - row * (D / 4);
+        const int b = b0 + row;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        if (b < Bend) {
+          const float* hb = p.Hb + (long)b * T * D + c4 * 4;
+          int t = 0;
+#pragma unroll 1
+          for (; t + 4 <= T; t += 4) {
+            f32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const float w = e_lds[row * T + t + u];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
+            }
+          }
+          for (; t < T; ++t) {
+            const float w = e_lds[row * T + t];
+            const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
+          }
+        }
+        if constexpr (X3) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
+        } else {
+          *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
+        }
+      }
+      __syncthreads();
+    }
+    // (5) gates = etab[token] + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
+    {
+      f32x4 acc[4];
+      const float pre_ih = 1.f / inv_ih;               // (a power of two)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
+      if constexpr (X3) {
+        if constexpr (WIDE) {
+          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
+            const int kn = min(CTX_CHUNK, D - k0);
+            context_chunk<true>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
+            __syncthreads();
+            mma_rows_hb_k<4>(acc, c_hi, c_lo, r_ih, D, k0, kn, wave, lane, CLDH);
+            if (k0 + CTX_CHUNK < D) __syncthreads();
+          }
+        } else {
+          mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
+        }
+        const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] *= ratio;
+        mma_rows_hb<4>(acc, h_hi, h_lo, r_hh, HID, wave, lane);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
+      } else {
+        if constexpr (WIDE) {
+          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
+            const int kn = min(CTX_CHUNK, D - k0);
+            context_chunk<false>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
+            __syncthreads();
+            mma_rows_k<4>(acc, ctx_lds, CLD, p.w_ih, D, k0, kn, wave, lane);
+            if (k0 + CTX_CHUNK < D) __syncthreads();
+          }
+        } else {
+          mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
+        }
+        mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
+      }
+      __syncthreads();  // every wave has finished reading h_lds
+      float h[4], act[4][4];
+      lstm_pointwise0(acc, bh, c, h, act);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rbase + r, b = b0 + row;
+        if constexpr (X3) store_h_split(h_hi, h_lo, row * LDH + j, b < Bend ? h[r] : 0.f);
+        else h_lds[row * HLD + j] = b < Bend ? h[r] : 0.f;
+      }
+    }
+    __syncthreads();
+    // (7) generator on the new h, (8) running argmax of the lane's classes
+    float best[4];
+    int bi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      best[r] = -INFINITY;
+      bi[r] = 0x7fffffff;
+    }
+#pragma unroll 1
+    for (int n = wave; n < ntile; n += NW) {
+      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_gen, HID, n, lane);
+      // (exact form: the stream pointer is advanced to tile n and the helper's wave argument stays 0 -- every other caller passes a wave
+      // index below 16, a range the compiler carries into the shared helper and that attn_decoder_kernel's register allocation rests on)
+      else mma_rows<1>(acc, h_lds, HLD, gp.w_gen + (long)n * (HID / 16) * 256, HID, 0, lane);
+      const int cls = n * 16 + col;
+      if (cls < C) {
+        const float bg = gp.b_gen[cls];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = acc[0][r] * inv_gen + bg;
+          const int b = b0 + rbase + r;
+          if (b < Bend) gp.logits[(long)b * gp.logits_stride_b + (long)step * gp.logits_stride_s + cls] = v;
+          if (v > best[r] || (v != v && best[r] == best[r])) {
+            best[r] = v;
+            bi[r] = cls;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float ov = __shfl_xor(best[r], o);
+        const int oi = __shfl_xor(bi[r], o);
+        if (argmax_take(ov, oi, best[r], bi[r])) {
+          best[r] = ov;
+          bi[r] = oi;
+        }
+      }
+    }
+    if (col == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        red_v[wave * BT + rbase + r] = best[r];
+        red_i[wave * BT + rbase + r] = bi[r];
+      }
+    }
+    __syncthreads();
+    if (t_ < BT) {                 // the next step reads tok_lds behind the barrier of its phase (1)
+      float bv = red_v[t_];
+      int bx = red_i[t_];
+      for (int w = 1; w < NW; ++w) {
+        const float ov = red_v[w * BT + t_];
+        const int oi = red_i[w * BT + t_];
+        if (argmax_take(ov, oi, bv, bx)) {
+          bv = ov;
+          bx = oi;
+        }
+      }
+      if (bx >= C) bx = 0;
+      tok_lds[t_] = bx;
+      const int b = b0 + t_;
+      if (gp.tokens_out && b < Bend) gp.tokens_out[(long)b * p.S + step] = bx;
+    }
+  }
+}
+
 // rows[i][:] = table[min-cut(idx[i])][:]   (Attention.cut_unknown: indices >= num_class map to 0)
 __global__ void embed_gather_kernel(const long* __restrict__ idx, const float* __restrict__ table,
                                     float* __restrict__ out, long n, int E, int num_class, long idx_stride, int S) {
@@ -1285,6 +1615,171 @@ MRN_EXPORT int mrn_attn_decoder_fwd_x3_grouped(const void* const* Hb, const void
     if (rc) return rc;
   }
   return MRN_OK;
+}
+
+// ---- greedy decoding: attn_greedy_kernel ----------------------------------------------------------------
+template <bool X3, bool WIDE>
+static void greedy_kernel_launch(const GreedyGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024)
+    hipFuncSetAttribute((const void*)attn_greedy_kernel<X3, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_greedy_kernel<X3, WIDE>), grid, dim3(NTH), lds, st, grp);
+}
+
+static int greedy_launch(GreedyGroup& grp, int groups, int D, int T, hipStream_t st) {
+  grp.groups = groups;
+  const int B = grp.g[0].a.B;
+  // samples per workgroup: every workgroup streams its expert's whole generator every step (5.5 MB at 5374 classes) on top of its
+  // samples' Hproj / Hb slices, so fewer, fuller workgroups cut that stream and lengthen the dependent chain.  Measured (B = 256, T = 65,
+  // S = 26, ms per launch at 2 / 4 / 8 / 16 samples, tools/bench_greedy.py --vb-sweep): one expert of 2091 classes 1.93 / 2.14 / 2.53 /
+  // 3.43, of 5374 classes 2.92 / 3.19 / 3.61 / 4.53, six experts 8.40 / 5.91 / 4.71 / 5.60 -- the chain wins until the launch no longer
+  // fits one round of workgroups, so the rule is attn_launch's: the fewest samples (from two) that keep the launch within 256
+  // workgroups.  MRN_GREEDY_VB (2, 4, 8, 16; read per launch) overrides it for tests and sweeps
+  grp.vb = BT;
+  for (int v = 2; v < BT; v *= 2)
+    if ((long)groups * ceil_div(B, v) <= 256) { grp.vb = v; break; }
+  const char* fvb = getenv("MRN_GREEDY_VB");
+  if (fvb) {
+    const int v = atoi(fvb);
+    if (v == 2 || v == 4 || v == 8 || v == 16) grp.vb = v;
+  }
+  grp.tiles = ceil_div(B, grp.vb);
+  grp.pinned = groups > 1 && grp.tiles * ceil_div(groups, 8) <= 32;
+  if (groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
+  const bool x3 = grp.g[0].a.w_inv != nullptr;
+  // the LDS of attn_launch plus the tokens and the argmax pairs; the WIDE form wherever the whole-context form with that extra passes
+  // 160 KiB, or under MRN_ATTN_CTX_CHUNK=1 (read per launch).  ops.attn_greedy_whole_context restates the rule
+  auto lds_for = [&](int dc) {
+    return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + GREEDY_LDS_EXTRA;
+  };
+  const char* force = getenv("MRN_ATTN_CTX_CHUNK");
+  const bool wide = lds_for(D) > 160 * 1024 || (force && atoi(force) == 1);
+  const size_t lds = lds_for(wide ? CTX_CHUNK : D);
+  MRN_CHECK_ARG(lds <= 160 * 1024, "mrn_attn_greedy_decode: LDS budget exceeded (D=%d T=%d)", D, T);
+  const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
+  if (x3) {
+    if (wide) greedy_kernel_launch<true, true>(grp, grid, lds, st);
+    else greedy_kernel_launch<true, false>(grp, grid, lds, st);
+  } else {
+    if (wide) greedy_kernel_launch<false, true>(grp, grid, lds, st);
+    else greedy_kernel_launch<false, false>(grp, grid, lds, st);
+  }
+  MRN_LAUNCH_CHECK("attn_greedy");
+  return MRN_OK;
+}
+
+static void greedy_fill(GreedyParams& gp, const float* Hb, const float* Hproj, const float* etab, const int64_t* start,
+                        const float* w_h2h, const float* b_h2h, const float* w_score, const float* w_ih_ctx, const float* w_hh,
+                        const float* w_inv, const float* b_hh, const float* w_gen, const float* b_gen, int num_class, float* logits,
+                        int64_t stride_b, int64_t stride_s, int64_t* tokens_out, int B, int T, int D, int S) {
+  memset(&gp, 0, sizeof(gp));
+  AttnDecParams& p = gp.a;
+  p.Hb = Hb; p.Hproj = Hproj; p.w_h2h = w_h2h; p.b_h2h = b_h2h; p.w_score = w_score;
+  p.w_ih = w_ih_ctx; p.w_hh = w_hh; p.w_inv = w_inv; p.b_hh = b_hh;
+  p.B = B; p.T = T; p.D = D; p.S = S;
+  gp.etab = etab; gp.start = start; gp.w_gen = w_gen; gp.b_gen = b_gen; gp.num_class = num_class;
+  gp.logits = logits; gp.logits_stride_b = stride_b; gp.logits_stride_s = stride_s; gp.tokens_out = tokens_out;
+}
+
+#define MRN_GREEDY_CHECKS(who, dmul)                                                                                              \
+  MRN_CHECK_ARG(hidden == HID, who ": hidden=%d unsupported (library is built for %d)", hidden, HID);                             \
+  MRN_CHECK_ARG(D % dmul == 0 && D > 0, who ": D=%d must be a multiple of %d", D, dmul);                                          \
+  MRN_CHECK_ARG(B >= 0 && T > 0 && S >= 0, who ": bad geometry (B=%d T=%d S=%d)", B, T, S)
+
+// Greedy decoding of one expert: S steps, argmax fed back inside the launch (reference modules/prediction.py:70-86).
+MRN_EXPORT int mrn_attn_greedy_decode_f32(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
+                                          const float* w_h2h, const float* b_h2h, const float* w_score, const float* w_ih_ctx,
+                                          const float* w_hh, const float* b_hh, const float* w_gen, const float* b_gen, int num_class,
+                                          float* logits, int64_t logits_stride_b, int64_t logits_stride_s, int64_t* tokens_out, int B,
+                                          int T, int D, int S, int hidden, void* stream) {
+  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_gen && b_gen && logits,
+                "mrn_attn_greedy_decode_f32: null operand");
+  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_f32", 16);
+  MRN_CHECK_ARG(num_class >= 1, "mrn_attn_greedy_decode_f32: num_class=%d", num_class);
+  if (B == 0 || S == 0) return MRN_OK;
+  GreedyGroup grp;
+  memset(&grp, 0, sizeof(grp));
+  greedy_fill(grp.g[0], Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class,
+              logits, logits_stride_b, logits_stride_s, tokens_out, B, T, D, S);
+  return greedy_launch(grp, 1, D, T, (hipStream_t)stream);
+}
+
+MRN_EXPORT int mrn_attn_greedy_decode_x3(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
+                                         const void* w_h2h, const float* b_h2h, const float* w_score, const void* w_ih_ctx,
+                                         const void* w_hh, const float* w_inv, const float* b_hh, const void* w_gen, const float* b_gen,
+                                         int num_class, float* logits, int64_t logits_stride_b, int64_t logits_stride_s,
+                                         int64_t* tokens_out, int B, int T, int D, int S, int hidden, void* stream) {
+  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && w_gen && b_gen && logits,
+                "mrn_attn_greedy_decode_x3: null operand");
+  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_x3", 32);
+  MRN_CHECK_ARG(num_class >= 1, "mrn_attn_greedy_decode_x3: num_class=%d", num_class);
+  if (B == 0 || S == 0) return MRN_OK;
+  GreedyGroup grp;
+  memset(&grp, 0, sizeof(grp));
+  greedy_fill(grp.g[0], Hb, Hproj, etab, start_token, (const float*)w_h2h, b_h2h, w_score, (const float*)w_ih_ctx, (const float*)w_hh,
+              w_inv, b_hh, (const float*)w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, B, T, D, S);
+  return greedy_launch(grp, 1, D, T, (hipStream_t)stream);
+}
+
+// `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch (several beyond MAX_GROUPS).  Every
+// pointer argument is a HOST array of `groups` device pointers, num_class and the two logits strides host arrays of `groups` values; the start token is shared; tokens_out may be NULL.  x3 == false: w_inv is ignored.
+static int greedy_grouped(const char* who, bool x3, const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                          const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h, const void* const* w_score,
+                          const void* const* w_ih_ctx, const void* const* w_hh, const void* const* w_inv, const void* const* b_hh,
+                          const void* const* w_gen, const void* const* b_gen, const int* num_class, const void* const* logits,
+                          const int64_t* logits_stride_b, const int64_t* logits_stride_s, const void* const* tokens_out, int groups, int B, int T,
+                          int D, int S, void* stream) {
+  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
+    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
+    GreedyGroup grp;
+    memset(&grp, 0, sizeof(grp));
+    for (int i = 0; i < n; ++i) {
+      const int g = g0 + i;
+      MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&
+                        w_gen[g] && b_gen[g] && logits[g],
+                    "%s: null operand in group %d", who, g);
+      MRN_CHECK_ARG(num_class[g] >= 1, "%s: num_class=%d in group %d", who, num_class[g], g);
+      greedy_fill(grp.g[i], (const float*)Hb[g], (const float*)Hproj[g], (const float*)etab[g], start_token, (const float*)w_h2h[g],
+                  (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g], (const float*)w_hh[g],
+                  x3 ? (const float*)w_inv[g] : nullptr, b_hh ? (const float*)b_hh[g] : nullptr, (const float*)w_gen[g],
+                  (const float*)b_gen[g], num_class[g], (float*)logits[g], logits_stride_b[g], logits_stride_s[g],
+                  tokens_out ? (int64_t*)tokens_out[g] : nullptr, B, T, D, S);
+    }
+    const int rc = greedy_launch(grp, n, D, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return MRN_OK;
+}
+
+MRN_EXPORT int mrn_attn_greedy_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                  const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                  const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                  const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                                  const int* num_class, const void* const* logits, const int64_t* logits_stride_b,
+                                                  const int64_t* logits_stride_s, const void* const* tokens_out, int groups, int B, int T,
+                                                  int D, int S, int hidden, void* stream) {
+  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_gen && b_gen && num_class &&
+                    logits && logits_stride_b && logits_stride_s && groups >= 1, "mrn_attn_greedy_decode_grouped_f32: null operand");
+  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_grouped_f32", 16);
+  if (B == 0 || S == 0) return MRN_OK;
+  return greedy_grouped("mrn_attn_greedy_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
+                        nullptr, b_hh, w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, groups, B, T, D, S,
+                        stream);
+}
+
+MRN_EXPORT int mrn_attn_greedy_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                 const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                 const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                 const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                                 const void* const* b_gen, const int* num_class, const void* const* logits,
+                                                 const int64_t* logits_stride_b, const int64_t* logits_stride_s, const void* const* tokens_out,
+                                                 int groups, int B, int T, int D, int S, int hidden, void* stream) {
+  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && w_gen && b_gen &&
+                    num_class && logits && logits_stride_b && logits_stride_s && groups >= 1, "mrn_attn_greedy_decode_x3_grouped: null operand");
+  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_x3_grouped", 32);
+  if (B == 0 || S == 0) return MRN_OK;
+  return greedy_grouped("mrn_attn_greedy_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
+                        w_inv, b_hh, w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, groups, B, T, D, S,
+                        stream);
 }
 
 MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, const float* table, float* out, int B,

@@ -719,6 +719,32 @@ class HeadsGroup(SequenceGroup):
             return False
         return True
 
+    @staticmethod
+    def greedy_supported(experts):
+        """attention experts at evaluation time: lock-step BiLSTMs and i2h, then ONE greedy launch for all of them (run_greedy).  Kept apart
+        from supported(), whose answer for (attention, evaluation) stays False: run() has no evaluation form for the attention head."""
+        e0 = experts[0]
+        if e0.stages["Pred"] != "Attn" or any(e.stages != e0.stages for e in experts):
+            return False
+        return SequenceGroup.sequence_supported([e.model for e in experts])
+
+    def run_greedy(self, visual, start, feats_out, logits_out):
+        """run() for attention experts at evaluation time: start = device int64 tensor whose first element is the start token ([SOS]);
+        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count."""
+        G = self.G
+        _, B, _, T, Cf = visual.shape
+        feat = self.sequence(visual)                                              # [G,B,T,hidden]
+        feats_out.copy_(feat.permute(1, 2, 0, 3))
+        hidden = feat.shape[-1]
+        heads = [e.Prediction for e in self.experts]
+        cells = [h.attention_cell for h in heads]
+        S = self.experts[0].opt.batch_max_length + 1
+        Hproj = self._linear("i2h", ops.split_hl32(feat), B * T, hidden, [c.i2h.weight for c in cells], None).view(G, B, T, -1)
+        args = [h.greedy_args() for h in heads]      # (etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv) per expert
+        cols = list(zip(*args))
+        ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out,
+                                       w_inv=cols[9] if args[0][9] is not None else None)
+
     def run(self, visual, text, feats_out, logits_out):
         """visual: Act with the backbone features [G,B,1,T,C'] (HL32 and / or fp32); feats_out [B,T,G,hidden] (router
         layout, expert g -> slice [:, :, g, :]); logits_out: list of G [B,T_pred,C_g] views with padded rows."""

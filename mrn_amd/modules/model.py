@@ -430,7 +430,7 @@ class MRNNet(nn.Module):
     def _heads_group(self, group, is_train):
         """HeadsGroup (SequenceModeling + Prediction of all experts in lock-step) when `group` exists and the heads allow it"""
         from .expert_group import HeadsGroup
-        if group is None or not HeadsGroup.supported(list(self.model), is_train):
+        if group is None or not (HeadsGroup.supported(list(self.model), is_train) or self._greedy_heads(is_train)):
             return None
         if self._heads is None or self._heads[0] is not group:
             self._heads = (group, HeadsGroup(list(self.model)))
@@ -439,6 +439,19 @@ class MRNNet(nn.Module):
     @property
     def feature_dim(self):
         return 0 if self.out_dim is None else self.out_dim * len(self.model)
+
+    def _greedy_heads(self, is_train):
+        """attention experts at evaluation time decode greedily in lock-step (HeadsGroup.run_greedy: one launch for all of them) unless
+        MRN_GREEDY_DECODE=stepwise asks for the per-expert step loop"""
+        from .expert_group import HeadsGroup
+        return (not is_train and self.opt.Prediction == "Attn" and ops.greedy_decode_mode() == "fused"
+                and HeadsGroup.greedy_supported(list(self.model)))
+
+    def _run_heads(self, hg, visual, text, is_train, feats, logits):
+        if self._greedy_heads(is_train):
+            hg.run_greedy(visual, text, feats, logits)
+        else:
+            hg.run(visual, text, feats, logits)
 
     def forward(self, image, cross=True, text=None, is_train=True, experts=None):
         """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier"""
@@ -499,7 +512,7 @@ class MRNNet(nn.Module):
                             t.record_stream(sh)          # (allocated in the backbone stream's pool, read by the heads' stream)
                 with torch.cuda.stream(sh):
                     lg = [ops.padded_rows(B, T_pred, e.fc.out_features, dev) for e in list(self.model)[lo:hi]]
-                    hg.run(visual, text, feats[:, :, lo:hi, :], lg)
+                    self._run_heads(hg, visual, text, is_train, feats[:, :, lo:hi, :], lg)
                     done = torch.cuda.Event()
                     done.record(sh)
                 for t in (img, image, text, feats):
@@ -545,13 +558,13 @@ class MRNNet(nn.Module):
                 for (lo, hi, bg, hg), st in zip(halves, streams):
                     st.wait_stream(main)
                     with torch.cuda.stream(st):
-                        hg.run(bg.visual_all(image, as_act=True), text, feats[:, :, lo:hi, :], logits[lo:hi])
+                        self._run_heads(hg, bg.visual_all(image, as_act=True), text, is_train, feats[:, :, lo:hi, :], logits[lo:hi])
                 for st in streams[:len(halves)]:
                     main.wait_stream(st)
                     image.record_stream(st)
             elif heads is not None:
                 # backbones AND heads in lock-step: one grouped launch per conv layer / Linear / recurrence, one stream
-                heads.run(group.visual_all(image, as_act=True), text, feats, logits)
+                self._run_heads(heads, group.visual_all(image, as_act=True), text, is_train, feats, logits)
             elif self.expert_streams and I > 1:
                 # Phase 1, one stream: the conv backbones (grouped when the experts allow it, else one after the other).
                 # Phase 2, one HIP stream per expert: BiLSTM / attention decoder are latency-bound launches of 16-32

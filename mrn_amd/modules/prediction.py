@@ -3,7 +3,8 @@
 Same constructor (`Attention(input_size, hidden_size, num_class, fc, num_char_embeddings=256)`), forward signature
 and state_dict keys (attention_cell.{i2h,h2h,score,rnn}.*, generator.* aliasing fc, char_embeddings.weight).
 Teacher-forced mode is one persistent kernel for all 26 steps with i2h(H) and the embedding half of the LSTMCell
-input projection hoisted into GEMMs; greedy mode runs the same kernel step by step with the argmax fed back.
+input projection hoisted into GEMMs; greedy mode is one persistent kernel too (ops.attn_greedy_decode: generator and argmax inside
+the step, the token fed back in LDS), with the step-by-step form kept behind MRN_GREEDY_DECODE=stepwise.
 """
 import torch
 import torch.nn as nn
@@ -67,6 +68,30 @@ class Attention(nn.Module):
     def x3_ok(self):
         return ops.DECODER_X3 and self.attention_cell.input_size % 32 == 0 and self.hidden_size == 256
 
+    def _greedy_operands(self):
+        """what the fused greedy decoder reads besides the recurrent streams, cached per parameter version:
+        (etab [C,4H] = char_embeddings.weight . W_ih[:, D:]^T + b_ih, generator stream (ops.pack_generator), w_inv float[4] or None)"""
+        cell = self.attention_cell
+        x3 = self.x3_ok()
+        ps = (self.char_embeddings.weight, cell.rnn.weight_ih, cell.rnn.bias_ih, self.generator.weight, cell.h2h.weight, cell.rnn.weight_hh)
+        key = tuple((p.data_ptr(), p._version) for p in ps) + (x3,)
+        cache = getattr(self, "_mrn_greedy", None)
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                etab = ops.linear(self.char_embeddings.weight, cell.rnn.weight_ih[:, cell.input_size:], cell.rnn.bias_ih)
+                w_gen, g_inv = ops.pack_generator(self.generator.weight, x3)
+                w_inv = torch.cat([self._packed_x3()[3], g_inv]).contiguous() if x3 else None
+            cache = (key, (etab, w_gen, w_inv))
+            self._mrn_greedy = cache
+        return cache[1]
+
+    def greedy_args(self):
+        """(etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv) of ops.attn_greedy_decode[_grouped]"""
+        cell = self.attention_cell
+        etab, w_gen, w_inv = self._greedy_operands()
+        w_h2h, w_ih_ctx, w_hh = self._packed_x3()[:3] if w_inv is not None else self._packed()
+        return (etab, w_h2h, cell.h2h.bias, cell.score.weight, w_ih_ctx, w_hh, cell.rnn.bias_hh, w_gen, self.generator.bias, w_inv)
+
     def _decode(self, batch_H, Hproj, eproj, hid=None, h=None, c=None):
         cell = self.attention_cell
         if self.x3_ok():
@@ -105,6 +130,12 @@ class Attention(nn.Module):
             return ops.linear(hid, self.generator.weight, self.generator.bias, out=out)
         # greedy decode (reference :70-86): token_{s+1} = argmax(generator(h_s))
         dev = batch_H.device
+        if ops.greedy_decode_mode() == "fused":
+            # all S steps in one launch; faster than the step loop at every measured shape ("Greedy decoding")
+            etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+            return ops.attn_greedy_decode(batch_H, Hproj, etab, text, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                          self.hidden_size, S, out=out, w_inv=w_inv)
+        # MRN_GREEDY_DECODE=stepwise: five launches per step (gather, Linear, one decoder step with carried state, generator, argmax)
         targets = text[0].expand(B).contiguous().view(B, 1)
         probs = out if out is not None else torch.empty(B, S, self.num_class, device=dev, dtype=torch.float32)
         h = torch.zeros(B, self.hidden_size, device=dev)

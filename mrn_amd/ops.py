@@ -1418,6 +1418,101 @@ def attn_decoder_whole_context(D, T, x3=None):
     return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) <= 160 * 1024
 
 
+GREEDY_LDS_EXTRA = 4 * (16 + 2 * 16 * 16)      # attn_greedy_kernel: 16 tokens + 16 x 16 (value, index) argmax pairs
+
+
+def attn_greedy_whole_context(D, T, x3=None):
+    """attn_decoder_whole_context for the greedy decoder (csrc/rnn.hip greedy_launch): the same tile plus GREEDY_LDS_EXTRA bytes within
+    160 KiB.  At DERNet's widths (D = 256 * G) the crossing is where the teacher-forced decoder's is, between G = 7 and G = 8 for every
+    T <= 129; in between the extra 2112 bytes can tip a tile over (D = 1856 at T = 129 in the x3 form)."""
+    x3 = DECODER_X3 if x3 is None else x3
+    return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + GREEDY_LDS_EXTRA <= 160 * 1024
+
+
+def greedy_decode_mode():
+    """MRN_GREEDY_DECODE, read per call: "fused" (default: all steps in one launch, mrn_attn_greedy_decode*) or "stepwise" (five launches
+    per step, the form before the fused kernel; kept as the A/B reference)"""
+    mode = os.environ.get("MRN_GREEDY_DECODE", "") or "fused"
+    if mode not in ("fused", "stepwise"):
+        raise ValueError(f"MRN_GREEDY_DECODE={mode!r}: expected 'fused' or 'stepwise'")
+    return mode
+
+
+def pack_generator(w, x3):
+    """generator weight [C, 256] -> its fragment-major stream for the greedy decoder: rows zero-padded to a multiple of 16, ONE gate
+    group whose unit tiles are the 16-class tiles; (stream, inverse prescale [1]) in the x3 form, (stream, None) in the exact form"""
+    C, K = w.shape
+    Cp = (C + 15) // 16 * 16
+    wp = torch.zeros(Cp, K, device=w.device, dtype=torch.float32)
+    wp[:C] = w.detach()
+    if x3:
+        return pack_fragment_major_h(wp, Cp)
+    return pack_fragment_major(wp, Cp), None
+
+
+def _greedy_out(out, B, S, C, device):
+    if out is None:
+        out = torch.empty(B, S, C, device=device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, S, C) and out.dtype == torch.float32 and out.stride(2) == 1
+    return out
+
+
+def attn_greedy_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, out=None,
+                       want_tokens=False, w_inv=None):
+    """greedy decoding of one expert in one launch: Hb [B,T,D], Hproj [B,T,H], etab [C,4H] (= char_embeddings.weight . W_ih[:, D:]^T +
+    b_ih), start: device int64 tensor whose first element is the start token, the recurrent weights as for attn_decoder, w_gen from
+    pack_generator, b_gen [C]; with w_inv (device float[4]: h2h, ih, hh, generator) the x3 form.  -> logits [B,S,C] (`out` may be a
+    strided view) or (logits, tokens [B,S] int64)"""
+    _chk(Hb, Hproj, etab, b_h2h, w_score, b_hh, b_gen)
+    B, T, D = Hb.shape
+    C = b_gen.shape[0]
+    assert start.dtype == torch.int64 and start.is_cuda and etab.shape == (C, 4 * hidden) and w_ih.is_contiguous() and w_hh.is_contiguous()
+    assert w_gen.is_contiguous() and w_gen.shape[0] == (C + 15) // 16
+    out = _greedy_out(out, B, S, C, Hb.device)
+    tokens = torch.empty(B, S, device=Hb.device, dtype=torch.int64) if want_tokens else None
+    if w_inv is not None:
+        assert w_inv.numel() == 4 and w_inv.is_contiguous()
+        call("mrn_attn_greedy_decode_x3", _p(Hb), _p(Hproj), _p(etab), _p(start), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh),
+             _p(w_inv), _p(b_hh), _p(w_gen), _p(b_gen), C, _p(out), out.stride(0), out.stride(1), _p(tokens), B, T, D, S, hidden, _stream())
+    else:
+        _chk(w_h2h, w_ih, w_hh, w_gen)
+        call("mrn_attn_greedy_decode_f32", _p(Hb), _p(Hproj), _p(etab), _p(start), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh),
+             _p(b_hh), _p(w_gen), _p(b_gen), C, _p(out), out.stride(0), out.stride(1), _p(tokens), B, T, D, S, hidden, _stream())
+    return (out, tokens) if want_tokens else out
+
+
+def attn_greedy_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, out,
+                               want_tokens=False, w_inv=None):
+    """attn_greedy_decode for G experts of one geometry in one launch (per eight experts): Hb [G,B,T,D], Hproj [G,B,T,H]; every other
+    operand a list of G tensors, the class counts may differ; `out`: list of G [B,S,C_g] buffers, each with strides of its own
+    (padded-row views).  -> out or (out, tokens [G,B,S])"""
+    import ctypes
+    _chk(Hb, Hproj)
+    G, B, T, D = Hb.shape
+    assert Hb.is_contiguous() and Hproj.is_contiguous() and start.dtype == torch.int64 and start.is_cuda
+    classes = [int(b.shape[0]) for b in b_gen]
+    for g in range(G):
+        assert tuple(out[g].shape) == (B, S, classes[g]) and out[g].stride(2) == 1 and out[g].dtype == torch.float32
+        assert etab[g].shape == (classes[g], 4 * hidden) and etab[g].is_contiguous() and w_gen[g].is_contiguous()
+        assert w_gen[g].shape[0] == (classes[g] + 15) // 16 and b_gen[g].is_contiguous()
+    tokens = torch.empty(G, B, S, device=Hb.device, dtype=torch.int64) if want_tokens else None
+
+    def arr(ts):
+        return _ptr_array([t.data_ptr() for t in ts])
+    ncls = (ctypes.c_int * G)(*classes)
+    sb, ss = (ctypes.c_int64 * G)(*[o.stride(0) for o in out]), (ctypes.c_int64 * G)(*[o.stride(1) for o in out])
+    tok = arr(tokens) if want_tokens else None
+    if w_inv is not None:
+        call("mrn_attn_greedy_decode_x3_grouped", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
+             arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(w_gen), arr(b_gen), ncls, arr(out), sb, ss, tok,
+             G, B, T, D, S, hidden, _stream())
+    else:
+        call("mrn_attn_greedy_decode_grouped_f32", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
+             arr(w_ih), arr(w_hh), arr(b_hh), arr(w_gen), arr(b_gen), ncls, arr(out), sb, ss, tok,
+             G, B, T, D, S, hidden, _stream())
+    return (out, tokens) if want_tokens else out
+
+
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):
     """(h2h.weight [H,H], rnn.weight_ih [4H, D+E], rnn.weight_hh [4H,H]) -> (three pack_fragment_major_h streams, w_inv float[3])"""
     a, b, c = pack_fragment_major_h(w_h2h.detach()), pack_fragment_major_h(w_ih.detach()[:, :D].contiguous()), pack_fragment_major_h(w_hh.detach())
