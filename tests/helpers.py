@@ -240,3 +240,47 @@ def fake_text_samples(path, seed=5):
         ids = W.randint(name + ":lab", (L,), 0, len(alphabet), seed)
         labels.append("".join(alphabet[j] for j in ids))
     return images, labels
+
+
+def bn_bwd_reference(dz, keep, y, mean, invstd, gamma, dtype=torch.float64):
+    """BatchNorm2d(train) backward with the ReLU mask, written out: the yardstick of ops.bn_bwd.  dz, y [..., C] (any leading
+    dims: the rows), keep a 0/1 tensor like dz or None (no ReLU), mean / invstd / gamma [C].  Everything is cast to `dtype`
+    first (float64: the reference; float32: the baseline a plain fp32 evaluation of the same formula reaches).
+    -> dy, dgamma, dbeta, dres with g = dz * keep, xhat = (y - mean) * invstd,
+    dy = gamma * invstd * (g - sum(g) / N - xhat * sum(g * xhat) / N), dgamma = sum(g * xhat), dbeta = sum(g), dres = g"""
+    C = y.shape[-1]
+    dz, y = dz.detach().to(dtype).reshape(-1, C), y.detach().to(dtype).reshape(-1, C)
+    mean, invstd, gamma = mean.detach().to(dtype), invstd.detach().to(dtype), gamma.detach().to(dtype)
+    g = dz if keep is None else dz * keep.detach().to(dtype).reshape(-1, C)
+    n = y.shape[0]
+    xhat = (y - mean) * invstd
+    dbeta = g.sum(0)
+    dgamma = (g * xhat).sum(0)
+    dy = gamma * invstd * (g - dbeta / n - xhat * (dgamma / n))
+    return dy, dgamma, dbeta, g
+
+
+def pack_relu_mask(z):
+    """uint8 [numel / 4]: bit j of byte i is set when element 4 i + j of z (flattened) is > 0 -- the ReLU mask layout
+    scale_shift_act_kernel writes for the backward pass (ops.scale_shift_act pos_mask, ops.bn_bwd zmask)"""
+    pos = (z.detach().reshape(-1, 4) > 0).to(torch.uint8)
+    return pos[:, 0] | (pos[:, 1] << 1) | (pos[:, 2] << 2) | (pos[:, 3] << 3)
+
+
+def unpack_relu_mask(mask):
+    """inverse of pack_relu_mask: bool [4 * numel]"""
+    bits = torch.arange(4, device=mask.device, dtype=torch.uint8)
+    return ((mask.reshape(-1, 1) >> bits) & 1).bool().reshape(-1)
+
+
+def rel_err(got, ref):
+    """max |got - ref| relative to max |ref| (absolute where the reference is all zero), in float64"""
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    if ref.numel() == 0:
+        return 0.0
+    scale = float(ref.abs().max())
+    return float((got - ref).abs().max()) / (scale if scale > 0 else 1.0)
+
+
+F32_FLOOR = 4 * 2.0 ** -24        # two fp32 roundings of the result itself: the floor under every "8 x the fp32 baseline" bound
