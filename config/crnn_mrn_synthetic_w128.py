@@ -8,4 +8,6 @@ model = dict(model_name="CRNN", Transformation="None", FeatureExtraction="VGG", 
 optimizer = dict(schedule="super", optimizer="adam", lr=0.0005, sgd_momentum=0.9, sgd_weight_decay=0.000001, milestones=[2000, 4000],
                  lrate_decay=0.1, rho=0.95, eps=1e-8, lr_drop_rate=0.1)
 train = dict(saved_model="", Aug="None", workers=0, lan_list=["Chinese", "Latin", "Japanese"], valid_datas=["synthetic"],
-             select_data=["synthetic"], NED=True, batch_size=64, num_iter=20, val_interval=10, grad_clip=5)
+             select_data=["synthetic"], NED=True, batch_size=64, num_iter=20, val_interval=10, grad_clip=5,
+             ctc_decode="greedy")   # how validation() decodes the CTC head: "greedy" (best path) or "beam" (prefix beam search of
+#                                     beam_width = 8 entries over the beam_top_n = 15 best classes of a frame; mrn_amd/modules/decoding.py)

@@ -1614,6 +1614,29 @@ def greedy_score(idx, prob, label, label_len, canon, mode, eos=0):
     return tokens, result, confidence, packed
 
 
+def ctc_beam_decode(logits, beam_width, top_n):
+    """CTC prefix beam search of one batch of CTC-head logits [B,T,C], class 0 the blank (include/mrn_decode.h: mrn_ctc_beam_decode_f32):
+    beam_width entries are kept per frame, only the top_n non-blank classes of a frame extend a prefix
+    -> (tokens int32 [B,W,T], length int32 [B,W] (-1 = dead slot), score fp32 [B,W] = log-probability of the label, entries in
+    descending score; path int64 [B,T], prob fp32 [B,T]: the best entry as the (index, probability) rows greedy_score takes).
+    Batch and step strides are honoured (MRN hands out padded-row views); the last dimension is contiguous.  The limits
+    (modules/decoding.py) are the caller's to keep: outside them the call is an error, never a host fallback"""
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
+        raise RuntimeError("ctc_beam_decode needs a CUDA (HIP) fp32 tensor [B,T,C] with a contiguous last dimension; there is no "
+                           "CPU fallback")
+    B, T, C = logits.shape
+    W, K = int(beam_width), int(top_n)
+    shape = (B, max(W, 0), T)
+    tokens = torch.empty(shape, device=logits.device, dtype=torch.int32)
+    length = torch.empty(shape[:2], device=logits.device, dtype=torch.int32)
+    score = torch.empty(shape[:2], device=logits.device, dtype=torch.float32)
+    path = torch.empty(B, T, device=logits.device, dtype=torch.int64)
+    prob = torch.empty(B, T, device=logits.device, dtype=torch.float32)
+    call("mrn_ctc_beam_decode_f32", _p(logits), logits.stride(0), logits.stride(1), B, T, C, W, K, _p(tokens), _p(length), _p(score),
+         _p(path), _p(prob), _stream())
+    return tokens, length, score, path, prob
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     """LayerNorm over the last dim of (strided) rows -> (y, mean, rstd)"""
     x2 = rows2d(x)

@@ -12,6 +12,14 @@ Reference quirks reproduced on purpose (pinned by tests/golden/validation.npz):
     character (and the last probability) is dropped (test.py:224-226);
   * the returned strings / confidences / labels are those of the LAST batch only (test.py:270-279);
   * an empty pruned prediction has confidence 0 (the reference's bare `except`, test.py:262-265).
+
+opt.ctc_decode = "beam" (modules/decoding.py; absent or "greedy": best path, as above and bit for bit) decodes a CTC head by prefix
+beam search of width opt.beam_width over the opt.beam_top_n best classes of a frame: one mrn_ctc_beam_decode_f32 launch per batch,
+or the float64 host form for predictions that are not on the GPU and for batches outside the kernel's limits.  The decoder hands
+over the best label as a row of frames whose greedy collapse is that label, and its probability as that row's first factor, so
+everything behind the decoding line -- scoring on either path, the returned strings -- is the code above, unchanged; the confidence
+is then the label's (pruned) probability instead of the product of the per-frame maxima.  The attention head has no alignments to
+sum over: it ignores the option.
 """
 import time
 
@@ -20,6 +28,7 @@ import torch
 
 from . import functional as Fn
 from . import ops
+from .modules import decoding as D
 from .modules import scoring as S
 
 SCORE_TIMER = None     # a list here collects, per batch, the host seconds from the loss being on the host to the scores being there
@@ -109,6 +118,15 @@ def _device_scores(labels, preds_index, preds_max_prob, converter, canon, attn, 
     return out, (tokens, result), {b: st for b, (_, st) in host_rows.items()}
 
 
+def _beam_pair(preds, prediction, width, top_n):
+    """the beam decoder's (path, prob) for CTC logits [B,T,C], on the device of `preds`: one launch when the kernel takes the batch,
+    else the host form"""
+    if preds.is_cuda and D.beam_supported(prediction, preds.size(1), preds.size(2), width, top_n):
+        return ops.ctc_beam_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), width, top_n)[3:]
+    path, prob = D.ctc_beam_host(preds.detach().cpu().numpy(), width, top_n)[3:]
+    return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
+
+
 def validation(model, criterion, evaluation_loader, converter, opt, val_choose="val", tqdm_position=1):
     n_correct, norm_ED, length_of_data, infer_time = 0, 0.0, 0, 0.0
     loss_sum, loss_n = 0.0, 0
@@ -117,6 +135,7 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     dev = params[0].device if params else torch.device("cuda" if torch.cuda.is_available() else "cpu")
     attn, ned = "Attn" in opt.Prediction, getattr(opt, "NED", False)
     canon, last = None, None
+    ctc_decode, beam_width, beam_top_n = D.decode_options(opt)
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
         length_of_data += batch_size
@@ -139,7 +158,10 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         loss_n += 1
         if SCORE_TIMER is not None:
             t_score = time.perf_counter()
-        preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                         # :211, :218-219
+        if ctc_decode == "beam" and not attn:
+            preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
+        else:
+            preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                     # :211, :218-219
         T = preds.size(1)
         width = max((len(gt) for gt in labels), default=0)
         if preds_index.is_cuda and S.device_scoring_supported(converter, opt.Prediction, T, width):
