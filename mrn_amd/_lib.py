@@ -1,6 +1,7 @@
 """ctypes binding of libmrn_hip.so.
 
-Signatures are parsed from include/mrn_hip.h and include/mrn_decode.h, so the headers are the single source of truth for the C ABI.
+Signatures are parsed from include/mrn_hip.h, include/mrn_decode.h and include/mrn_attn_beam.h, so the headers are the single source of
+truth for the C ABI.
 There is no CPU fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
@@ -15,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRN_LIB_PATH") or os.path.join(_HERE, "csrc", "libmrn_hip.so")   # (override: A/B builds)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_hip.h")
 DECODE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_decode.h")     # the decoders' part of the C ABI
+ATTN_BEAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_attn_beam.h")     # beam search on the attention head
 
 _CTYPES = {
     "int": ctypes.c_int,
@@ -69,7 +71,7 @@ class _Lib:
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `python -m mrn_amd.build` (there is no CPU fallback)")
         dll = ctypes.CDLL(LIB_PATH)
-        self._protos = {**parse_header(), **parse_header(DECODE_HEADER_PATH)}
+        self._protos = {**parse_header(), **parse_header(DECODE_HEADER_PATH), **parse_header(ATTN_BEAM_HEADER_PATH)}
         for name, (ret, argtypes, _) in self._protos.items():
             fn = getattr(dll, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = _CTYPES[ret]

@@ -1336,6 +1336,450 @@ __global__ void embed_gather_kernel(const long* __restrict__ idx, const float* _
   for (int e = threadIdx.x; e < E; e += blockDim.x) out[i * E + e] = table[k * E + e];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Beam-search decoding on the attention head (extends reference modules/prediction.py:70-86; the algorithm is stated in
+// mrn_amd/modules/decoding.py), all S steps of all experts in one launch.  The 16 MFMA rows of a workgroup are 16 / W samples x W
+// entries: row r is entry r % W of sample b0 + r / W, rows of one sample read the same Hproj / Hb slices.  Per step:
+//   (0)-(7) as attn_greedy_kernel (whole-context form), the same arithmetic in the same order on every row, so a row's logits are
+//       bit-identical to the greedy kernel's for the same token history; the logits go to the workgroup's scratch rows in global
+//       memory (16 x C floats do not fit beside the tile in LDS), the new c of every row is staged in hp_lds, free since phase (2)
+//   (8) wave r, row r: log-sum-exp of the row, then its W best classes by W scans (larger logit first, a tie to the lower class, a
+//       NaN logit counts as -inf) -> candidates (score_r + logit - lse, class, logit - lse) in LDS; a finished row gives (score_r,
+//       eos, 0) alone, a dead row nothing
+//   (9) one thread per candidate ranks it among its sample's W x W (larger score first, ties in (row, class) order); rank q < W with
+//       a score above -inf becomes entry q of the next step: (parent, token, logp) go to the step's history record, score / token /
+//       finished to LDS
+//   (10) every row takes its parent's h (LDS planes, read to registers before a barrier, written behind it) and c (hp_lds)
+// The loop ends early once no row of the workgroup is live and unfinished (every later step would copy the entries as they are).
+// Tail: one thread per row walks the history back from the last step and writes the outputs.
+// ---------------------------------------------------------------------------------------------
+struct BeamParams {
+  GreedyParams g;                   // the greedy operands (logits / tokens_out unused)
+  float* scratch;                   // [tiles][16][Cpad + 3 * S]: per workgroup 16 logit rows, then history parent / token / logp [S][16]
+  int32_t* tokens;                  // [B][W][S]
+  int32_t* length;                  // [B][W]
+  float* score;                     // [B][W]
+  float* logp;                      // [B][W][S]
+  int64_t* path;                    // [B][S]
+  float* prob;                      // [B][S]
+};
+struct BeamGroup {
+  BeamParams g[MAX_GROUPS];
+  int tiles, groups, pinned, W, eos;
+};
+constexpr int BEAM_LDS_EXTRA = 4 * (8 * BT + 3 * BT * BT);   // token, score, finished, four next-step rows, a flag row + 16 x 16 candidates (score, class, logp)
+
+__device__ __forceinline__ bool beam_before(float va, int ia, float vb_, int ib) { return va > vb_ || (va == vb_ && ia < ib); }
+
+template <bool X3>
+__global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int gi, tile_;                  // (group, tile) placement: as attn_greedy_kernel
+  if (grp.pinned == 2) {
+    const int per = grp.groups * grp.tiles / 8;
+    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+    gi = pair / grp.tiles;
+    tile_ = pair - gi * grp.tiles;
+  } else {
+    gi = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
+    tile_ = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
+  }
+  if (gi >= grp.groups) return;
+  const BeamParams& bp = grp.g[gi];
+  const GreedyParams& gp = bp.g;
+  const AttnDecParams& p = gp.a;
+  const int D = p.D, T = p.T, C = gp.num_class, S = p.S;
+  const int W = grp.W, eos = grp.eos;
+  const int ntile = (C + 15) / 16;
+  const int CP = ntile * 16;                 // scratch row stride
+  const int CLD = D + 4;
+  const int CLDH = D + 8;
+  float* h_lds = lds;                      // the LDS map of attn_greedy_kernel's whole-context form ...
+  float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;
+  float* ctx_lds = hp_lds + BT * HLD;
+  float* e_lds = X3 ? ctx_lds + (2 * BT * CLDH) / 2 : ctx_lds + BT * CLD;
+  float* sw_lds = e_lds + BT * T;
+  int* tok_lds = reinterpret_cast<int*>(sw_lds + HID);       // ... + the beam state of BEAM_LDS_EXTRA
+  float* score_lds = reinterpret_cast<float*>(tok_lds + BT);
+  int* fin_lds = reinterpret_cast<int*>(score_lds + BT);
+  float* nsc = reinterpret_cast<float*>(fin_lds + BT);
+  int* npar = reinterpret_cast<int*>(nsc + BT);
+  int* ntok = npar + BT;
+  float* nlp = reinterpret_cast<float*>(ntok + BT);
+  int* flag_lds = reinterpret_cast<int*>(nlp + BT);
+  float* cand_v = reinterpret_cast<float*>(flag_lds + BT);
+  int* cand_c = reinterpret_cast<int*>(cand_v + BT * BT);
+  float* cand_lp = reinterpret_cast<float*>(cand_c + BT * BT);
+  _Float16* h_hi = reinterpret_cast<_Float16*>(h_lds);
+  _Float16* h_lo = h_hi + BT * LDH;
+  _Float16* c_hi = reinterpret_cast<_Float16*>(ctx_lds);
+  _Float16* c_lo = c_hi + BT * CLDH;
+  const float inv_h2h = X3 ? p.w_inv[0] : 1.f, inv_ih = X3 ? p.w_inv[1] : 1.f, inv_hh = X3 ? p.w_inv[2] : 1.f;
+  const float inv_gen = X3 ? p.w_inv[3] : 1.f;
+  const __amdgpu_buffer_rsrc_t r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * D * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? ntile * 16 * HID * 4 : 0, 0x00020000);
+
+  const int ns = BT / W;                     // samples per workgroup
+  const int nrows = ns * W;                  // rows in use
+  const int b0 = tile_ * ns;
+  const int Bend = min(p.B, b0 + ns);
+  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
+  const int col = lane & 15, rbase = (lane >> 4) * 4;
+  const int j = wave * 16 + col;
+  float* const row_scr = bp.scratch + (long)tile_ * BT * (CP + 3 * S);      // [16][CP]
+  int* const hist_par = reinterpret_cast<int*>(row_scr + (long)BT * CP);   // [S][16]
+  int* const hist_tok = hist_par + (long)S * BT;
+  float* const hist_lp = reinterpret_cast<float*>(hist_tok + (long)S * BT);
+
+  if constexpr (X3) {
+    for (int i = t_; i < BT * LDH; i += NTH) store_h_split(h_hi, h_lo, i, 0.f);
+    for (int i = t_; i < BT * HLD + BT * CLDH + BT * T; i += NTH) hp_lds[i] = 0.f;   // hp, ctx planes, e: unused rows stay zero
+  } else {
+    for (int i = t_; i < BT * HLD; i += NTH) h_lds[i] = 0.f;
+    for (int i = t_; i < BT * (HLD + CLD + T); i += NTH) hp_lds[i] = 0.f;
+  }
+  for (int i = t_; i < HID; i += NTH) sw_lds[i] = p.w_score[i];
+  if (t_ < BT) {
+    const long k = gp.start[0];
+    tok_lds[t_] = (k >= C || k < 0) ? 0 : (int)k;
+    score_lds[t_] = (t_ < nrows && t_ % W == 0 && b0 + t_ / W < Bend) ? 0.f : -INFINITY;      // one live entry per sample
+    fin_lds[t_] = 0;
+  }
+  float bh[4], c[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < 4; ++g) bh[g] = p.b_hh ? p.b_hh[g * HID + j] : 0.f;
+  const float bj = p.b_h2h[j];
+  __syncthreads();
+
+  int nst = 0;                               // steps run
+  for (int step = 0; step < S; ++step) {
+    // (1) hp = h2h(h) + bias
+    {
+      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_h2h, HID, wave, lane);
+      else mma_rows<1>(acc, h_lds, HLD, p.w_h2h, HID, wave, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hp_lds[(rbase + r) * HLD + j] = acc[0][r] * inv_h2h + bj;
+    }
+    __syncthreads();
+    // (2) e[row][t] = score . tanh(Hproj[b][t] + hp[row])
+    {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(sw_lds + lane * 4);
+      const int npair = nrows * T;
+      constexpr int U = 4;
+      for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
+        f32x4 hv[U];
+        int rows[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int pr = pr0 + u;
+          const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
+          rows[u] = row;
+          const int b = b0 + row / W;
+          hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (pr < npair && b < Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
+        }
+        float sacc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const f32x4 pv = *reinterpret_cast<const f32x4*>(hp_lds + rows[u] * HLD + lane * 4);
+          float s = 0.f;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
+          sacc[u] = s;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
+        }
+        if (lane < U && pr0 + lane < npair) {
+          float v = sacc[0];
+#pragma unroll
+          for (int u = 1; u < U; ++u) v = lane == u ? sacc[u] : v;
+          e_lds[pr0 + lane] = (b0 + ((pr0 + lane) / T) / W < Bend) ? v : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    // (3) softmax over t, one wave per row
+    if (wave < nrows) {
+      const int row = wave;
+      float m = -INFINITY;
+      for (int t = lane; t < T; t += 64) m = fmaxf(m, e_lds[row * T + t]);
+      m = wave_max(m);
+      float sum = 0.f;
+      for (int t = lane; t < T; t += 64) {
+        const float v = expf(e_lds[row * T + t] - m);
+        e_lds[row * T + t] = v;
+        sum += v;
+      }
+      sum = wave_sum(sum);
+      const float inv = 1.f / sum;
+      for (int t = lane; t < T; t += 64) e_lds[row * T + t] *= inv;
+    }
+    __syncthreads();
+    // (0) the token's row of etab: the initial value of the gate accumulators (lands during phase (4))
+    f32x4 acc5[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* ep = gp.etab + (long)tok_lds[rbase + r] * (4 * HID) + j;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
+    }
+    // (4) context[row][:] = sum_t alpha[row][t] * Hb[b][t][:]
+    for (int it = t_; it < nrows * (D / 4); it += NTH) {
+      const int row = it / (D / 4), c4 = it - row * (D / 4);
+      const int b = b0 + row / W;
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (b < Bend) {
+        const float* hb = p.Hb + (long)b * T * D + c4 * 4;
+        int t = 0;
+#pragma unroll 1
+        for (; t + 4 <= T; t += 4) {
+          f32x4 v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float w = e_lds[row * T + t + u];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
+          }
+        }
+        for (; t < T; ++t) {
+          const float w = e_lds[row * T + t];
+          const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
+        }
+      }
+      if constexpr (X3) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
+      } else {
+        *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
+      }
+    }
+    __syncthreads();
+    // (5) gates = etab[token] + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
+    {
+      f32x4 acc[4];
+      const float pre_ih = 1.f / inv_ih;               // (a power of two)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
+      if constexpr (X3) {
+        mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
+        const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] *= ratio;
+        mma_rows_hb<4>(acc, h_hi, h_lo, r_hh, HID, wave, lane);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
+      } else {
+        mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
+        mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
+      }
+      __syncthreads();  // every wave has finished reading h_lds
+      float h[4], act[4][4];
+      lstm_pointwise0(acc, bh, c, h, act);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rbase + r, b = b0 + row / W;
+        if constexpr (X3) store_h_split(h_hi, h_lo, row * LDH + j, b < Bend ? h[r] : 0.f);
+        else h_lds[row * HLD + j] = b < Bend ? h[r] : 0.f;
+        hp_lds[row * HLD + j] = c[r];                   // staged for (10)
+      }
+    }
+    __syncthreads();
+    // (7) generator on the new h -> the workgroup's scratch rows
+#pragma unroll 1
+    for (int n = wave; n < ntile; n += NW) {
+      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_gen, HID, n, lane);
+      else mma_rows<1>(acc, h_lds, HLD, gp.w_gen + (long)n * (HID / 16) * 256, HID, 0, lane);   // (wave argument 0: see attn_greedy_kernel)
+      const int cls = n * 16 + col;
+      if (cls < C) {
+        const float bg = gp.b_gen[cls];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) row_scr[(long)(rbase + r) * CP + cls] = acc[0][r] * inv_gen + bg;
+      }
+    }
+    __syncthreads();
+    // (8) row `wave`: log-sum-exp and the W best classes
+    {
+      const int row = wave;
+      const float sc = score_lds[row];
+      const bool live = row < nrows && b0 + row / W < Bend && sc > -INFINITY;
+      if (lane < W) {
+        cand_v[row * BT + lane] = -INFINITY;
+        cand_c[row * BT + lane] = 0x7fffffff;
+        cand_lp[row * BT + lane] = 0.f;
+      }
+      if (lane == 0) {                       // the next step's row, dead until (9) fills it
+        nsc[row] = -INFINITY;
+        npar[row] = row;
+        ntok[row] = eos;
+        nlp[row] = 0.f;
+      }
+      if (live && fin_lds[row]) {
+        if (lane == 0) {
+          cand_v[row * BT] = sc;
+          cand_c[row * BT] = eos;
+        }
+      } else if (live) {
+        const float* x = row_scr + (long)row * CP;
+        float m = -INFINITY;
+        for (int k = lane; k < C; k += 64) {
+          const float v = x[k];
+          m = fmaxf(m, v == v ? v : -INFINITY);
+        }
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int k = lane; k < C; k += 64) {
+          const float v = x[k];
+          sum += v == v ? expf(v - m) : 0.f;
+        }
+        sum = wave_sum(sum);
+        const float lse = m + logf(sum);
+        float pv = INFINITY;
+        int pc = -1;
+        for (int q = 0; q < W; ++q) {
+          float bv = -INFINITY;
+          int bc = 0x7fffffff;
+          for (int k = lane; k < C; k += 64) {
+            float v = x[k];
+            v = v == v ? v : -INFINITY;
+            if ((v < pv || (v == pv && k > pc)) && beam_before(v, k, bv, bc)) {
+              bv = v;
+              bc = k;
+            }
+          }
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oc = __shfl_xor(bc, o);
+            if (beam_before(ov, oc, bv, bc)) {
+              bv = ov;
+              bc = oc;
+            }
+          }
+          if (bc >= C) break;                 // fewer than W classes
+          if (lane == 0) {
+            const float lp = bv - lse;
+            const float cv = sc + lp;
+            cand_v[row * BT + q] = cv == cv ? cv : -INFINITY;
+            cand_c[row * BT + q] = bc;
+            cand_lp[row * BT + q] = lp;
+          }
+          pv = bv;
+          pc = bc;
+        }
+      }
+    }
+    __syncthreads();
+    // (9) rank every candidate among its sample's
+    if (t_ < BT * BT) {
+      const int row = t_ >> 4, q = t_ & 15;
+      if (row < nrows && q < W) {
+        const float v = cand_v[t_];
+        if (v > -INFINITY) {
+          const int cc = cand_c[t_];
+          const int r0 = (row / W) * W;
+          int rank = 0;
+          for (int i = r0; i < r0 + W; ++i)
+            for (int k = 0; k < W; ++k) {
+              const float ov = cand_v[i * BT + k];
+              const int oc = cand_c[i * BT + k];
+              rank += (ov > v || (ov == v && (i < row || (i == row && oc < cc)))) ? 1 : 0;
+            }
+          if (rank < W) {
+            nsc[r0 + rank] = v;
+            npar[r0 + rank] = row;
+            ntok[r0 + rank] = cc;
+            nlp[r0 + rank] = cand_lp[t_];
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // (10) every row takes its parent's state; the step's history record
+    float hf[4];
+    _Float16 hh[4], hl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int par = npar[rbase + r];
+      c[r] = hp_lds[par * HLD + j];
+      if constexpr (X3) {
+        hh[r] = h_hi[par * LDH + j];
+        hl[r] = h_lo[par * LDH + j];
+      } else {
+        hf[r] = h_lds[par * HLD + j];
+      }
+    }
+    if (t_ < BT) {
+      const float v = nsc[t_];
+      const int tk = ntok[t_];
+      hist_par[step * BT + t_] = npar[t_];
+      hist_tok[step * BT + t_] = tk;
+      hist_lp[step * BT + t_] = nlp[t_];
+      score_lds[t_] = v;
+      tok_lds[t_] = tk;
+      fin_lds[t_] = tk == eos ? 1 : 0;
+      const unsigned long long open = __ballot(v > -INFINITY && tk != eos);    // (threads 0 ... 15: one wave)
+      if (t_ == 0) flag_lds[0] = (open & 0xffffull) != 0 ? 1 : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rbase + r;
+      if constexpr (X3) {
+        h_hi[row * LDH + j] = hh[r];
+        h_lo[row * LDH + j] = hl[r];
+      } else {
+        h_lds[row * HLD + j] = hf[r];
+      }
+    }
+    const int go_on = flag_lds[0];
+    nst = step + 1;
+    __syncthreads();
+    if (!go_on) break;
+  }
+
+  // tail: walk the history back from the last step run; behind it (an early stop: every live entry is finished) the fill
+  if (t_ < BT) {
+    const int row = t_, b = b0 + row / W, q = row % W;
+    if (row < nrows && b < Bend) {
+      const float sc = score_lds[row];
+      const bool live = sc > -INFINITY;
+      int32_t* tk = bp.tokens + ((long)b * W + q) * S;
+      float* lp = bp.logp + ((long)b * W + q) * S;
+      int first = S;                          // step of the first eos
+      int cur = row;
+      for (int s = S - 1; s >= 0; --s) {
+        int tok = eos;
+        float l = 0.f;
+        if (live && s < nst) {
+          tok = hist_tok[s * BT + cur];
+          l = hist_lp[s * BT + cur];
+          cur = hist_par[s * BT + cur];
+          if (tok == eos) first = s;
+        }
+        tk[s] = tok;
+        lp[s] = l;
+        if (q == 0) {
+          bp.path[(long)b * S + s] = tok;
+          bp.prob[(long)b * S + s] = expf(l);
+        }
+      }
+      bp.length[(long)b * W + q] = live ? (first < S ? first + 1 : S) : -1;
+      bp.score[(long)b * W + q] = live ? sc : -INFINITY;
+    }
+  }
+}
+
 }  // namespace
 
 static int lstm_launch(LstmGroup& grp, int groups, int hidden, hipStream_t st) {
@@ -1791,4 +2235,114 @@ MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, cons
                      n, E, num_class, (long)idx_stride, S);
   MRN_LAUNCH_CHECK("embed_gather");
   return MRN_OK;
+}
+
+// ---- beam-search decoding on the attention head: attn_beam_kernel (include/mrn_attn_beam.h) ----------------
+template <bool X3>
+static void beam_kernel_launch(const BeamGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024)
+    hipFuncSetAttribute((const void*)attn_beam_kernel<X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_beam_kernel<X3>), grid, dim3(NTH), lds, st, grp);
+}
+
+// the whole-context tile of greedy_launch plus the beam state; there is no chunked form (ops.attn_beam_whole_context restates the sum)
+static size_t beam_lds(bool x3, int D, int T) {
+  return sizeof(float) * (2 * BT * HLD + BT * (D + 4) + BT * T + HID) + (x3 ? 1024 : 0) + BEAM_LDS_EXTRA;
+}
+
+static int beam_launch(BeamGroup& grp, int groups, int D, int T, hipStream_t st) {
+  grp.groups = groups;
+  const int B = grp.g[0].g.a.B;
+  grp.tiles = ceil_div(B, BT / grp.W);       // 16 / W samples per workgroup
+  grp.pinned = groups > 1 && grp.tiles * ceil_div(groups, 8) <= 32;
+  if (groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
+  const bool x3 = grp.g[0].g.a.w_inv != nullptr;
+  const size_t lds = beam_lds(x3, D, T);
+  const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
+  if (x3) beam_kernel_launch<true>(grp, grid, lds, st);
+  else beam_kernel_launch<false>(grp, grid, lds, st);
+  MRN_LAUNCH_CHECK("attn_beam");
+  return MRN_OK;
+}
+
+// `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch per MAX_GROUPS experts.  Every limit is
+// checked for every group before the first launch
+static int beam_grouped(const char* who, bool x3, const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                        const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h, const void* const* w_score,
+                        const void* const* w_ih_ctx, const void* const* w_hh, const void* const* w_inv, const void* const* b_hh,
+                        const void* const* w_gen, const void* const* b_gen, const int* num_class, int eos, int W,
+                        const void* const* scratch, int64_t scratch_floats, const void* const* tokens, const void* const* length,
+                        const void* const* score, const void* const* logp, const void* const* path, const void* const* prob,
+                        int groups, int B, int T, int D, int S, int hidden, void* stream) {
+  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && (!x3 || w_inv) && w_gen && b_gen &&
+                    num_class && scratch && tokens && length && score && logp && path && prob && groups >= 1, "%s: null operand", who);
+  MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
+  MRN_CHECK_ARG(W >= 1 && W <= BT, "%s: beam width W=%d outside 1 ... %d", who, W, BT);
+  MRN_CHECK_ARG(S >= 1 && S <= 512, "%s: S=%d steps outside 1 ... 512", who, S);
+  MRN_CHECK_ARG(D > 0 && D % (x3 ? 32 : 16) == 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
+  MRN_CHECK_ARG(B >= 0 && T > 0, "%s: bad geometry (B=%d T=%d)", who, B, T);
+  MRN_CHECK_ARG(beam_lds(x3, D, T) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+  const long tiles = ceil_div(B, BT / W);
+  for (int g = 0; g < groups; ++g) {
+    MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&
+                      w_gen[g] && b_gen[g] && (B == 0 || (scratch[g] && tokens[g] && length[g] && score[g] && logp[g] && path[g] && prob[g])),
+                  "%s: null operand in group %d", who, g);
+    MRN_CHECK_ARG(num_class[g] >= 2, "%s: num_class=%d in group %d (at least 2)", who, num_class[g], g);
+    MRN_CHECK_ARG(eos >= 0 && eos < num_class[g], "%s: eos=%d outside the %d classes of group %d", who, eos, num_class[g], g);
+    const long need = tiles * BT * ((long)ceil_div(num_class[g], 16) * 16 + 3L * S);
+    MRN_CHECK_ARG(scratch_floats >= need, "%s: scratch of %ld floats, group %d needs %ld", who, (long)scratch_floats, g, need);
+  }
+  if (B == 0) return MRN_OK;
+  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
+    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
+    BeamGroup grp;
+    memset(&grp, 0, sizeof(grp));
+    grp.W = W;
+    grp.eos = eos;
+    for (int i = 0; i < n; ++i) {
+      const int g = g0 + i;
+      BeamParams& bp = grp.g[i];
+      greedy_fill(bp.g, (const float*)Hb[g], (const float*)Hproj[g], (const float*)etab[g], start_token, (const float*)w_h2h[g],
+                  (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g], (const float*)w_hh[g],
+                  x3 ? (const float*)w_inv[g] : nullptr, b_hh ? (const float*)b_hh[g] : nullptr, (const float*)w_gen[g],
+                  (const float*)b_gen[g], num_class[g], nullptr, 0, 0, nullptr, B, T, D, S);
+      bp.scratch = (float*)scratch[g];
+      bp.tokens = (int32_t*)tokens[g];
+      bp.length = (int32_t*)length[g];
+      bp.score = (float*)score[g];
+      bp.logp = (float*)logp[g];
+      bp.path = (int64_t*)path[g];
+      bp.prob = (float*)prob[g];
+    }
+    const int rc = beam_launch(grp, n, D, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return MRN_OK;
+}
+
+MRN_EXPORT int mrn_attn_beam_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                                const int* num_class, int eos, int W, const void* const* scratch, int64_t scratch_floats,
+                                                const void* const* tokens, const void* const* length, const void* const* score,
+                                                const void* const* logp, const void* const* path, const void* const* prob, int groups,
+                                                int B, int T, int D, int S, int hidden, void* stream) {
+  return beam_grouped("mrn_attn_beam_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
+                      nullptr, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, B, T, D, S, hidden, stream);
+}
+
+MRN_EXPORT int mrn_attn_beam_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                               const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                               const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                               const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                               const void* const* b_gen, const int* num_class, int eos, int W,
+                                               const void* const* scratch, int64_t scratch_floats, const void* const* tokens,
+                                               const void* const* length, const void* const* score, const void* const* logp,
+                                               const void* const* path, const void* const* prob, int groups, int B, int T, int D, int S,
+                                               int hidden, void* stream) {
+  return beam_grouped("mrn_attn_beam_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv,
+                      b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob, groups, B,
+                      T, D, S, hidden, stream);
 }

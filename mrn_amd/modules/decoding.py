@@ -20,6 +20,26 @@ Outputs per sample, entries in descending total: tokens [W][T] (0 behind the pre
 the best entry the pair that goes wherever argmax_prob_lastdim's goes: path [T] = its classes with one blank between equal
 neighbours, blanks behind (the greedy collapse gives the prefix back) and prob [T] = [exp(score), 1, 1, ...] (the cumulative product
 is exp(score): multiplying by 1.0 is exact).
+
+The attention head (reference modules/prediction.py:70-86 feeds the arg-max back: one hypothesis) is decoded by beam search with
+opt.attn_decode = "beam"; the width is opt.beam_width.  mrn_attn_beam_decode_* (mrn_amd/csrc/rnn.hip attn_beam_kernel) runs it in
+float32, all steps of all experts in one launch, attn_beam_host below in float64.  Per sample: width W, S = batch_max_length + 1 steps,
+start token sos, end token eos.  An entry is (tokens, score, finished, h, c).  Start: one live entry (no tokens, score 0, h = c = 0, fed
+sos); the other W - 1 slots are dead (score -inf).  Per step:
+
+  1. every live unfinished entry i runs the attention cell of modules/prediction.py on its last token (a token >= num_class or < 0
+     counts as 0, as in greedy) and lp = log_softmax(generator(h)) over the num_class real classes;
+  2. entry i gives the candidates (i, c) with score_i + lp[c]; a finished entry (its last token is eos) gives the single candidate
+     (i, eos) with its score unchanged, and keeps its tokens;
+  3. the W candidates of largest score survive, ties in candidate order (i, then c); a NaN score counts as -inf, and a candidate of
+     score -inf never survives (its slot is dead);
+  4. a survivor takes its parent's new (h, c); it is finished if c == eos.
+
+There is no length normalisation.  Decoding may stop once every live entry is finished: further steps change nothing.  Outputs per
+sample, entries in descending score: tokens int32 [W][S] (eos behind the first eos), length [W] (the tokens up to and including eos, S
+for an entry that never finished, -1 = dead slot), score [W] (-inf for a dead slot), logp [W][S] (the log-probability of each chosen
+token, 0 behind the first eos); and for the best entry path int64 [S] and prob [S] = exp(logp), 1.0 behind the first eos: the pair
+argmax_prob_lastdim hands the scorer.  With W = 1 this is greedy decoding.
 """
 import numpy as np
 
@@ -31,6 +51,11 @@ BEAM_MAX_T = 512             # frames mrn_ctc_beam_decode_f32 takes (the scorer'
 BEAM_MAX_CLASSES = 65535     # classes are 16-bit tokens there
 BEAM_MAX_WIDTH = 16          # entries live in lanes, candidates four per lane: W * (K + 1) <= 256
 BEAM_MAX_TOP_N = 15
+
+ATTN_DECODERS = ("greedy", "beam")
+ATTN_BEAM_MAX_WIDTH = 16     # the 16 MFMA rows of a workgroup are 16 / W samples x W entries
+ATTN_BEAM_MAX_STEPS = 512
+ATTN_EOS = 3                 # AttnLabelConverter (tools/utils.py): [UNK]=0 [PAD]=1 [SOS]=2 [EOS]=3 -- the end token of the evaluation forwards
 
 
 def _positive_int(opt, name, default):
@@ -46,6 +71,25 @@ def decode_options(opt):
     if mode not in CTC_DECODERS:
         raise ValueError(f"ctc_decode must be one of {CTC_DECODERS}, got {mode!r}")
     return mode, _positive_int(opt, "beam_width", DEFAULT_BEAM_WIDTH), _positive_int(opt, "beam_top_n", DEFAULT_BEAM_TOP_N)
+
+
+def attn_decode_options(opt):
+    """(attn_decode, width) of an options object; absent keys are "greedy", 8.  The width is beam_width, the key the CTC decoder reads"""
+    mode = getattr(opt, "attn_decode", "greedy")
+    if mode not in ATTN_DECODERS:
+        raise ValueError(f"attn_decode must be one of {ATTN_DECODERS}, got {mode!r}")
+    return mode, _positive_int(opt, "beam_width", DEFAULT_BEAM_WIDTH)
+
+
+def attn_beam_request(attn_beam, prediction, is_train):
+    """the width an evaluation forward decodes by beam search with, or None: attn_beam is set, the head is an attention head, the call is
+    an evaluation under no_grad"""
+    import torch
+    if attn_beam is None or "Attn" not in prediction or is_train or torch.is_grad_enabled():
+        return None
+    if isinstance(attn_beam, bool) or not isinstance(attn_beam, (int, np.integer)) or attn_beam < 1:
+        raise ValueError(f"attn_beam must be an integer >= 1, got {attn_beam!r}")
+    return int(attn_beam)
 
 
 def beam_supported(prediction, T, C, W, K):
@@ -137,3 +181,93 @@ def ctc_beam_host(logits, W, K):
             path[b] = frame_path(entries[0][0], T)
         prob[b, 0] = np.float32(np.exp(score[b, 0]))
     return tokens, length, score, path, prob
+
+
+def _f64(v):
+    return np.asarray(v.detach().cpu() if hasattr(v, "detach") else v).astype(np.float64)
+
+
+def _sigmoid(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
+def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=False):
+    """float64 beam search on the attention head: sd = a state dict of modules/prediction.py Attention (tensors or arrays), batch_H
+    [B][T][D] -> (tokens int32 [B][W][S], length int32 [B][W], score float64 [B][W], logp float64 [B][W][S], path int64 [B][S], prob
+    float32 [B][S]): the outputs of ops.attn_beam_decode, for CPU tensors and as the kernel's yardstick.  Any width >= 1.
+    want_margin adds margin float64 [B]: the smallest gap, over the steps, between neighbouring kept candidates and between the last
+    kept and the best dropped one, divided by the step's token count (a score of n tokens is known to n times a token's band)"""
+    W, S = int(width), int(batch_max_length) + 1
+    w = {k: _f64(v) for k, v in sd.items()}
+    Hb = _f64(batch_H)
+    if Hb.ndim != 3 or W < 1 or S < 1:
+        raise ValueError(f"attn_beam_host needs batch_H [B][T][D], width >= 1 and batch_max_length >= 0, got {Hb.shape}, {W}, {S - 1}")
+    B, T, D = Hb.shape
+    emb, gen_w, gen_b = w["char_embeddings.weight"], w["generator.weight"], w["generator.bias"]
+    C, Hd = gen_w.shape
+    if not 0 <= eos < C:
+        raise ValueError(f"eos={eos} outside the {C} classes")
+    a = "attention_cell."
+    Hproj = Hb @ w[a + "i2h.weight"].T                                    # [B][T][H]
+    h, c = np.zeros((B, W, Hd)), np.zeros((B, W, Hd))
+    last = np.full((B, W), int(sos), dtype=np.int64)
+    score = np.full((B, W), -np.inf)
+    score[:, 0] = 0.0
+    finished = np.zeros((B, W), dtype=bool)
+    tokens = np.full((B, W, S), eos, dtype=np.int32)
+    logp = np.zeros((B, W, S))
+    margin = np.full(B, np.inf)
+    rows = np.arange(B)[:, None]
+    for s in range(S):
+        if not ((score > -np.inf) & ~finished).any():
+            break
+        tok = np.where((last >= C) | (last < 0), 0, last)
+        hp = h @ w[a + "h2h.weight"].T + w[a + "h2h.bias"]
+        e = np.tanh(Hproj[:, None] + hp[:, :, None, :]) @ w[a + "score.weight"][0]              # [B][W][T]
+        e = np.exp(e - e.max(axis=2, keepdims=True))
+        alpha = e / e.sum(axis=2, keepdims=True)
+        ctx = np.einsum("bwt,btd->bwd", alpha, Hb)
+        g = (np.concatenate([ctx, emb[tok]], axis=2) @ w[a + "rnn.weight_ih"].T + w[a + "rnn.bias_ih"]
+             + h @ w[a + "rnn.weight_hh"].T + w[a + "rnn.bias_hh"])
+        gi, gf, gg, go = np.split(g, 4, axis=2)
+        c2 = _sigmoid(gf) * c + _sigmoid(gi) * np.tanh(gg)
+        h2 = _sigmoid(go) * np.tanh(c2)
+        x = h2 @ gen_w.T + gen_b                                          # [B][W][C]
+        x = np.where(np.isnan(x), -np.inf, x)
+        peak = x.max(axis=2, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lp = x - (peak + np.log(np.exp(x - peak).sum(axis=2, keepdims=True)))
+            cand = score[:, :, None] + lp
+        done = np.full((B, W, C), -np.inf)
+        done[:, :, eos] = score
+        cand = np.where(finished[:, :, None], done, cand)
+        cand[np.isnan(cand)] = -np.inf
+        flat = cand.reshape(B, W * C)                                     # candidate order (i, c)
+        order = np.argsort(-flat, axis=1, kind="stable")[:, :W + 1]
+        top = np.take_along_axis(flat, order, axis=1)
+        if top.shape[1] < W + 1:
+            top = np.concatenate([top, np.full((B, W + 1 - top.shape[1]), -np.inf)], axis=1)
+        with np.errstate(invalid="ignore"):
+            gaps = np.where(top[:, :W] > -np.inf, top[:, :W] - top[:, 1:W + 1], np.inf)
+        margin = np.minimum(margin, gaps.min(axis=1) / (s + 1))
+        keep = order[:, :W]
+        if keep.shape[1] < W:
+            keep = np.concatenate([keep, np.zeros((B, W - keep.shape[1]), dtype=keep.dtype)], axis=1)
+        new_score = top[:, :W]
+        par, cls = keep // C, keep % C
+        alive = new_score > -np.inf
+        was_done = finished[rows, par]
+        tokens, logp = tokens[rows, par], logp[rows, par]
+        tokens[:, :, s] = np.where(alive, cls, eos)
+        logp[:, :, s] = np.where(alive & ~was_done, lp[rows, par, cls], 0.0)
+        tokens[~alive], logp[~alive] = eos, 0.0
+        h, c = h2[rows, par], c2[rows, par]
+        last = np.where(alive, cls, eos)
+        finished = alive & (cls == eos)
+        score = new_score
+    alive = score > -np.inf
+    is_eos = tokens == eos
+    length = np.where(is_eos.any(axis=2), is_eos.argmax(axis=2) + 1, S).astype(np.int32)
+    length[~alive] = -1
+    out = (tokens, length, score, logp, tokens[:, 0].astype(np.int64), np.exp(logp[:, 0]).astype(np.float32))
+    return out + (margin,) if want_margin else out

@@ -728,9 +728,10 @@ class HeadsGroup(SequenceGroup):
             return False
         return SequenceGroup.sequence_supported([e.model for e in experts])
 
-    def run_greedy(self, visual, start, feats_out, logits_out):
+    def run_greedy(self, visual, start, feats_out, logits_out, beam=None):
         """run() for attention experts at evaluation time: start = device int64 tensor whose first element is the start token ([SOS]);
-        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count."""
+        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  beam = (width, eos): one more launch
+        for the group on the same features, Hproj and operands (run_beam) -> (path [G,B,S], prob [G,B,S]), else None."""
         G = self.G
         _, B, _, T, Cf = visual.shape
         feat = self.sequence(visual)                                              # [G,B,T,hidden]
@@ -744,6 +745,21 @@ class HeadsGroup(SequenceGroup):
         cols = list(zip(*args))
         ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out,
                                        w_inv=cols[9] if args[0][9] is not None else None)
+        return None if beam is None else self.run_beam(feat, Hproj, start, cols, beam[0], beam[1])
+
+    def run_beam(self, feat, Hproj, start, cols, width, eos):
+        """beam search of all G attention experts in lock-step: ONE mrn_attn_beam_decode_* launch on run_greedy's features, Hproj and
+        greedy_args() columns where every head takes the fused form; else every head's own Attention.beam_search (stepwise)
+        -> (path int64 [G,B,S], prob [G,B,S])"""
+        heads = [e.Prediction for e in self.experts]
+        G, B, T, D = feat.shape
+        L = self.experts[0].opt.batch_max_length
+        if all(h.beam_fused(D, T, L + 1, eos, width) for h in heads):
+            res = ops.attn_beam_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,
+                                               w_inv=cols[9] if cols[9][0] is not None else None)
+            return res[4], res[5]
+        pairs = [h.beam_search(feat[g], start, eos, width, L)[4:] for g, h in enumerate(heads)]
+        return torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
 
     def run(self, visual, text, feats_out, logits_out):
         """visual: Act with the backbone features [G,B,1,T,C'] (HL32 and / or fp32); feats_out [B,T,G,hidden] (router

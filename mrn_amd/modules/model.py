@@ -18,6 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
+from .decoding import ATTN_EOS, attn_beam_request
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import check_call, frames
@@ -122,11 +123,13 @@ class Model(nn.Module):
             raise Exception("Prediction is neither CTC or Attn")
         self.Prediction.to(device)
 
-    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None):
-        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out)
+    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None):
+        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam)
 
-    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None):
-        """SequenceModeling + Prediction on precomputed backbone features"""
+    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None):
+        """SequenceModeling + Prediction on precomputed backbone features.  attn_beam (a width; attention head, evaluation under
+        no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of a beam search on the same features
+        (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's"""
         feat = self.model.sequence(visual, out=feature_out)
         if self.stages["Pred"] == "CTC":
             if needs_grad(self.Prediction, feat):
@@ -135,7 +138,11 @@ class Model(nn.Module):
                 pred = ops.linear(feat, self.Prediction.weight, self.Prediction.bias, out=predict_out)
         else:
             pred = self.Prediction(feat, text, is_train, batch_max_length=self.opt.batch_max_length, out=predict_out)
-        return {"predict": pred, "feature": feat}
+        out = {"predict": pred, "feature": feat}
+        width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
+        if width is not None:
+            out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(feat, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
+        return out
 
     def update_fc(self, hidden_size, nb_classes, device=None):
         fc = nn.Linear(hidden_size, nb_classes)
@@ -294,12 +301,17 @@ class DERNet(Model):
             return ops.linear(feat, head.weight, head.bias)
         return head(feat if feat.is_contiguous() else feat.contiguous(), text, is_train, batch_max_length=self.opt.batch_max_length)
 
-    def forward(self, image, text=None, is_train=True, frozen=None):
-        """frozen: optional handle of frozen_prefetch(image) (same batch)"""
+    def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None):
+        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam: as Model.heads (the main head's beam pair)"""
         feat = self._features(image, frozen)
         logits = self._head(self.Prediction, feat, text, is_train)
         aux = self._head(self.aux_Prediction, feat[:, :, -self.out_dim:], text, is_train)
-        return {"logits": logits, "aux_logits": aux, "features": feat}
+        out = {"logits": logits, "aux_logits": aux, "features": feat}
+        width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
+        if width is not None:
+            rows = feat if feat.is_contiguous() else feat.contiguous()
+            out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(rows, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
+        return out
 
     def update_fc(self, hidden_size, nb_classes, device=None):
         if not tasks_supported(len(self.model) + 1):
@@ -447,22 +459,39 @@ class MRNNet(nn.Module):
         return (not is_train and self.opt.Prediction == "Attn" and ops.greedy_decode_mode() == "fused"
                 and HeadsGroup.greedy_supported(list(self.model)))
 
-    def _run_heads(self, hg, visual, text, is_train, feats, logits):
+    def _run_heads(self, hg, visual, text, is_train, feats, logits, beam=None, first=0):
+        """beam: None or (width, list that takes (first expert, path [G,B,S], prob [G,B,S]) of the group's beam launch)"""
         if self._greedy_heads(is_train):
-            hg.run_greedy(visual, text, feats, logits)
+            pair = hg.run_greedy(visual, text, feats, logits, beam=None if beam is None else (beam[0], ATTN_EOS))
+            if beam is not None:
+                beam[1].append((first,) + pair)
         else:
             hg.run(visual, text, feats, logits)
 
-    def forward(self, image, cross=True, text=None, is_train=True, experts=None):
-        """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier"""
+    def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None):
+        """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier.
+        attn_beam (a width; attention experts, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of
+        a beam search (modules/decoding.py) of the expert the hard routing index picks for each sample, for cross=False of the newest
+        expert; one more launch per heads group on the same features, `logits` is still the greedy decoder's"""
         check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
+        width = attn_beam_request(attn_beam, self.opt.Prediction, is_train)
+        pair = None
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
-            features, index = self.model[-1](image, text, is_train)["predict"], None
+            newest = self.model[-1](image, text, is_train, attn_beam=width)
+            features, index = newest["predict"], None
+            if width is not None:
+                pair = (newest["beam_path"], newest["beam_prob"])
         elif is_train == False:  # noqa: E712
-            features, index = self.cross_forward_expert(image, text, is_train)
+            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width)
+            features, index = routed[:2]
+            if width is not None:
+                pair = routed[2]
         else:
             features, index = self.cross_forward(image, text, is_train, experts=experts)
-        return {"logits": features, "index": index, "aux_logits": None}
+        out = {"logits": features, "index": index, "aux_logits": None}
+        if pair is not None:
+            out["beam_path"], out["beam_prob"] = pair
+        return out
 
     # -- shared by both routed paths -------------------------------------------------------------------
     def experts_prefetch(self, image, text=None, is_train=True):
@@ -523,7 +552,8 @@ class MRNNet(nn.Module):
                 parts.append((lg, done))
             return {"parts": parts, "batch": B, "feats": feats}
 
-    def _experts_and_gate(self, image, text, is_train, experts=None):
+    def _experts_and_gate(self, image, text, is_train, experts=None, beam=None):
+        """beam: None or (width, empty list): the list takes (first expert, path [G,B,S], prob [G,B,S]) per heads group / expert"""
         I = len(self.model)
         B = image.shape[0]
         dev = image.device
@@ -558,13 +588,14 @@ class MRNNet(nn.Module):
                 for (lo, hi, bg, hg), st in zip(halves, streams):
                     st.wait_stream(main)
                     with torch.cuda.stream(st):
-                        self._run_heads(hg, bg.visual_all(image, as_act=True), text, is_train, feats[:, :, lo:hi, :], logits[lo:hi])
+                        self._run_heads(hg, bg.visual_all(image, as_act=True), text, is_train, feats[:, :, lo:hi, :], logits[lo:hi],
+                                        beam=beam, first=lo)
                 for st in streams[:len(halves)]:
                     main.wait_stream(st)
                     image.record_stream(st)
             elif heads is not None:
                 # backbones AND heads in lock-step: one grouped launch per conv layer / Linear / recurrence, one stream
-                self._run_heads(heads, group.visual_all(image, as_act=True), text, is_train, feats, logits)
+                self._run_heads(heads, group.visual_all(image, as_act=True), text, is_train, feats, logits, beam=beam)
             elif self.expert_streams and I > 1:
                 # Phase 1, one stream: the conv backbones (grouped when the experts allow it, else one after the other).
                 # Phase 2, one HIP stream per expert: BiLSTM / attention decoder are latency-bound launches of 16-32
@@ -579,17 +610,23 @@ class MRNNet(nn.Module):
                 for i, expert in enumerate(self.model):
                     streams[i].wait_stream(main)
                     with torch.cuda.stream(streams[i]):
+                        kw = {} if beam is None else {"attn_beam": beam[0]}
                         if visuals is None:
-                            expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i])
+                            res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
                         else:
-                            expert.heads(visuals[i], text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i])
+                            res = expert.heads(visuals[i], text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
                             visuals[i].record_stream(streams[i])
+                        if beam is not None:
+                            beam[1].append((i, res["beam_path"].unsqueeze(0), res["beam_prob"].unsqueeze(0)))
                 for st in streams[:I]:
                     main.wait_stream(st)
                     image.record_stream(st)
             else:
                 for i, expert in enumerate(self.model):
-                    expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i])
+                    res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i],
+                                 **({} if beam is None else {"attn_beam": beam[0]}))
+                    if beam is not None:
+                        beam[1].append((i, res["beam_path"].unsqueeze(0), res["beam_prob"].unsqueeze(0)))
         r = self.dm_router[0].forward_l2(feats)               # [B,P,I,C]
         r = LinearFn.apply(r.view(B * self.patch, I * self.out_dim), self.channel_route.weight, self.channel_route.bias)
         return logits, r.view(B, self.patch, I)
@@ -603,11 +640,26 @@ class MRNNet(nn.Module):
         w = GateTailFn.apply(r, self.route.weight, self.route.bias, float(self.beta))
         return FaninFn.apply(w, *logits), w
 
-    def cross_forward_expert(self, image, text=None, is_train=True):
+    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None):
+        """-> (the routed expert's logits, the hard routing index); with attn_beam (a width) also the routed expert's beam pair
+        (path, prob) [B,S] as a third value"""
         with torch.no_grad():
-            logits, r = self._experts_and_gate(image, text, is_train)
+            beam = None if attn_beam is None else (attn_beam, [])
+            logits, r = self._experts_and_gate(image, text, is_train, beam=beam)
             _, index = ops.gate_tail_fwd(r.contiguous(), self.route.weight.view(-1), self.route.bias, float(self.beta), hard=True)
-            return ops.select_expert(logits, index), index
+            pair = None
+            if beam is not None:
+                main = torch.cuda.current_stream() if image.is_cuda else None
+                parts = sorted(beam[1], key=lambda p: p[0])
+                for _, path, prob in parts:
+                    if main is not None:              # (decoded on a side stream that this stream has waited for)
+                        path.record_stream(main)
+                        prob.record_stream(main)
+                paths, probs = torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])      # [I,B,S]
+                pick, rows = index.view(-1).long(), torch.arange(paths.shape[1], device=paths.device)
+                pair = (paths[pick, rows], probs[pick, rows])
+            routed = ops.select_expert(logits, index)
+            return (routed, index) if beam is None else (routed, index, pair)
 
     def build_fc(self, hidden_size, nb_classes):
         self.update_fc(hidden_size, nb_classes)

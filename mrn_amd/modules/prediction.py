@@ -101,6 +101,80 @@ class Attention(nn.Module):
         return ops.attn_decoder(batch_H, Hproj, eproj, w_h2h, cell.h2h.bias, cell.score.weight,
                                 w_ih_ctx, w_hh, cell.rnn.bias_hh, self.hidden_size, hid=hid, h_state=h, c_state=c, w_inv=w_inv)
 
+    def beam_fused(self, D, T, S, eos, width):
+        """does beam_search take the fused launch (mrn_attn_beam_decode_*): its limits, the LDS budget and MRN_ATTN_BEAM (read per call)"""
+        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and self.num_class >= 2
+                and 0 <= eos < self.num_class and ops.attn_beam_whole_context(D, T, width, self.x3_ok()))
+
+    @torch.no_grad()
+    def beam_search(self, batch_H, sos, eos, width, batch_max_length=25):
+        """beam search of width `width` (modules/decoding.py states the algorithm): batch_H [B,T,D], sos an int or a device int64
+        tensor whose first element is the start token -> (tokens int32 [B,W,S], length int32 [B,W], score [B,W], logp [B,W,S],
+        path int64 [B,S], prob [B,S]), entries in descending score.  One launch where the kernel's limits and the LDS budget allow,
+        otherwise (or under MRN_ATTN_BEAM=stepwise) the step loop of forward() on the B * W-row batch.  Inference only (no_grad)"""
+        check_hidden(None, "Attn", self.hidden_size)
+        W, S, eos = int(width), int(batch_max_length) + 1, int(eos)
+        if W < 1 or not 0 <= eos < self.num_class:
+            raise ValueError(f"beam_search needs width >= 1 and 0 <= eos < {self.num_class}, got {width}, {eos}")
+        cell = self.attention_cell
+        B, T, D = batch_H.shape
+        dev = batch_H.device
+        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=dev)
+        batch_H = batch_H.contiguous()
+        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        if self.beam_fused(D, T, S, eos, W):
+            etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+            return ops.attn_beam_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                        self.hidden_size, S, eos, W, w_inv=w_inv)
+        # stepwise: gather, Linear, one decoder step with carried state and the generator on B * W rows; the selection on the sorted candidates
+        C, H = self.num_class, self.hidden_size
+        w_emb = cell.rnn.weight_ih[:, D:]
+        Hb_rows = batch_H.repeat_interleave(W, dim=0)
+        Hproj_rows = Hproj.repeat_interleave(W, dim=0)
+        h = torch.zeros(B * W, H, device=dev)
+        c = torch.zeros(B * W, H, device=dev)
+        hid = torch.empty(B * W, 1, H, device=dev)
+        targets = start.expand(B * W).contiguous().view(B * W, 1)
+        neg = torch.tensor(float("-inf"), device=dev)
+        score = torch.full((B, W), float("-inf"), device=dev)
+        score[:, 0] = 0.0
+        finished = torch.zeros(B, W, dtype=torch.bool, device=dev)
+        tokens = torch.full((B, W, S), eos, dtype=torch.int32, device=dev)
+        logp = torch.zeros(B, W, S, device=dev)
+        rows = torch.arange(B, device=dev).view(B, 1)
+        for s in range(S):
+            emb = ops.embed_gather(targets, self.char_embeddings.weight, C)
+            eproj = ops.linear(emb, w_emb, cell.rnn.bias_ih)
+            self._decode(Hb_rows, Hproj_rows, eproj, hid=hid, h=h, c=c)
+            x = ops.linear(hid, self.generator.weight, self.generator.bias).view(B, W, C)
+            lp = torch.log_softmax(torch.where(torch.isnan(x), neg, x), dim=2)
+            done = torch.full((B, W, C), float("-inf"), device=dev)
+            done[:, :, eos] = score
+            cand = torch.where(finished.unsqueeze(2), done, score.unsqueeze(2) + lp)
+            cand = torch.where(torch.isnan(cand), neg, cand).view(B, W * C)               # candidate order (i, c)
+            val, idx = torch.sort(cand, dim=1, descending=True, stable=True)
+            val, idx = val[:, :W], idx[:, :W]
+            if val.shape[1] < W:               # (W * C < W cannot happen: C >= 1)
+                raise RuntimeError("beam_search: fewer candidates than entries")
+            par, cls = idx // C, idx % C
+            alive = val > float("-inf")
+            was_done = finished[rows, par]
+            tokens, logp = tokens[rows, par], logp[rows, par]
+            tokens[:, :, s] = torch.where(alive, cls, eos).to(torch.int32)
+            logp[:, :, s] = torch.where(alive & ~was_done, lp[rows, par, cls], 0.0)
+            tokens[~alive] = eos
+            logp[~alive] = 0.0
+            h = h.view(B, W, H)[rows, par].reshape(B * W, H).contiguous()
+            c = c.view(B, W, H)[rows, par].reshape(B * W, H).contiguous()
+            targets = torch.where(alive, cls, eos).reshape(B * W, 1).contiguous()
+            finished = alive & (cls == eos)
+            score = val
+        alive = score > float("-inf")
+        is_eos = tokens == eos
+        length = torch.where(is_eos.any(dim=2), is_eos.to(torch.int32).argmax(dim=2) + 1, S).to(torch.int32)
+        length[~alive] = -1
+        return tokens, length, score, logp, tokens[:, 0].to(torch.int64), torch.exp(logp[:, 0])
+
     def forward(self, batch_H, text, is_train=True, batch_max_length=25, out=None):
         """batch_H [B,T,D]; text [B,S] (teacher forcing) or [B] of [SOS] (greedy) -> logits [B,S,num_class].
         `out` may be a preallocated (possibly strided) [B,S,num_class] buffer."""

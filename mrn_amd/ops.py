@@ -1513,6 +1513,76 @@ def attn_greedy_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_
     return (out, tokens) if want_tokens else out
 
 
+ATTN_BEAM_LDS_EXTRA = 4 * (8 * 16 + 3 * 16 * 16)      # attn_beam_kernel: eight 16-row state arrays + 16 x 16 candidates (score, class, logp)
+
+
+def attn_beam_whole_context(D, T, W, x3=None):
+    """does the fused beam decoder (csrc/rnn.hip beam_lds / beam_grouped) take D context columns, T frames and beam width W: the
+    whole-context tile of attn_greedy_whole_context with ATTN_BEAM_LDS_EXTRA bytes in place of the arg-max pairs within 160 KiB (the 16
+    rows are 16 // W samples x W entries, so the tile does not grow with W), 1 <= W <= 16, D a multiple of 16 (32 in the x3 form).  There
+    is no chunked form: what does not fit is decoded stepwise (Attention.beam_search)"""
+    x3 = DECODER_X3 if x3 is None else x3
+    lds = 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + ATTN_BEAM_LDS_EXTRA
+    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and lds <= 160 * 1024
+
+
+def attn_beam_mode():
+    """MRN_ATTN_BEAM, read per call: "fused" (default: all steps in one launch where the limits allow) or "stepwise" (forced)"""
+    mode = os.environ.get("MRN_ATTN_BEAM", "") or "fused"
+    if mode not in ("fused", "stepwise"):
+        raise ValueError(f"MRN_ATTN_BEAM={mode!r}: expected 'fused' or 'stepwise'")
+    return mode
+
+
+def attn_beam_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width,
+                             w_inv=None):
+    """beam search on the attention head for G experts of one geometry in one launch (per eight experts; include/mrn_attn_beam.h):
+    the operands of attn_greedy_decode_grouped, the end token and the beam width -> (tokens int32 [G,B,W,S], length int32 [G,B,W], score
+    fp32 [G,B,W], logp fp32 [G,B,W,S], path int64 [G,B,S], prob fp32 [G,B,S]), entries in descending score (modules/decoding.py).  The
+    limits are the caller's to keep (attn_beam_whole_context, S <= 512, 2 <= classes, hidden 256): outside them the call is an error"""
+    import ctypes
+    _chk(Hb, Hproj)
+    G, B, T, D = Hb.shape
+    W, S = int(width), int(S)
+    assert Hb.is_contiguous() and Hproj.is_contiguous() and start.dtype == torch.int64 and start.is_cuda
+    classes = [int(b.shape[0]) for b in b_gen]
+    for g in range(G):
+        assert etab[g].shape[0] == classes[g] and etab[g].is_contiguous() and w_gen[g].is_contiguous()
+        assert w_gen[g].shape[0] == (classes[g] + 15) // 16 and b_gen[g].is_contiguous()
+    dev = Hb.device
+    Wd, Sd = max(W, 0), max(S, 0)
+    tokens = torch.empty(G, B, Wd, Sd, device=dev, dtype=torch.int32)
+    length = torch.empty(G, B, Wd, device=dev, dtype=torch.int32)
+    score = torch.empty(G, B, Wd, device=dev, dtype=torch.float32)
+    logp = torch.empty(G, B, Wd, Sd, device=dev, dtype=torch.float32)
+    path = torch.empty(G, B, Sd, device=dev, dtype=torch.int64)
+    prob = torch.empty(G, B, Sd, device=dev, dtype=torch.float32)
+    # per workgroup (16 // W samples) 16 rows of a step's logits and S history records of 16 x (parent, token, logp)
+    tiles = -(-B // (16 // W)) if 1 <= W <= 16 else 0
+    per = tiles * 16 * ((max(classes) + 15) // 16 * 16 + 3 * Sd)
+    scratch = torch.empty(G, max(per, 1), device=dev, dtype=torch.float32)
+
+    def arr(ts):
+        return _ptr_array([t.data_ptr() for t in ts])
+    outs = (arr(scratch), per, arr(tokens), arr(length), arr(score), arr(logp), arr(path), arr(prob))
+    ncls = (ctypes.c_int * G)(*classes)
+    if w_inv is not None:
+        call("mrn_attn_beam_decode_x3_grouped", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
+             arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *outs, G, B, T, D, S, hidden, _stream())
+    else:
+        call("mrn_attn_beam_decode_grouped_f32", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
+             arr(w_ih), arr(w_hh), arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *outs, G, B, T, D, S, hidden, _stream())
+    return tokens, length, score, logp, path, prob
+
+
+def attn_beam_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv=None):
+    """attn_beam_decode_grouped for one expert (G = 1): Hb [B,T,D], Hproj [B,T,H], the operands of attn_greedy_decode -> the six outputs
+    without the expert dimension"""
+    res = attn_beam_decode_grouped(Hb.unsqueeze(0), Hproj.unsqueeze(0), [etab], start, [w_h2h], [b_h2h], [w_score], [w_ih], [w_hh], [b_hh],
+                                   [w_gen], [b_gen], hidden, S, eos, width, w_inv=None if w_inv is None else [w_inv])
+    return tuple(r[0] for r in res)
+
+
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):
     """(h2h.weight [H,H], rnn.weight_ih [4H, D+E], rnn.weight_hh [4H,H]) -> (three pack_fragment_major_h streams, w_inv float[3])"""
     a, b, c = pack_fragment_major_h(w_h2h.detach()), pack_fragment_major_h(w_ih.detach()[:, :D].contiguous()), pack_fragment_major_h(w_hh.detach())

@@ -20,6 +20,13 @@ over the best label as a row of frames whose greedy collapse is that label, and 
 everything behind the decoding line -- scoring on either path, the returned strings -- is the code above, unchanged; the confidence
 is then the label's (pruned) probability instead of the product of the per-frame maxima.  The attention head has no alignments to
 sum over: it ignores the option.
+
+opt.attn_decode = "beam" (absent or "greedy": as above, bit for bit; CTC heads ignore it) decodes an attention head by beam search of
+width opt.beam_width: the evaluation forward is asked for the beam pair (attn_beam=width: one more launch per heads group on the
+same features, modules/decoding.py) and preds_index / preds_max_prob are the best entry's tokens and their probabilities instead of
+the per-step arg-max and its probability.  The loss is still computed on the greedy decoder's logits, and the scorer, the "no [EOS]
+drops the last character" quirk and the returned strings are the code above, unchanged: the confidence is then the probability of
+the kept tokens of the best entry.
 """
 import time
 
@@ -47,8 +54,9 @@ def edit_distance(a, b):
     return prev[-1]
 
 
-def _forward(model, image, opt, converter, val_choose):
-    """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model"""
+def _forward(model, image, opt, converter, val_choose, attn_beam=None):
+    """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
+    attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits"""
     if "CTC" in opt.Prediction:
         if val_choose == "FF":
             out = model(image, cross=False, is_train=False)
@@ -58,13 +66,19 @@ def _forward(model, image, opt, converter, val_choose):
             out = model(image, is_train=False)
     else:
         sos = torch.full((image.size(0),), converter.dict["[SOS]"], dtype=torch.long, device=image.device)
+        kw = {} if attn_beam is None else {"attn_beam": attn_beam}
         if val_choose == "FF":
-            out = model(image, cross=False, text=sos, is_train=False)
+            out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
-            out = model(image, cross=True, text=sos, is_train=False)
+            out = model(image, cross=True, text=sos, is_train=False, **kw)
         else:
-            out = model(image, text=sos, is_train=False)
-    return out["logits"] if "logits" in out else out["predict"]
+            out = model(image, text=sos, is_train=False, **kw)
+    logits = out["logits"] if "logits" in out else out["predict"]
+    if attn_beam is None:
+        return logits
+    if "beam_path" not in out:
+        raise RuntimeError("attn_decode='beam': the evaluation forward returned no beam pair (it runs under torch.no_grad() only)")
+    return logits, (out["beam_path"], out["beam_prob"])
 
 
 def _ned_term(n_gt, n_prd, distance):
@@ -136,6 +150,10 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     attn, ned = "Attn" in opt.Prediction, getattr(opt, "NED", False)
     canon, last = None, None
     ctc_decode, beam_width, beam_top_n = D.decode_options(opt)
+    attn_decode, attn_width = D.attn_decode_options(opt)
+    attn_beam = attn_width if attn and attn_decode == "beam" else None
+    if attn_beam is not None and converter.dict["[EOS]"] != D.ATTN_EOS:
+        raise ValueError(f"attn_decode='beam' ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
         length_of_data += batch_size
@@ -144,7 +162,9 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         if image.is_cuda:
             torch.cuda.synchronize()                 # the launches are asynchronous: infer_time is forward time, not host issue time
         start = time.time()
-        preds = _forward(model, image, opt, converter, val_choose)
+        preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam)
+        if attn_beam is not None:
+            preds, beam_pair = preds
         if image.is_cuda:
             torch.cuda.synchronize()
         infer_time += time.time() - start
@@ -160,6 +180,8 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
             t_score = time.perf_counter()
         if ctc_decode == "beam" and not attn:
             preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
+        elif attn_beam is not None:
+            preds_index, preds_max_prob = beam_pair
         else:
             preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                     # :211, :218-219
         T = preds.size(1)
