@@ -271,3 +271,164 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
     length[~alive] = -1
     out = (tokens, length, score, logp, tokens[:, 0].astype(np.int64), np.exp(logp[:, 0]).astype(np.float32))
     return out + (margin,) if want_margin else out
+
+
+# ---- lexicon-constrained decoding on the CTC heads ---------------------------------------------------------------------------------
+# With opt.lexicon (a sequence of words) a CTC head is decoded to the lexicon word of largest log p(word | image).  The algorithm, which
+# mrn_ctc_lexicon_decode_f32 (mrn_amd/csrc/ctc_lexicon.hip) runs in float32 and ctc_lexicon_host below in float64.  Per sample x[T][C],
+# class 0 the blank, and word w = (c_1 .. c_L), 1 <= c_i <= C - 1, L >= 0:
+#
+#   lse[t] = m + log sum_k exp(x[t][k] - m), m the row maximum;  lp[t][k] = x[t][k] - lse[t];
+#   states z_0 .. z_2L = blank, c_1, blank, ..., c_L, blank;
+#   alpha_0(0) = lp[0][0], alpha_0(1) = lp[0][c_1] if L >= 1, every other alpha_0(s) = -inf;
+#   alpha_t(s) = lp[t][z_s] + logaddexp(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2) if z_s != blank and z_s != z_{s-2}]);
+#   score = logaddexp(alpha_{T-1}(2L), alpha_{T-1}(2L-1)), alpha_{T-1}(0) for L = 0;  logaddexp of all -inf is -inf, never NaN.
+#
+# That is -ctc_loss(log_softmax(x), w, blank=0); a word with L + repeats > T scores -inf.  Per sample the positions (the word index, or
+# the slot of the sample's candidate row) are ranked by descending score, a tie to the lower position.  A position of score -inf is
+# dead (an infeasible word, an unused candidate slot), and so is every position of a sample whose lse is NaN in any frame (a NaN or
+# +inf logit, a frame of -inf).  Dead slots come last, with index -1 and score -inf.  Outputs: index int32 [B][n] (WORD indices:
+# cand[b][slot] with candidate lists), score [B][n], score_all [B][Nc] (Nc = K with candidate lists, else N), and for the best entry the
+# pair that goes wherever argmax_prob_lastdim's goes: path [B][T] = frame_path(word, T), prob [B][T] = [exp(score), 1, 1, ...]; a sample
+# without a live word has an all-blank path and prob[0] = 0.
+LEXICON_MAX_T = 512           # frames mrn_ctc_lexicon_decode_f32 takes (the scorer's SCORE_MAX_T)
+LEXICON_MAX_CLASSES = 65535
+LEXICON_MAX_LENGTH = 31       # state s of a word lives in lane s: 2 L + 1 <= 64, the limit of the 64-state CTC loss kernel
+LEXICON_MAX_WORDS = 1 << 20
+LEXICON_MAX_TOP_N = 16
+DEFAULT_LEXICON_TOP_N = 1
+
+
+def lexicon_options(opt):
+    """(words or None, n) of an options object: opt.lexicon is absent / None (off) or a sequence of str, opt.lexicon_top_n (default 1)
+    the entries returned per sample"""
+    n = _positive_int(opt, "lexicon_top_n", DEFAULT_LEXICON_TOP_N)
+    words = getattr(opt, "lexicon", None)
+    if words is None:
+        return None, n
+    if isinstance(words, (str, bytes)) or not hasattr(words, "__iter__"):
+        raise ValueError(f"lexicon must be a sequence of words (str), got {type(words).__name__}")
+    words = list(words)
+    for w in words:
+        if not isinstance(w, str):
+            raise ValueError(f"lexicon must be a sequence of words (str), got an entry {w!r}")
+    return words, n
+
+
+def lexicon_supported(prediction, T, C, Lmax, N, n):
+    """does mrn_ctc_lexicon_decode_f32 score N words of at most Lmax classes against T frames of C classes of a `prediction` head and
+    return n entries per sample"""
+    return ("CTC" in prediction and 1 <= T <= LEXICON_MAX_T and 2 <= C <= LEXICON_MAX_CLASSES and 0 <= Lmax <= LEXICON_MAX_LENGTH
+            and 1 <= N <= LEXICON_MAX_WORDS and 1 <= n <= LEXICON_MAX_TOP_N)
+
+
+def encode_lexicon(converter, words):
+    """words -> (tokens int32 [N][Lmax] (0 behind a word), lengths int32 [N], kept_words): the words a CTC converter can spell, in
+    their order, duplicates kept.  A word with a character outside converter.dict, or one of the [UNK] / [CTCblank] class, is dropped;
+    ValueError if nothing is left"""
+    table = converter.dict
+    banned = {0, table.get("[UNK]")}
+    rows, kept = [], []
+    for w in words:
+        row = [table.get(ch) for ch in w]
+        if any(c is None or c in banned for c in row):
+            continue
+        rows.append(row)
+        kept.append(w)
+    if not kept:
+        raise ValueError(f"lexicon: none of the {len(list(words))} words can be spelled with the converter's characters")
+    lengths = np.fromiter((len(r) for r in rows), dtype=np.int32, count=len(rows))
+    tokens = np.zeros((len(rows), max(int(lengths.max()), 1)), dtype=np.int32)
+    for i, r in enumerate(rows):
+        tokens[i, :len(r)] = r
+    return tokens, lengths, kept
+
+
+def _lexicon_scores(lp, tokens, lengths):
+    """log p(word | frames) of M words against lp [T][C] (float64 log-probabilities) -> float64 [M], vectorised over the words"""
+    T = lp.shape[0]
+    M, Lm = tokens.shape
+    S = 2 * Lm + 1
+    z = np.zeros((M, S), dtype=np.int64)
+    z[:, 1::2] = tokens
+    valid = np.arange(S)[None, :] < (2 * lengths + 1)[:, None]
+    z[~valid] = 0
+    skip = np.zeros((M, S), dtype=bool)
+    skip[:, 3::2] = tokens[:, 1:] != tokens[:, :-1]
+    skip &= valid
+    neg = np.full((M, 2), -np.inf)
+    alpha = np.full((M, S), -np.inf)
+    alpha[:, 0] = lp[0, 0]
+    if Lm:
+        alpha[:, 1] = np.where(lengths >= 1, lp[0, z[:, 1]], -np.inf)
+    for t in range(1, T):
+        a1 = np.concatenate([neg[:, :1], alpha[:, :-1]], axis=1)
+        a2 = np.where(skip, np.concatenate([neg, alpha[:, :-2]], axis=1)[:, :S], -np.inf)
+        m = np.maximum(np.maximum(alpha, a1), a2)
+        m0 = np.where(m > -np.inf, m, 0.0)
+        with np.errstate(divide="ignore"):
+            acc = m0 + np.log(np.exp(alpha - m0) + np.exp(a1 - m0) + np.exp(a2 - m0))      # all -inf: 0 + log(0) = -inf
+        alpha = np.where(valid, acc + lp[t][z], -np.inf)
+    rows = np.arange(M)
+    e1 = alpha[rows, 2 * lengths]
+    e2 = np.where(lengths >= 1, alpha[rows, np.maximum(2 * lengths - 1, 0)], -np.inf)
+    m = np.maximum(e1, e2)
+    m0 = np.where(m > -np.inf, m, 0.0)
+    with np.errstate(divide="ignore"):
+        return m0 + np.log(np.exp(e1 - m0) + np.exp(e2 - m0))
+
+
+def ctc_lexicon_host(logits, lex_tokens, lex_len, n, cand=None):
+    """float64 lexicon decoding of logits [B][T][C] (numpy) against the words lex_tokens int [N][Lmax] / lex_len int [N], or per sample
+    against the words cand int [B][K] names (-1 = unused slot) -> (index int32 [B][n], score float64 [B][n], score_all float64
+    [B][Nc], path int64 [B][T], prob float32 [B][T]): the outputs of ops.ctc_lexicon_decode, for CPU tensors and for batches outside
+    the kernel's limits.  Any word length, any N >= 1 and n >= 1"""
+    logits = np.asarray(logits)
+    tokens = np.asarray(lex_tokens).astype(np.int64)
+    lengths = np.asarray(lex_len).astype(np.int64)
+    if logits.ndim != 3 or logits.shape[1] < 1 or logits.shape[2] < 2 or n < 1:
+        raise ValueError(f"ctc_lexicon_host needs logits [B][T >= 1][C >= 2] and n >= 1, got {logits.shape}, {n}")
+    B, T, C = logits.shape
+    if tokens.ndim != 2 or lengths.shape != tokens.shape[:1] or len(lengths) < 1:
+        raise ValueError(f"ctc_lexicon_host needs tokens [N >= 1][Lmax] and lengths [N], got {tokens.shape}, {lengths.shape}")
+    N, Lmax = tokens.shape
+    if lengths.min() < 0 or lengths.max() > Lmax:
+        raise ValueError(f"ctc_lexicon_host: word lengths outside 0..{Lmax}")
+    tokens = np.where(np.arange(Lmax)[None, :] < lengths[:, None], tokens, 0)
+    used = tokens[np.arange(Lmax)[None, :] < lengths[:, None]]
+    if used.size and (used.min() < 1 or used.max() > C - 1):
+        raise ValueError(f"ctc_lexicon_host: word tokens outside 1..{C - 1}")
+    if cand is not None:
+        cand = np.asarray(cand).astype(np.int64)
+        if cand.ndim != 2 or cand.shape[0] != B or cand.shape[1] < 1 or (cand.size and (cand.min() < -1 or cand.max() > N - 1)):
+            raise ValueError(f"ctc_lexicon_host needs cand [B][K >= 1] with entries in -1..{N - 1}, got {cand.shape}")
+    Nc = N if cand is None else cand.shape[1]
+    index = np.full((B, n), -1, dtype=np.int32)
+    score = np.full((B, n), -np.inf, dtype=np.float64)
+    score_all = np.full((B, Nc), -np.inf, dtype=np.float64)
+    path = np.zeros((B, T), dtype=np.int64)
+    prob = np.ones((B, T), dtype=np.float32)
+    x64 = logits.astype(np.float64)
+    for b in range(B):
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            peak = x64[b].max(axis=1, keepdims=True)
+            lse = peak + np.log(np.exp(x64[b] - peak).sum(axis=1, keepdims=True))
+        words = np.arange(N) if cand is None else cand[b]
+        if not np.isnan(lse).any():
+            used = np.flatnonzero(words >= 0)
+            if used.size:
+                with np.errstate(invalid="ignore"):
+                    lp = x64[b] - lse
+                s = _lexicon_scores(lp, tokens[words[used]], lengths[words[used]])
+                score_all[b, used] = np.where(np.isnan(s), -np.inf, s)
+        order = [q for q in np.argsort(-score_all[b], kind="stable")[:n] if score_all[b, q] > -np.inf]
+        for r, q in enumerate(order):
+            index[b, r] = words[q]
+            score[b, r] = score_all[b, q]
+        if order:
+            w = int(words[order[0]])
+            path[b] = frame_path([int(c) for c in tokens[w, :lengths[w]]], T)
+            prob[b, 0] = np.float32(np.exp(score[b, 0]))
+        else:
+            prob[b, 0] = 0.0
+    return index, score, score_all, path, prob

@@ -1707,6 +1707,60 @@ def ctc_beam_decode(logits, beam_width, top_n):
     return tokens, length, score, path, prob
 
 
+LEXICON_SCORE_BYTES = 256 << 20      # the [B][Nc] score table of one mrn_ctc_lexicon_decode_f32 call stays within this
+
+
+def ctc_lexicon_decode(logits, lex_tokens, lex_len, n=1, cand=None):
+    """lexicon-constrained decoding of one batch of CTC-head logits [B,T,C], class 0 the blank (include/mrn_lexicon.h:
+    mrn_ctc_lexicon_decode_f32): every sample against the words lex_tokens int32 [N,Lmax] / lex_len int32 [N], or against the words
+    its row of cand int32 [B,K] names (-1 = unused slot)
+    -> (index int32 [B,n] word indices in descending score, -1 = dead slot; score fp32 [B,n]; score_all fp32 [B,Nc] = log p(word |
+    sample) of every position, Nc = K with cand else N; path int64 [B,T], prob fp32 [B,T]: the best word as the (index, probability)
+    rows greedy_score takes).
+    The batch is cut into chunks of samples whose score table stays within LEXICON_SCORE_BYTES (samples are independent: nothing is
+    merged); a batch that needs more than one chunk returns score_all = None.  Batch and step strides are honoured; the last
+    dimension is contiguous.  Outside the kernel's limits (modules/decoding.py lexicon_supported: a word table wider than 31 classes,
+    more than 16 entries, ...) the same outputs come from the float64 host form, ctc_lexicon_host, as validation() takes it; operands
+    that are no CUDA tensors, a candidate table without slots and out-of-range words or candidates stay errors"""
+    import numpy as np
+    from .modules import decoding as D
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
+        raise RuntimeError("ctc_lexicon_decode needs a CUDA (HIP) fp32 tensor [B,T,C] with a contiguous last dimension; there is no "
+                           "CPU fallback")
+    operands = [(lex_tokens, 2), (lex_len, 1)] + ([(cand, 2)] if cand is not None else [])
+    for t, nd in operands:
+        if not t.is_cuda or t.dtype != torch.int32 or t.dim() != nd or not t.is_contiguous():
+            raise RuntimeError("ctc_lexicon_decode needs contiguous CUDA (HIP) int32 tensors: tokens [N,Lmax], lengths [N], cand [B,K]")
+    B, T, C = logits.shape
+    N, Lmax = lex_tokens.shape
+    if lex_len.shape[0] != N or (cand is not None and cand.shape[0] != B):
+        raise RuntimeError(f"ctc_lexicon_decode: {N} words, {lex_len.shape[0]} lengths"
+                           + ("" if cand is None else f", {cand.shape[0]} candidate rows for {B} samples"))
+    n, K = int(n), 0 if cand is None else cand.shape[1]
+    if cand is not None and K < 1:
+        raise RuntimeError("ctc_lexicon_decode: a candidate table needs K >= 1 slots per sample")
+    Nc = N if cand is None else K
+    dev = logits.device
+    if not D.lexicon_supported("CTC", T, C, Lmax, N, n):
+        host = D.ctc_lexicon_host(logits.cpu().numpy(), lex_tokens.cpu().numpy(), lex_len.cpu().numpy(), n,
+                                  None if cand is None else cand.cpu().numpy())
+        return tuple(torch.from_numpy(o.astype(np.float32) if o.dtype == np.float64 else o).to(dev) for o in host)
+    index = torch.empty(B, max(n, 0), device=dev, dtype=torch.int32)
+    score = torch.empty(B, max(n, 0), device=dev, dtype=torch.float32)
+    path = torch.empty(B, T, device=dev, dtype=torch.int64)
+    prob = torch.empty(B, T, device=dev, dtype=torch.float32)
+    step = max(1, LEXICON_SCORE_BYTES // (4 * max(Nc, 1)))
+    whole = B <= step
+    score_all = torch.empty(min(B, step), Nc, device=dev, dtype=torch.float32)
+    for b0 in range(0, max(B, 1), step):
+        b1 = min(B, b0 + step)
+        x = logits[b0:b1]
+        call("mrn_ctc_lexicon_decode_f32", _p(x), x.stride(0), x.stride(1), b1 - b0, T, C, _p(lex_tokens), Lmax, _p(lex_len), N,
+             None if cand is None else _p(cand[b0:b1]), K, n, _p(index[b0:b1]), _p(score[b0:b1]), _p(score_all), _p(path[b0:b1]),
+             _p(prob[b0:b1]), _stream())
+    return index, score, score_all if whole else None, path, prob
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     """LayerNorm over the last dim of (strided) rows -> (y, mean, rstd)"""
     x2 = rows2d(x)

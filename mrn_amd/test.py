@@ -27,6 +27,14 @@ same features, modules/decoding.py) and preds_index / preds_max_prob are the bes
 the per-step arg-max and its probability.  The loss is still computed on the greedy decoder's logits, and the scorer, the "no [EOS]
 drops the last character" quirk and the returned strings are the code above, unchanged: the confidence is then the probability of
 the kept tokens of the best entry.
+
+opt.lexicon = a sequence of words (absent or None: as above, bit for bit; the attention head ignores it) decodes a CTC head to the
+lexicon word of largest log p(word | image), the exact CTC forward score of every (sample, word) pair (modules/decoding.py): the words
+the converter can spell are encoded and uploaded once per call, then one mrn_ctc_lexicon_decode_f32 call per batch, or the float64
+host form for predictions that are not on the GPU and for lexicons or batches outside the kernel's limits (a word of more than 31
+characters).  The hand-over is the beam decoder's: the best word as a row of frames whose greedy collapse is that word, its probability
+as that row's first factor, and the scorer behind it unchanged.  opt.lexicon_top_n (default 1) is the number of entries the decoder
+ranks per sample; validation() scores the best one.  A lexicon together with ctc_decode = "beam" is an error: both replace best path.
 """
 import time
 
@@ -141,6 +149,26 @@ def _beam_pair(preds, prediction, width, top_n):
     return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
 
 
+class _Lexicon:
+    """opt.lexicon encoded once per validation() call; the device copies are made when the first CUDA batch needs them"""
+
+    def __init__(self, converter, words, n):
+        self.tokens, self.lengths, self.words = D.encode_lexicon(converter, words)
+        self.n = n
+        self.device = None
+
+    def pair(self, preds, prediction):
+        """the lexicon decoder's (path, prob) for CTC logits [B,T,C], on the device of `preds`: the kernel when it takes the batch,
+        else the host form"""
+        N = len(self.lengths)
+        if preds.is_cuda and D.lexicon_supported(prediction, preds.size(1), preds.size(2), int(self.lengths.max()), N, self.n):
+            if self.device is None:
+                self.device = (torch.from_numpy(self.tokens).to(preds.device), torch.from_numpy(self.lengths).to(preds.device))
+            return ops.ctc_lexicon_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), *self.device, n=self.n)[3:]
+        path, prob = D.ctc_lexicon_host(preds.detach().cpu().numpy(), self.tokens, self.lengths, self.n)[3:]
+        return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
+
+
 def validation(model, criterion, evaluation_loader, converter, opt, val_choose="val", tqdm_position=1):
     n_correct, norm_ED, length_of_data, infer_time = 0, 0.0, 0, 0.0
     loss_sum, loss_n = 0.0, 0
@@ -152,6 +180,10 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     ctc_decode, beam_width, beam_top_n = D.decode_options(opt)
     attn_decode, attn_width = D.attn_decode_options(opt)
     attn_beam = attn_width if attn and attn_decode == "beam" else None
+    lexicon_words, lexicon_n = D.lexicon_options(opt)
+    if lexicon_words is not None and not attn and ctc_decode == "beam":
+        raise ValueError("lexicon and ctc_decode='beam' both replace best-path decoding on a CTC head: set one of them")
+    lexicon = _Lexicon(converter, lexicon_words, lexicon_n) if lexicon_words is not None and not attn else None
     if attn_beam is not None and converter.dict["[EOS]"] != D.ATTN_EOS:
         raise ValueError(f"attn_decode='beam' ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
@@ -178,7 +210,9 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         loss_n += 1
         if SCORE_TIMER is not None:
             t_score = time.perf_counter()
-        if ctc_decode == "beam" and not attn:
+        if lexicon is not None:
+            preds_index, preds_max_prob = lexicon.pair(preds, opt.Prediction)
+        elif ctc_decode == "beam" and not attn:
             preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
         elif attn_beam is not None:
             preds_index, preds_max_prob = beam_pair
