@@ -394,6 +394,21 @@ struct LstmX3Group {
   int tiles, B, T, ndir, nsets, pinned;
 };
 
+// (group, tile) of workgroup blockIdx.x among groups x tiles pairs (the sets of the LSTM layers, the experts of the attention decoders).
+// pinned == 0: group-major; 1: all tiles of a group on XCD (group % 8) (workgroup b runs on XCD b % 8; groups past the last come out
+// >= `groups`: the workgroup returns); 2: the pairs in group-major order cut into eight equal runs, one per XCD
+__device__ __forceinline__ void group_tile(int groups, int tiles, int pinned, int& group, int& tile) {
+  if (pinned == 2) {
+    const int per = groups * tiles / 8;
+    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+    group = pair / tiles;
+    tile = pair - group * tiles;
+  } else {
+    group = pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / tiles) : (int)blockIdx.x / tiles;
+    tile = pinned ? (int)((blockIdx.x / 8) % tiles) : (int)blockIdx.x % tiles;
+  }
+}
+
 // RB: 16-sample row blocks per workgroup.  A workgroup streams the whole W_hh of its (expert, direction) set through one CU every step
 // (1 MiB; 64 B / clk / CU from L2 = 7.8 us), with little MFMA work behind each fragment (96 MFMAs of 16 cycles per wave).  RB = 2 -- the same
 // stream for twice the samples, half as many workgroups per L2 -- was built and measured SLOWER (round 6, tools/bench_lstm.py, B = 256,
@@ -416,15 +431,7 @@ __global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_x3_kernel(const 
   // L2 serves the same number of workgroups and at most two or three sets' weights.  The step time follows the number of workgroups
   // streaming through one L2 (13.1 us at 4, 17.4 at 16, 21.9 at 32): 12 sets = 24 per XCD instead of 32 / 16, 6 sets = 12 instead of 16 / 0.
   int set, tile;
-  if (grp.pinned == 2) {
-    const int per = grp.nsets * grp.tiles / 8;
-    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    set = pair / grp.tiles;
-    tile = pair - set * grp.tiles;
-  } else {
-    set = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
-    tile = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
-  }
+  group_tile(grp.nsets, grp.tiles, grp.pinned, set, tile);
   if (set >= grp.nsets) return;
   const int gi = set / grp.ndir;
   const float* __restrict__ xproj = grp.g[gi].xproj;
@@ -674,310 +681,306 @@ struct AttnDecGroup {
 // context live in LDS as fp16 hi / lo planes, the weights come as fragment-major hi / lo streams with a power-of-two prescale
 // (ops.pack_fragment_major_h).  On the exact-fp32 pipe those products are 30 us of a step (576 MFMAs of 32 cycles per wave, four
 // waves per SIMD); as x3 216 MFMAs of 16 cycles.
-// (4) of the WIDE form, one chunk: ctx[row][k0 + c] = sum_t alpha[row][t] * Hb[b][t][k0 + c] for the kn columns from k0, into column c
-// of the LDS tile (fp32 rows of stride cld, or the fp16 hi / lo planes of stride cldh) and ctx_out; the same sums as (4) in the kernel
-template <bool X3>
-__device__ __forceinline__ void context_chunk(const AttnDecParams& p, const float* __restrict__ e_lds, float* ctx_lds, _Float16* c_hi,
-                                              _Float16* c_lo, int cld, int cldh, int b0, int Bend, int vb, int step, int k0, int kn,
-                                              int t_) {
-  const int T = p.T, D = p.D, n4 = kn / 4;
-  for (int it = t_; it < vb * n4; it += NTH) {
-    const int row = it / n4, c4 = it - row * n4;
-    const int b = b0 + row;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (b < Bend) {
-      const float* hb = p.Hb + (long)b * T * D + k0 + c4 * 4;
-      int t = 0;
-#pragma unroll 1
-      for (; t + 4 <= T; t += 4) {
-        f32x4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float w = e_lds[row * T + t + u];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
-        }
-      }
-      for (; t < T; ++t) {
-        const float w = e_lds[row * T + t];
-        const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
-      }
-    }
-    if constexpr (X3) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * cldh + c4 * 4 + k, a[k]);
-    } else {
-      *reinterpret_cast<f32x4*>(ctx_lds + row * cld + c4 * 4) = a;
-    }
-    if (p.ctx_out && b < Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + k0 + c4 * 4) = a;
-  }
-}
-
 // WIDE: the context tile holds CTX_CHUNK columns instead of D.  Phases (4) and the context half of (5) then run chunk by chunk: form
 // one chunk of every row's context, multiply it into the gate accumulators, next chunk (attn_launch takes this form when the whole
 // tile would not fit the LDS budget: D = 256 * G for G >= 8 at T = 65, DERNet's main head).
 constexpr int CTX_CHUNK = 1024;
 
+// ---- the attention cell's step, shared by attn_decoder_kernel, attn_greedy_kernel and attn_beam_kernel -------------------------------
+// A workgroup owns the 16 rows of an MFMA tile; `nrows` of them are in use, row r belongs to sample b0 + r / per (per = 1: a row per
+// sample; the beam kernel's W entries of a sample share its Hproj / Hb slices), the others are treated like rows beyond the batch.  One
+// step, the same arithmetic in the same order for every caller -- which is what makes a beam row's logits bit-identical to the greedy
+// kernel's, and beam width 1 greedy:
+//   (1) hp = h2h(h) + bias                                                                  } attn_scores
+//   (2) e[row][t] = score . tanh(Hproj[b][t] + hp[row])                                     }
+//   (3) alpha = softmax over t, one wave per row                                            }
+//       the caller loads the embedding half of the LSTMCell input for the step (eproj, or the token's row of etab): issued here, it
+//       lands during phase (4) and becomes the INITIAL value of the gate accumulators (x the W_ih stream's power-of-two prescale:
+//       exact) -- sixteen registers live over one phase, not the step
+//   (4) context[row][:] = sum_t alpha[row][t] * Hb[b][t][:]   (context_chunk; WIDE: chunk by chunk in (5))       } attn_cell
+//   (5) gates = that seed + ctx . W_ih[:, :D]^T + h . W_hh^T                                                    }
+//   (6) LSTM cell; the new h replaces the old one in LDS, (h, gates, c) go back to the caller for its own stores  }
+// The LDS map, in floats: h [BT][HLD] (x3: two fp16 planes [BT][LDH]), hp [BT][HLD], ctx [BT][CLD] (x3: two fp16 planes [BT][CLDH]),
+// e [BT][T], the score vector [HID]; a kernel's own arrays follow at sw_lds + HID.
+template <bool X3>
+struct AttnTile {
+  float *h_lds, *hp_lds, *ctx_lds, *e_lds, *sw_lds;
+  _Float16 *h_hi, *h_lo, *c_hi, *c_lo;
+  int CLD, CLDH;                             // context row: fp32, fp16 planes
+  __amdgpu_buffer_rsrc_t r_h2h, r_ih, r_hh;  // x3: the three fp16 weight streams (4 bytes per weight) behind buffer resources
+  float inv_h2h, inv_ih, inv_hh;
+  int b0, Bend, nrows, per;
+  int t_, lane, wave, col, rbase, j;         // lane (col, rbase ... rbase + 3) of the MFMA tile; j: this lane's hidden unit
+  float bj, bh[4];                           // its h2h and gate biases
+  __device__ __forceinline__ int sample(int row) const { return b0 + row / per; }
+};
+
+// the view of workgroup `tile` (ns samples of `per` rows each, dc context columns in LDS); fills the tile: h from the carried state
+// where one is given, else zero, everything else zero (rows not in use stay zero), the score vector.  The caller's barrier follows
+template <bool X3>
+__device__ __forceinline__ AttnTile<X3> attn_tile(float* lds, const AttnDecParams& p, int dc, int tile, int ns, int per) {
+  AttnTile<X3> v;
+  const int T = p.T;
+  v.CLD = dc + 4;
+  v.CLDH = dc + 8;
+  v.h_lds = lds;
+  v.hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : v.h_lds + BT * HLD;
+  v.ctx_lds = v.hp_lds + BT * HLD;
+  v.e_lds = X3 ? v.ctx_lds + (2 * BT * v.CLDH) / 2 : v.ctx_lds + BT * v.CLD;
+  v.sw_lds = v.e_lds + BT * T;
+  v.h_hi = reinterpret_cast<_Float16*>(v.h_lds);
+  v.h_lo = v.h_hi + BT * LDH;
+  v.c_hi = reinterpret_cast<_Float16*>(v.ctx_lds);
+  v.c_lo = v.c_hi + BT * v.CLDH;
+  v.inv_h2h = X3 ? p.w_inv[0] : 1.f, v.inv_ih = X3 ? p.w_inv[1] : 1.f, v.inv_hh = X3 ? p.w_inv[2] : 1.f;
+  v.r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
+  v.r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * p.D * 4 : 0, 0x00020000);
+  v.r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
+  v.b0 = tile * ns;
+  v.Bend = min(p.B, v.b0 + ns);
+  v.nrows = ns * per;
+  v.per = per;
+  v.t_ = threadIdx.x, v.lane = v.t_ & 63, v.wave = v.t_ >> 6;
+  v.col = v.lane & 15, v.rbase = (v.lane >> 4) * 4;
+  v.j = v.wave * 16 + v.col;
+
+  const int ld = X3 ? LDH : HLD;
+  for (int i = v.t_; i < BT * ld; i += NTH) {
+    const int row = i / ld, jj = i - row * ld;
+    const int b = v.sample(row);
+    const float h0 = (p.h_state && b < v.Bend && jj < HID) ? p.h_state[(long)b * HID + jj] : 0.f;
+    if constexpr (X3) store_h_split(v.h_hi, v.h_lo, i, h0);
+    else v.h_lds[i] = h0;
+  }
+  for (int i = v.t_; i < BT * HLD + BT * (X3 ? v.CLDH : v.CLD) + BT * T; i += NTH) v.hp_lds[i] = 0.f;   // hp, ctx (planes), e
+  for (int i = v.t_; i < HID; i += NTH) v.sw_lds[i] = p.w_score[i];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) v.bh[g] = p.b_hh ? p.b_hh[g * HID + v.j] : 0.f;
+  v.bj = p.b_h2h[v.j];
+  return v;
+}
+
+// (1)-(3); ends behind the barrier that publishes alpha.  SAVES (here, in context_chunk and in attn_cell): the teacher-forced kernel's
+// optional training saves hp_out, alpha_out and ctx_out.  The decoding kernels, whose parameters leave them null, compile them out: the
+// row addresses of the saves stay live over the step, registers that attn_greedy_kernel and attn_beam_kernel do not have to spare
+template <bool X3, bool SAVES>
+__device__ __forceinline__ void attn_scores(const AttnTile<X3>& v, const AttnDecParams& p, int step) {
+  const int T = p.T, lane = v.lane, wave = v.wave;
+  // (1) hp = h2h(h) + bias
+  {
+    f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+    if constexpr (X3) mma_rows_hb<1>(acc, v.h_hi, v.h_lo, v.r_h2h, HID, wave, lane);
+    else mma_rows<1>(acc, v.h_lds, HLD, p.w_h2h, HID, wave, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float hp = acc[0][r] * v.inv_h2h + v.bj;
+      v.hp_lds[(v.rbase + r) * HLD + v.j] = hp;
+      const int b = v.sample(v.rbase + r);
+      if (SAVES && p.hp_out && b < v.Bend) p.hp_out[((long)b * p.S + step) * HID + v.j] = hp;
+    }
+  }
+  __syncthreads();
+  // (2) e[row][t] = score . tanh(Hproj[b][t] + hp[row]); one wave per (row, t) pair, 4 channels per lane, four pairs in
+  //     flight per wave so the Hproj loads (L2) and the cross-lane reductions of different pairs overlap
+  {
+    const f32x4 wv = *reinterpret_cast<const f32x4*>(v.sw_lds + lane * 4);
+    const int npair = v.nrows * T;
+    constexpr int U = 4;                 // pairs in flight per wave (8 measured the same, round 6)
+    for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
+      f32x4 hv[U];
+      int rows[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int pr = pr0 + u;
+        const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
+        rows[u] = row;
+        const int b = v.sample(row);
+        hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (pr < npair && b < v.Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
+      }
+      float sacc[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(v.hp_lds + rows[u] * HLD + lane * 4);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
+        sacc[u] = s;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
+      }
+      if (lane < U && pr0 + lane < npair) {
+        float s = sacc[0];
+#pragma unroll
+        for (int u = 1; u < U; ++u) s = lane == u ? sacc[u] : s;
+        v.e_lds[pr0 + lane] = (v.sample((pr0 + lane) / T) < v.Bend) ? s : 0.f;
+      }
+    }
+  }
+  __syncthreads();
+  // (3) softmax over t, one wave per row
+  if (wave < v.nrows) {
+    float* e = v.e_lds + wave * T;
+    float m = -INFINITY;
+    for (int t = lane; t < T; t += 64) m = fmaxf(m, e[t]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int t = lane; t < T; t += 64) {
+      const float x = expf(e[t] - m);
+      e[t] = x;
+      sum += x;
+    }
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+    const int b = v.sample(wave);
+    for (int t = lane; t < T; t += 64) {
+      const float a = e[t] * inv;
+      e[t] = a;
+      if (SAVES && p.alpha_out && b < v.Bend) p.alpha_out[((long)b * p.S + step) * T + t] = a;
+    }
+  }
+  __syncthreads();
+}
+
+// (4), the kn columns from k0: ctx[row][k0 + c] = sum_t alpha[row][t] * Hb[b][t][k0 + c] into column c of the LDS tile (fp32 rows, or
+// the fp16 hi / lo planes) and ctx_out.  The sums do not depend on the cut, so the chunked context equals the whole one bit for bit
+template <bool X3, bool SAVES>
+__device__ __forceinline__ void context_chunk(const AttnTile<X3>& v, const AttnDecParams& p, int step, int k0, int kn) {
+  const int T = p.T, D = p.D, n4 = kn / 4;
+  for (int it = v.t_; it < v.nrows * n4; it += NTH) {
+    const int row = it / n4, c4 = it - row * n4;
+    const int b = v.sample(row);
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (b < v.Bend) {
+      const float* hb = p.Hb + (long)b * T * D + k0 + c4 * 4;
+      int t = 0;
+#pragma unroll 1
+      for (; t + 4 <= T; t += 4) {                 // four independent loads in flight per lane, 16 waves per CU (eight: no faster)
+        f32x4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float w = v.e_lds[row * T + t + u];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, x[u][k], a[k]);
+        }
+      }
+      for (; t < T; ++t) {
+        const float w = v.e_lds[row * T + t];
+        const f32x4 x = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = fmaf(w, x[k], a[k]);
+      }
+    }
+    if constexpr (X3) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) store_h_split(v.c_hi, v.c_lo, row * v.CLDH + c4 * 4 + k, a[k]);
+    } else {
+      *reinterpret_cast<f32x4*>(v.ctx_lds + row * v.CLD + c4 * 4) = a;
+    }
+    if (SAVES && p.ctx_out && b < v.Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + k0 + c4 * 4) = a;
+  }
+}
+
+// (4)-(6): acc5 is the caller's gate seed, c the lane's cell state (updated); h and the post-activation gates come back, h is in LDS for
+// the next step.  The caller's stores and the barrier that publishes h follow
+template <bool X3, bool WIDE, bool SAVES>
+__device__ __forceinline__ void attn_cell(const AttnTile<X3>& v, const AttnDecParams& p, int step, const f32x4 (&acc5)[4], float (&c)[4],
+                                          float (&h)[4], float (&act)[4][4]) {
+  const int D = p.D, lane = v.lane, wave = v.wave;
+  if constexpr (!WIDE) {
+    context_chunk<X3, SAVES>(v, p, step, 0, D);
+    __syncthreads();
+  }
+  f32x4 acc[4];
+  const float pre_ih = 1.f / v.inv_ih;               // (a power of two)
+#pragma unroll
+  for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
+  if constexpr (WIDE) {
+    for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
+      const int kn = min(CTX_CHUNK, D - k0);
+      context_chunk<X3, SAVES>(v, p, step, k0, kn);
+      __syncthreads();
+      if constexpr (X3) mma_rows_hb_k<4>(acc, v.c_hi, v.c_lo, v.r_ih, D, k0, kn, wave, lane, v.CLDH);
+      else mma_rows_k<4>(acc, v.ctx_lds, v.CLD, p.w_ih, D, k0, kn, wave, lane);
+      if (k0 + CTX_CHUNK < D) __syncthreads();   // every wave is done with this chunk before the next one lands
+    }
+  } else {
+    if constexpr (X3) mma_rows_hb<4>(acc, v.c_hi, v.c_lo, v.r_ih, D, wave, lane, v.CLDH);
+    else mma_rows<4>(acc, v.ctx_lds, v.CLD, p.w_ih, D, wave, lane);
+  }
+  if constexpr (X3) {
+    const float ratio = v.inv_ih / v.inv_hh;            // (powers of two: exact)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] *= ratio;
+    mma_rows_hb<4>(acc, v.h_hi, v.h_lo, v.r_hh, HID, wave, lane);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] *= v.inv_hh;
+  } else {
+    mma_rows<4>(acc, v.h_lds, HLD, p.w_hh, HID, wave, lane);
+  }
+  __syncthreads();  // every wave has finished reading h_lds
+  lstm_pointwise0(acc, v.bh, c, h, act);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = v.rbase + r;
+    const float hn = v.sample(row) < v.Bend ? h[r] : 0.f;
+    if constexpr (X3) store_h_split(v.h_hi, v.h_lo, row * LDH + v.j, hn);
+    else v.h_lds[row * HLD + v.j] = hn;
+  }
+}
+
+// Teacher forced: the gate seed of a step is eproj[b][step]; stores hid, the optional training saves and the carried state.
 template <bool X3, bool WIDE>
 __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup grp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // pinned == 1: one expert's recurrent weights (2.3 MiB) stay in one XCD's L2, all tiles of a group run on XCD (group % 8); pinned == 2
   // (six experts: 24 workgroups on every XCD instead of 32 on six of them; two experts' weights per L2 at most)
   int gi, tile_;
-  if (grp.pinned == 2) {          // equal group-major runs of (group, tile) pairs per XCD: see lstm_layer_x3_kernel
-    const int per = grp.groups * grp.tiles / 8;
-    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    gi = pair / grp.tiles;
-    tile_ = pair - gi * grp.tiles;
-  } else {
-    gi = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
-    tile_ = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
-  }
+  group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
   if (gi >= grp.groups) return;
-  const AttnDecParams p = grp.g[gi];
-  const int D = p.D, T = p.T;
-  const int DC = WIDE ? CTX_CHUNK : D;     // context columns the LDS tile holds
-  const int CLD = DC + 4;
-  const int CLDH = DC + 8;                 // x3: fp16 row of the context planes
-  float* h_lds = lds;                      // [BT][HLD]                     (x3: two fp16 planes [BT][LDH])
-  float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;        // [BT][HLD]
-  float* ctx_lds = hp_lds + BT * HLD;      // [BT][CLD]                     (x3: two fp16 planes [BT][CLDH])
-  float* e_lds = X3 ? ctx_lds + (2 * BT * CLDH) / 2 : ctx_lds + BT * CLD;  // [BT][T]
-  float* sw_lds = e_lds + BT * T;          // [HID]
-  _Float16* h_hi = reinterpret_cast<_Float16*>(h_lds);
-  _Float16* h_lo = h_hi + BT * LDH;
-  _Float16* c_hi = reinterpret_cast<_Float16*>(ctx_lds);
-  _Float16* c_lo = c_hi + BT * CLDH;
-  const float inv_h2h = X3 ? p.w_inv[0] : 1.f, inv_ih = X3 ? p.w_inv[1] : 1.f, inv_hh = X3 ? p.w_inv[2] : 1.f;
-  // x3: the three fp16 weight streams (4 bytes per weight) behind buffer resources
-  const __amdgpu_buffer_rsrc_t r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * D * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
-
+  const AttnDecParams& p = grp.g[gi];       // (read in place, as the other two kernels do: a copy costs the kernel 90 bytes of scratch per lane)
   // vb = samples per workgroup (2 ... 16, the fewest that keep the launch within 256 workgroups -- attn_launch: every step
   // re-reads the workgroup's Hproj / Hb slices (66 KB per sample each), so more, smaller workgroups shorten the step);
   // rows >= vb of the 16-row MFMA tile are treated like rows beyond the batch
-  const int vb = grp.vb;
-  const int b0 = tile_ * vb;
-  const int Bend = min(p.B, b0 + vb);
-  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
-  const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;
-
-  if constexpr (X3) {
-    for (int i = t_; i < BT * LDH; i += NTH) {
-      const int row = i / LDH, jj = i - row * LDH;
-      const int b = b0 + row;
-      store_h_split(h_hi, h_lo, i, (p.h_state && b < Bend && jj < HID) ? p.h_state[(long)b * HID + jj] : 0.f);
-    }
-    for (int i = t_; i < BT * HLD + BT * CLDH + BT * T; i += NTH) hp_lds[i] = 0.f;   // hp, ctx planes, e: rows >= vb stay zero
-  } else {
-    for (int i = t_; i < BT * HLD; i += NTH) {
-      const int row = i / HLD, jj = i - row * HLD;
-      const int b = b0 + row;
-      h_lds[i] = (p.h_state && b < Bend && jj < HID) ? p.h_state[(long)b * HID + jj] : 0.f;
-    }
-    for (int i = t_; i < BT * (HLD + CLD + T); i += NTH) hp_lds[i] = 0.f;     // hp, ctx, e: rows >= vb stay zero
-  }
-  for (int i = t_; i < HID; i += NTH) sw_lds[i] = p.w_score[i];
-  float bh[4], c[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) bh[g] = p.b_hh ? p.b_hh[g * HID + j] : 0.f;
+  const AttnTile<X3> v = attn_tile<X3>(lds, p, WIDE ? CTX_CHUNK : p.D, tile_, grp.vb, 1);
+  const int j = v.j;
+  float c[4];
+  float h[4] = {0.f, 0.f, 0.f, 0.f};        // h of the last step (the carried state, exact also when LDS holds the fp16 planes)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int b = b0 + rbase + r;
-    c[r] = (p.c_state && b < Bend) ? p.c_state[(long)b * HID + j] : 0.f;
+    const int b = v.b0 + v.rbase + r;
+    c[r] = (p.c_state && b < v.Bend) ? p.c_state[(long)b * HID + j] : 0.f;
   }
-  const float bj = p.b_h2h[j];
-  float hlast[4] = {0.f, 0.f, 0.f, 0.f};        // h of the last step (the carried state, exact also when LDS holds the fp16 planes)
   __syncthreads();
 
   for (int step = 0; step < p.S; ++step) {
-    // (1) hp = h2h(h) + bias
-    {
-      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_h2h, HID, wave, lane);
-      else mma_rows<1>(acc, h_lds, HLD, p.w_h2h, HID, wave, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = acc[0][r] * inv_h2h + bj;
-        hp_lds[(rbase + r) * HLD + j] = v;
-        const int b = b0 + rbase + r;
-        if (p.hp_out && b < Bend) p.hp_out[((long)b * p.S + step) * HID + j] = v;
-      }
-    }
-    __syncthreads();
-    // (2) e[b][t] = score . tanh(Hproj[b][t] + hp[b]); one wave per (b, t) pair, 4 channels per lane, four pairs in
-    //     flight per wave so the Hproj loads (L2) and the cross-lane reductions of different pairs overlap
-    {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(sw_lds + lane * 4);
-      const int npair = vb * T;
-      constexpr int U = 4;                 // pairs in flight per wave (8 measured the same, round 6)
-      for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
-        f32x4 hv[U];
-        int rows[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int pr = pr0 + u;
-          const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
-          rows[u] = row;
-          const int b = b0 + row;
-          hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (pr < npair && b < Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
-        }
-        float sacc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const f32x4 pv = *reinterpret_cast<const f32x4*>(hp_lds + rows[u] * HLD + lane * 4);
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
-          sacc[u] = s;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
-        }
-        if (lane < U && pr0 + lane < npair) {
-          float v = sacc[0];
-#pragma unroll
-          for (int u = 1; u < U; ++u) v = lane == u ? sacc[u] : v;
-          e_lds[pr0 + lane] = (b0 + (pr0 + lane) / T < p.B) ? v : 0.f;
-        }
-      }
-    }
-    __syncthreads();
-    // (3) softmax over t, one wave per sample
-    if (wave < vb) {
-      const int row = wave;
-      float m = -INFINITY;
-      for (int t = lane; t < T; t += 64) m = fmaxf(m, e_lds[row * T + t]);
-      m = wave_max(m);
-      float sum = 0.f;
-      for (int t = lane; t < T; t += 64) {
-        const float v = expf(e_lds[row * T + t] - m);
-        e_lds[row * T + t] = v;
-        sum += v;
-      }
-      sum = wave_sum(sum);
-      const float inv = 1.f / sum;
-      for (int t = lane; t < T; t += 64) {
-        const float a = e_lds[row * T + t] * inv;
-        e_lds[row * T + t] = a;
-        const int b = b0 + row;
-        if (p.alpha_out && b < Bend) p.alpha_out[((long)b * p.S + step) * T + t] = a;
-      }
-    }
-    __syncthreads();
-    // embedding half of the LSTMCell input projection for this step: issued here, it lands during phase (4) and becomes the INITIAL value
-    // of the gate accumulators (x the W_ih stream's power-of-two prescale: exact) -- sixteen registers live over one phase, not the step
+    attn_scores<X3, true>(v, p, step);
     f32x4 acc5[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int b = b0 + rbase + r;
-      const float* ep = p.eproj + (long)(b < Bend ? b : 0) * p.eproj_stride_b + (long)step * p.eproj_stride_s + j;
+      const int b = v.b0 + v.rbase + r;
+      const float* ep = p.eproj + (long)(b < v.Bend ? b : 0) * p.eproj_stride_b + (long)step * p.eproj_stride_s + j;
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
     }
-    // (4) context[b][:] = sum_t alpha[b][t] * Hb[b][t][:]   (WIDE: chunk by chunk in (5))
-    if constexpr (!WIDE) {
-      for (int it = t_; it < vb * (D / 4); it += NTH) {
-        const int row = it / (D / 4), c4 = it - row * (D / 4);
-        const int b = b0 + row;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (b < Bend) {
-          const float* hb = p.Hb + (long)b * T * D + c4 * 4;
-          int t = 0;
-#pragma unroll 1
-          for (; t + 4 <= T; t += 4) {                 // four independent loads in flight per lane, 16 waves per CU (eight: no faster)
-            f32x4 v[4];
+    float act[4][4];
+    attn_cell<X3, WIDE, true>(v, p, step, acc5, c, h, act);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
+    for (int r = 0; r < 4; ++r) {
+      const int b = v.b0 + v.rbase + r;
+      if (b < v.Bend) {
+        p.hid[(long)b * p.hid_stride_b + (long)step * p.hid_stride_s + j] = h[r];
+        if (p.gates_out) {
+          const long base = (long)b * p.S + step;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const float w = e_lds[row * T + t + u];
-#pragma unroll
-              for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
-            }
-          }
-          for (; t < T; ++t) {
-            const float w = e_lds[row * T + t];
-            const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
-          }
+          for (int g = 0; g < 4; ++g) p.gates_out[base * 4 * HID + g * HID + j] = act[g][r];
+          p.c_out[base * HID + j] = c[r];
         }
-        if constexpr (X3) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
-        } else {
-          *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
-        }
-        if (p.ctx_out && b < Bend) *reinterpret_cast<f32x4*>(p.ctx_out + ((long)b * p.S + step) * D + c4 * 4) = a;
-      }
-      __syncthreads();
-    }
-    // (5) gates = eproj + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
-    {
-      f32x4 acc[4];
-      const float pre_ih = 1.f / inv_ih;               // (a power of two)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
-      if constexpr (X3) {
-        if constexpr (WIDE) {
-          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
-            const int kn = min(CTX_CHUNK, D - k0);
-            context_chunk<true>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
-            __syncthreads();
-            mma_rows_hb_k<4>(acc, c_hi, c_lo, r_ih, D, k0, kn, wave, lane, CLDH);
-            if (k0 + CTX_CHUNK < D) __syncthreads();   // every wave is done with this chunk before the next one lands
-          }
-        } else {
-          mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
-        }
-        const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= ratio;
-        mma_rows_hb<4>(acc, h_hi, h_lo, r_hh, HID, wave, lane);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
-      } else {
-        if constexpr (WIDE) {
-          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
-            const int kn = min(CTX_CHUNK, D - k0);
-            context_chunk<false>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
-            __syncthreads();
-            mma_rows_k<4>(acc, ctx_lds, CLD, p.w_ih, D, k0, kn, wave, lane);
-            if (k0 + CTX_CHUNK < D) __syncthreads();
-          }
-        } else {
-          mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
-        }
-        mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
-      }
-      __syncthreads();  // every wave has finished reading h_lds
-      float h[4], act[4][4];
-      lstm_pointwise0(acc, bh, c, h, act);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rbase + r, b = b0 + row;
-        if (b < Bend) {
-          p.hid[(long)b * p.hid_stride_b + (long)step * p.hid_stride_s + j] = h[r];
-          if (p.gates_out) {
-            const long base = (long)b * p.S + step;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) p.gates_out[base * 4 * HID + g * HID + j] = act[g][r];
-            p.c_out[base * HID + j] = c[r];
-          }
-        }
-        if constexpr (X3) store_h_split(h_hi, h_lo, row * LDH + j, b < Bend ? h[r] : 0.f);
-        else h_lds[row * HLD + j] = b < Bend ? h[r] : 0.f;
-        hlast[r] = h[r];
       }
     }
     __syncthreads();
@@ -986,9 +989,9 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
   if (p.h_state) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = rbase + r, b = b0 + row;
-      if (b < Bend) {
-        p.h_state[(long)b * HID + j] = hlast[r];
+      const int b = v.b0 + v.rbase + r;
+      if (b < v.Bend) {
+        p.h_state[(long)b * HID + j] = h[r];
         p.c_state[(long)b * HID + j] = c[r];
       }
     }
@@ -996,16 +999,12 @@ __global__ __launch_bounds__(NTH) void attn_decoder_kernel(const AttnDecGroup gr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Greedy decoding (reference modules/prediction.py:70-86), all S steps of all experts in one launch: the step of attn_decoder_kernel
-// with the token fed back inside the workgroup.  A workgroup's samples never need another workgroup's result, so this is a plain
-// persistent loop with workgroup barriers only.  Per step:
+// Greedy decoding (reference modules/prediction.py:70-86), all S steps of all experts in one launch: the shared step with the token fed
+// back inside the workgroup.  A workgroup's samples never need another workgroup's result, so this is a plain persistent loop with
+// workgroup barriers only.  What it adds to the step:
 //   (0) token: the caller's start token at step 0, then the previous step's argmax (LDS); a token >= num_class counts as 0
-//       (Attention.cut_unknown).  The embedding half of the LSTMCell input is row `token` of etab [num_class][4*HID] =
-//       char_embeddings.weight . W_ih[:, D:]^T + b_ih, which seeds the gate accumulators where eproj does in attn_decoder_kernel
-//   (1)-(6) as attn_decoder_kernel, the same arithmetic in the same order (chunked context in the WIDE form)
-//   (7) logits[b][step][:] = h . W_gen^T + b_gen: class tile n (16 classes) belongs to wave n % 16, K = 256 comes from the h planes
-//       in LDS, W_gen is a one-gate-group fragment-major stream whose rows are zero-padded to a multiple of 16 (padded columns are
-//       neither stored nor compared)
+//       (Attention.cut_unknown).  The gate seed is row `token` of etab [num_class][4*HID] = char_embeddings.weight . W_ih[:, D:]^T + b_ih
+//   (7) logits[b][step][:] = h . W_gen^T + b_gen (generator_tiles)
 //   (8) argmax: a running best per lane over its tiles, shuffles over the 16 class columns, then the 16 waves through LDS; the
 //       comparison of rowops.hip argmax_kernel (first index of the maximum, a NaN beats a number, an all-NaN row gives 0)
 // ---------------------------------------------------------------------------------------------
@@ -1030,139 +1029,57 @@ __device__ __forceinline__ bool argmax_take(float ov, int oi, float best, int bi
   return (ov > best) || (ov == best && oi < bi) || (ov != ov && best == best);
 }
 
+// the generator on the new h, of the greedy and beam kernels: logits[row][cls] = h . W_gen^T + b_gen, class tile n (16 classes) belongs
+// to wave n % 16, K = 256 comes from the h planes in LDS, W_gen is a one-gate-group fragment-major stream whose rows are zero-padded
+// to a multiple of 16 (padded columns never reach the sink).  sink(r, cls, logit): row rbase + r of the lane's class
+// (r_gen, inv_gen: the stream's buffer resource and inverse prescale, formed by the kernel once before its step loop -- formed here, the
+// beam kernel ran 0.4-1 % slower at W = 4 and 8)
+template <bool X3, class Sink>
+__device__ __forceinline__ void generator_tiles(const AttnTile<X3>& v, const GreedyParams& gp, __amdgpu_buffer_rsrc_t r_gen, float inv_gen,
+                                                Sink sink) {
+  const int C = gp.num_class, ntile = (C + 15) / 16;
+#pragma unroll 1
+  for (int n = v.wave; n < ntile; n += NW) {
+    f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+    if constexpr (X3) mma_rows_hb<1>(acc, v.h_hi, v.h_lo, r_gen, HID, n, v.lane);
+    // (exact form: the stream pointer is advanced to tile n and the helper's wave argument stays 0 -- every other caller passes a wave
+    // index below 16, a range the compiler carries into the shared helper and that attn_decoder_kernel's register allocation rests on)
+    else mma_rows<1>(acc, v.h_lds, HLD, gp.w_gen + (long)n * (HID / 16) * 256, HID, 0, v.lane);
+    const int cls = n * 16 + v.col;
+    if (cls < C) {
+      const float bg = gp.b_gen[cls];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sink(r, cls, acc[0][r] * inv_gen + bg);
+    }
+  }
+}
+
 template <bool X3, bool WIDE>
 __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int gi, tile_;                  // (group, tile) placement: as attn_decoder_kernel
-  if (grp.pinned == 2) {
-    const int per = grp.groups * grp.tiles / 8;
-    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    gi = pair / grp.tiles;
-    tile_ = pair - gi * grp.tiles;
-  } else {
-    gi = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
-    tile_ = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
-  }
+  int gi, tile_;
+  group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
   if (gi >= grp.groups) return;
   const GreedyParams& gp = grp.g[gi];
   const AttnDecParams& p = gp.a;
-  const int D = p.D, T = p.T, C = gp.num_class;
-  const int ntile = (C + 15) / 16;
-  const int DC = WIDE ? CTX_CHUNK : D;
-  const int CLD = DC + 4;
-  const int CLDH = DC + 8;
-  float* h_lds = lds;                      // the LDS map of attn_decoder_kernel ...
-  float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;
-  float* ctx_lds = hp_lds + BT * HLD;
-  float* e_lds = X3 ? ctx_lds + (2 * BT * CLDH) / 2 : ctx_lds + BT * CLD;
-  float* sw_lds = e_lds + BT * T;
-  int* tok_lds = reinterpret_cast<int*>(sw_lds + HID);       // ... + [BT] tokens, [NW][BT] best values, [NW][BT] best indices
+  const int C = gp.num_class;
+  const float inv_gen = X3 ? p.w_inv[3] : 1.f;     // the generator stream (x3: fp16 hi / lo behind a buffer resource) and its inverse prescale
+  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0, 0x00020000);
+  const AttnTile<X3> v = attn_tile<X3>(lds, p, WIDE ? CTX_CHUNK : p.D, tile_, grp.vb, 1);
+  int* tok_lds = reinterpret_cast<int*>(v.sw_lds + HID);     // behind the shared map: [BT] tokens, [NW][BT] best values, [NW][BT] best indices
   float* red_v = reinterpret_cast<float*>(tok_lds + BT);
   int* red_i = reinterpret_cast<int*>(red_v + NW * BT);
-  _Float16* h_hi = reinterpret_cast<_Float16*>(h_lds);
-  _Float16* h_lo = h_hi + BT * LDH;
-  _Float16* c_hi = reinterpret_cast<_Float16*>(ctx_lds);
-  _Float16* c_lo = c_hi + BT * CLDH;
-  const float inv_h2h = X3 ? p.w_inv[0] : 1.f, inv_ih = X3 ? p.w_inv[1] : 1.f, inv_hh = X3 ? p.w_inv[2] : 1.f;
-  const float inv_gen = X3 ? p.w_inv[3] : 1.f;
-  const __amdgpu_buffer_rsrc_t r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * D * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? ntile * 16 * HID * 4 : 0, 0x00020000);
-
-  const int vb = grp.vb;
-  const int b0 = tile_ * vb;
-  const int Bend = min(p.B, b0 + vb);
-  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
-  const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;
-
-  if constexpr (X3) {
-    for (int i = t_; i < BT * LDH; i += NTH) store_h_split(h_hi, h_lo, i, 0.f);
-    for (int i = t_; i < BT * HLD + BT * CLDH + BT * T; i += NTH) hp_lds[i] = 0.f;   // hp, ctx planes, e: rows >= vb stay zero
-  } else {
-    for (int i = t_; i < BT * HLD; i += NTH) h_lds[i] = 0.f;
-    for (int i = t_; i < BT * (HLD + CLD + T); i += NTH) hp_lds[i] = 0.f;
-  }
-  for (int i = t_; i < HID; i += NTH) sw_lds[i] = p.w_score[i];
+  const int t_ = v.t_, wave = v.wave, rbase = v.rbase, j = v.j;
   if (t_ < BT) {
     const long k = gp.start[0];
     tok_lds[t_] = (k >= C || k < 0) ? 0 : (int)k;
   }
-  float bh[4], c[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < 4; ++g) bh[g] = p.b_hh ? p.b_hh[g * HID + j] : 0.f;
-  const float bj = p.b_h2h[j];
+  float c[4] = {0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
   for (int step = 0; step < p.S; ++step) {
-    // (1) hp = h2h(h) + bias
-    {
-      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_h2h, HID, wave, lane);
-      else mma_rows<1>(acc, h_lds, HLD, p.w_h2h, HID, wave, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hp_lds[(rbase + r) * HLD + j] = acc[0][r] * inv_h2h + bj;
-    }
-    __syncthreads();
-    // (2) e[b][t] = score . tanh(Hproj[b][t] + hp[b])
-    {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(sw_lds + lane * 4);
-      const int npair = vb * T;
-      constexpr int U = 4;
-      for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
-        f32x4 hv[U];
-        int rows[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int pr = pr0 + u;
-          const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
-          rows[u] = row;
-          const int b = b0 + row;
-          hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (pr < npair && b < Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
-        }
-        float sacc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const f32x4 pv = *reinterpret_cast<const f32x4*>(hp_lds + rows[u] * HLD + lane * 4);
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
-          sacc[u] = s;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
-        }
-        if (lane < U && pr0 + lane < npair) {
-          float v = sacc[0];
-#pragma unroll
-          for (int u = 1; u < U; ++u) v = lane == u ? sacc[u] : v;
-          e_lds[pr0 + lane] = (b0 + (pr0 + lane) / T < p.B) ? v : 0.f;
-        }
-      }
-    }
-    __syncthreads();
-    // (3) softmax over t, one wave per sample
-    if (wave < vb) {
-      const int row = wave;
-      float m = -INFINITY;
-      for (int t = lane; t < T; t += 64) m = fmaxf(m, e_lds[row * T + t]);
-      m = wave_max(m);
-      float sum = 0.f;
-      for (int t = lane; t < T; t += 64) {
-        const float v = expf(e_lds[row * T + t] - m);
-        e_lds[row * T + t] = v;
-        sum += v;
-      }
-      sum = wave_sum(sum);
-      const float inv = 1.f / sum;
-      for (int t = lane; t < T; t += 64) e_lds[row * T + t] *= inv;
-    }
-    __syncthreads();
-    // (0) the token's row of etab: the initial value of the gate accumulators (lands during phase (4))
+    attn_scores<X3, false>(v, p, step);
+    // (0) the token's row of etab
     f32x4 acc5[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1170,91 +1087,8 @@ __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp)
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
     }
-    // (4) context[b][:] = sum_t alpha[b][t] * Hb[b][t][:]   (WIDE: chunk by chunk in (5))
-    if constexpr (!WIDE) {
-      for (int it = t_; it < vb * (D / 4); it += NTH) {
-        const int row = it / (D / 4), c4 = it - row * (D / 4);
-        const int b = b0 + row;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (b < Bend) {
-          const float* hb = p.Hb + (long)b * T * D + c4 * 4;
-          int t = 0;
-#pragma unroll 1
-          for (; t + 4 <= T; t += 4) {
-            f32x4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const float w = e_lds[row * T + t + u];
-#pragma unroll
-              for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
-            }
-          }
-          for (; t < T; ++t) {
-            const float w = e_lds[row * T + t];
-            const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
-          }
-        }
-        if constexpr (X3) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
-        } else {
-          *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
-        }
-      }
-      __syncthreads();
-    }
-    // (5) gates = etab[token] + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
-    {
-      f32x4 acc[4];
-      const float pre_ih = 1.f / inv_ih;               // (a power of two)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
-      if constexpr (X3) {
-        if constexpr (WIDE) {
-          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
-            const int kn = min(CTX_CHUNK, D - k0);
-            context_chunk<true>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
-            __syncthreads();
-            mma_rows_hb_k<4>(acc, c_hi, c_lo, r_ih, D, k0, kn, wave, lane, CLDH);
-            if (k0 + CTX_CHUNK < D) __syncthreads();
-          }
-        } else {
-          mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
-        }
-        const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= ratio;
-        mma_rows_hb<4>(acc, h_hi, h_lo, r_hh, HID, wave, lane);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
-      } else {
-        if constexpr (WIDE) {
-          for (int k0 = 0; k0 < D; k0 += CTX_CHUNK) {
-            const int kn = min(CTX_CHUNK, D - k0);
-            context_chunk<false>(p, e_lds, ctx_lds, c_hi, c_lo, CLD, CLDH, b0, Bend, vb, step, k0, kn, t_);
-            __syncthreads();
-            mma_rows_k<4>(acc, ctx_lds, CLD, p.w_ih, D, k0, kn, wave, lane);
-            if (k0 + CTX_CHUNK < D) __syncthreads();
-          }
-        } else {
-          mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
-        }
-        mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
-      }
-      __syncthreads();  // every wave has finished reading h_lds
-      float h[4], act[4][4];
-      lstm_pointwise0(acc, bh, c, h, act);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rbase + r, b = b0 + row;
-        if constexpr (X3) store_h_split(h_hi, h_lo, row * LDH + j, b < Bend ? h[r] : 0.f);
-        else h_lds[row * HLD + j] = b < Bend ? h[r] : 0.f;
-      }
-    }
+    float h[4], act[4][4];
+    attn_cell<X3, WIDE, false>(v, p, step, acc5, c, h, act);
     __syncthreads();
     // (7) generator on the new h, (8) running argmax of the lane's classes
     float best[4];
@@ -1264,28 +1098,14 @@ __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp)
       best[r] = -INFINITY;
       bi[r] = 0x7fffffff;
     }
-#pragma unroll 1
-    for (int n = wave; n < ntile; n += NW) {
-      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_gen, HID, n, lane);
-      // (exact form: the stream pointer is advanced to tile n and the helper's wave argument stays 0 -- every other caller passes a wave
-      // index below 16, a range the compiler carries into the shared helper and that attn_decoder_kernel's register allocation rests on)
-      else mma_rows<1>(acc, h_lds, HLD, gp.w_gen + (long)n * (HID / 16) * 256, HID, 0, lane);
-      const int cls = n * 16 + col;
-      if (cls < C) {
-        const float bg = gp.b_gen[cls];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc[0][r] * inv_gen + bg;
-          const int b = b0 + rbase + r;
-          if (b < Bend) gp.logits[(long)b * gp.logits_stride_b + (long)step * gp.logits_stride_s + cls] = v;
-          if (v > best[r] || (v != v && best[r] == best[r])) {
-            best[r] = v;
-            bi[r] = cls;
-          }
-        }
+    generator_tiles<X3>(v, gp, r_gen, inv_gen, [&](int r, int cls, float x) {
+      const int b = v.b0 + rbase + r;
+      if (b < v.Bend) gp.logits[(long)b * gp.logits_stride_b + (long)step * gp.logits_stride_s + cls] = x;
+      if (x > best[r] || (x != x && best[r] == best[r])) {
+        best[r] = x;
+        bi[r] = cls;
       }
-    }
+    });
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) {
 #pragma unroll
@@ -1298,7 +1118,7 @@ __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp)
         }
       }
     }
-    if (col == 0) {
+    if (v.col == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         red_v[wave * BT + rbase + r] = best[r];
@@ -1319,8 +1139,8 @@ __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp)
       }
       if (bx >= C) bx = 0;
       tok_lds[t_] = bx;
-      const int b = b0 + t_;
-      if (gp.tokens_out && b < Bend) gp.tokens_out[(long)b * p.S + step] = bx;
+      const int b = v.b0 + t_;
+      if (gp.tokens_out && b < v.Bend) gp.tokens_out[(long)b * p.S + step] = bx;
     }
   }
 }
@@ -1340,8 +1160,8 @@ __global__ void embed_gather_kernel(const long* __restrict__ idx, const float* _
 // Beam-search decoding on the attention head (extends reference modules/prediction.py:70-86; the algorithm is stated in
 // mrn_amd/modules/decoding.py), all S steps of all experts in one launch.  The 16 MFMA rows of a workgroup are 16 / W samples x W
 // entries: row r is entry r % W of sample b0 + r / W, rows of one sample read the same Hproj / Hb slices.  Per step:
-//   (0)-(7) as attn_greedy_kernel (whole-context form), the same arithmetic in the same order on every row, so a row's logits are
-//       bit-identical to the greedy kernel's for the same token history; the logits go to the workgroup's scratch rows in global
+//   (0)-(7) the shared step in its whole-context form on every row, with the greedy kernel's token feed and generator: a row's logits
+//       are bit-identical to the greedy kernel's for the same token history; the logits go to the workgroup's scratch rows in global
 //       memory (16 x C floats do not fit beside the tile in LDS), the new c of every row is staged in hp_lds, free since phase (2)
 //   (8) wave r, row r: log-sum-exp of the row, then its W best classes by W scans (larger logit first, a tie to the lower class, a
 //       NaN logit counts as -inf) -> candidates (score_r + logit - lse, class, logit - lse) in LDS; a finished row gives (score_r,
@@ -1374,32 +1194,19 @@ __device__ __forceinline__ bool beam_before(float va, int ia, float vb_, int ib)
 template <bool X3>
 __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int gi, tile_;                  // (group, tile) placement: as attn_greedy_kernel
-  if (grp.pinned == 2) {
-    const int per = grp.groups * grp.tiles / 8;
-    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    gi = pair / grp.tiles;
-    tile_ = pair - gi * grp.tiles;
-  } else {
-    gi = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
-    tile_ = grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles;
-  }
+  int gi, tile_;
+  group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
   if (gi >= grp.groups) return;
   const BeamParams& bp = grp.g[gi];
   const GreedyParams& gp = bp.g;
   const AttnDecParams& p = gp.a;
-  const int D = p.D, T = p.T, C = gp.num_class, S = p.S;
+  const int C = gp.num_class, S = p.S;
   const int W = grp.W, eos = grp.eos;
-  const int ntile = (C + 15) / 16;
-  const int CP = ntile * 16;                 // scratch row stride
-  const int CLD = D + 4;
-  const int CLDH = D + 8;
-  float* h_lds = lds;                      // the LDS map of attn_greedy_kernel's whole-context form ...
-  float* hp_lds = X3 ? lds + (2 * BT * LDH) / 2 : h_lds + BT * HLD;
-  float* ctx_lds = hp_lds + BT * HLD;
-  float* e_lds = X3 ? ctx_lds + (2 * BT * CLDH) / 2 : ctx_lds + BT * CLD;
-  float* sw_lds = e_lds + BT * T;
-  int* tok_lds = reinterpret_cast<int*>(sw_lds + HID);       // ... + the beam state of BEAM_LDS_EXTRA
+  const int CP = (C + 15) / 16 * 16;         // scratch row stride
+  const float inv_gen = X3 ? p.w_inv[3] : 1.f;     // the generator stream (x3: fp16 hi / lo behind a buffer resource) and its inverse prescale
+  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0, 0x00020000);
+  const AttnTile<X3> v = attn_tile<X3>(lds, p, p.D, tile_, BT / W, W);       // 16 / W samples x W entries
+  int* tok_lds = reinterpret_cast<int*>(v.sw_lds + HID);     // behind the shared map: the beam state of BEAM_LDS_EXTRA
   float* score_lds = reinterpret_cast<float*>(tok_lds + BT);
   int* fin_lds = reinterpret_cast<int*>(score_lds + BT);
   float* nsc = reinterpret_cast<float*>(fin_lds + BT);
@@ -1410,118 +1217,25 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
   float* cand_v = reinterpret_cast<float*>(flag_lds + BT);
   int* cand_c = reinterpret_cast<int*>(cand_v + BT * BT);
   float* cand_lp = reinterpret_cast<float*>(cand_c + BT * BT);
-  _Float16* h_hi = reinterpret_cast<_Float16*>(h_lds);
-  _Float16* h_lo = h_hi + BT * LDH;
-  _Float16* c_hi = reinterpret_cast<_Float16*>(ctx_lds);
-  _Float16* c_lo = c_hi + BT * CLDH;
-  const float inv_h2h = X3 ? p.w_inv[0] : 1.f, inv_ih = X3 ? p.w_inv[1] : 1.f, inv_hh = X3 ? p.w_inv[2] : 1.f;
-  const float inv_gen = X3 ? p.w_inv[3] : 1.f;
-  const __amdgpu_buffer_rsrc_t r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * D * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? ntile * 16 * HID * 4 : 0, 0x00020000);
-
-  const int ns = BT / W;                     // samples per workgroup
-  const int nrows = ns * W;                  // rows in use
-  const int b0 = tile_ * ns;
-  const int Bend = min(p.B, b0 + ns);
-  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
-  const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;
+  const int b0 = v.b0, Bend = v.Bend, nrows = v.nrows, t_ = v.t_, lane = v.lane, wave = v.wave, rbase = v.rbase, j = v.j;
   float* const row_scr = bp.scratch + (long)tile_ * BT * (CP + 3 * S);      // [16][CP]
   int* const hist_par = reinterpret_cast<int*>(row_scr + (long)BT * CP);   // [S][16]
   int* const hist_tok = hist_par + (long)S * BT;
   float* const hist_lp = reinterpret_cast<float*>(hist_tok + (long)S * BT);
 
-  if constexpr (X3) {
-    for (int i = t_; i < BT * LDH; i += NTH) store_h_split(h_hi, h_lo, i, 0.f);
-    for (int i = t_; i < BT * HLD + BT * CLDH + BT * T; i += NTH) hp_lds[i] = 0.f;   // hp, ctx planes, e: unused rows stay zero
-  } else {
-    for (int i = t_; i < BT * HLD; i += NTH) h_lds[i] = 0.f;
-    for (int i = t_; i < BT * (HLD + CLD + T); i += NTH) hp_lds[i] = 0.f;
-  }
-  for (int i = t_; i < HID; i += NTH) sw_lds[i] = p.w_score[i];
   if (t_ < BT) {
     const long k = gp.start[0];
     tok_lds[t_] = (k >= C || k < 0) ? 0 : (int)k;
     score_lds[t_] = (t_ < nrows && t_ % W == 0 && b0 + t_ / W < Bend) ? 0.f : -INFINITY;      // one live entry per sample
     fin_lds[t_] = 0;
   }
-  float bh[4], c[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < 4; ++g) bh[g] = p.b_hh ? p.b_hh[g * HID + j] : 0.f;
-  const float bj = p.b_h2h[j];
+  float c[4] = {0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
   int nst = 0;                               // steps run
   for (int step = 0; step < S; ++step) {
-    // (1) hp = h2h(h) + bias
-    {
-      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_h2h, HID, wave, lane);
-      else mma_rows<1>(acc, h_lds, HLD, p.w_h2h, HID, wave, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hp_lds[(rbase + r) * HLD + j] = acc[0][r] * inv_h2h + bj;
-    }
-    __syncthreads();
-    // (2) e[row][t] = score . tanh(Hproj[b][t] + hp[row])
-    {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(sw_lds + lane * 4);
-      const int npair = nrows * T;
-      constexpr int U = 4;
-      for (int pr0 = wave * U; pr0 < npair; pr0 += NW * U) {
-        f32x4 hv[U];
-        int rows[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int pr = pr0 + u;
-          const int row = pr < npair ? pr / T : 0, t = pr < npair ? pr - row * T : 0;
-          rows[u] = row;
-          const int b = b0 + row / W;
-          hv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (pr < npair && b < Bend) hv[u] = *reinterpret_cast<const f32x4*>(p.Hproj + ((long)b * T + t) * HID + lane * 4);
-        }
-        float sacc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const f32x4 pv = *reinterpret_cast<const f32x4*>(hp_lds + rows[u] * HLD + lane * 4);
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) s = fmaf(wv[k], fast_tanh(hv[u][k] + pv[k]), s);
-          sacc[u] = s;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) sacc[u] += __shfl_xor(sacc[u], o);
-        }
-        if (lane < U && pr0 + lane < npair) {
-          float v = sacc[0];
-#pragma unroll
-          for (int u = 1; u < U; ++u) v = lane == u ? sacc[u] : v;
-          e_lds[pr0 + lane] = (b0 + ((pr0 + lane) / T) / W < Bend) ? v : 0.f;
-        }
-      }
-    }
-    __syncthreads();
-    // (3) softmax over t, one wave per row
-    if (wave < nrows) {
-      const int row = wave;
-      float m = -INFINITY;
-      for (int t = lane; t < T; t += 64) m = fmaxf(m, e_lds[row * T + t]);
-      m = wave_max(m);
-      float sum = 0.f;
-      for (int t = lane; t < T; t += 64) {
-        const float v = expf(e_lds[row * T + t] - m);
-        e_lds[row * T + t] = v;
-        sum += v;
-      }
-      sum = wave_sum(sum);
-      const float inv = 1.f / sum;
-      for (int t = lane; t < T; t += 64) e_lds[row * T + t] *= inv;
-    }
-    __syncthreads();
-    // (0) the token's row of etab: the initial value of the gate accumulators (lands during phase (4))
+    attn_scores<X3, false>(v, p, step);
+    // (0) the token's row of etab
     f32x4 acc5[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1529,84 +1243,13 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
     }
-    // (4) context[row][:] = sum_t alpha[row][t] * Hb[b][t][:]
-    for (int it = t_; it < nrows * (D / 4); it += NTH) {
-      const int row = it / (D / 4), c4 = it - row * (D / 4);
-      const int b = b0 + row / W;
-      f32x4 a = {0.f, 0.f, 0.f, 0.f};
-      if (b < Bend) {
-        const float* hb = p.Hb + (long)b * T * D + c4 * 4;
-        int t = 0;
-#pragma unroll 1
-        for (; t + 4 <= T; t += 4) {
-          f32x4 v[4];
+    float h[4], act[4][4];
+    attn_cell<X3, false, false>(v, p, step, acc5, c, h, act);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(hb + (long)(t + u) * D);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float w = e_lds[row * T + t + u];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[u][k], a[k]);
-          }
-        }
-        for (; t < T; ++t) {
-          const float w = e_lds[row * T + t];
-          const f32x4 v = *reinterpret_cast<const f32x4*>(hb + (long)t * D);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) a[k] = fmaf(w, v[k], a[k]);
-        }
-      }
-      if constexpr (X3) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) store_h_split(c_hi, c_lo, row * CLDH + c4 * 4 + k, a[k]);
-      } else {
-        *reinterpret_cast<f32x4*>(ctx_lds + row * CLD + c4 * 4) = a;
-      }
-    }
-    __syncthreads();
-    // (5) gates = etab[token] + ctx . W_ih[:, :D]^T + h . W_hh^T ; (6) LSTM cell
-    {
-      f32x4 acc[4];
-      const float pre_ih = 1.f / inv_ih;               // (a power of two)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = acc5[g] * pre_ih;
-      if constexpr (X3) {
-        mma_rows_hb<4>(acc, c_hi, c_lo, r_ih, D, wave, lane, CLDH);
-        const float ratio = inv_ih / inv_hh;            // (powers of two: exact)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= ratio;
-        mma_rows_hb<4>(acc, h_hi, h_lo, r_hh, HID, wave, lane);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] *= inv_hh;
-      } else {
-        mma_rows<4>(acc, ctx_lds, CLD, p.w_ih, D, wave, lane);
-        mma_rows<4>(acc, h_lds, HLD, p.w_hh, HID, wave, lane);
-      }
-      __syncthreads();  // every wave has finished reading h_lds
-      float h[4], act[4][4];
-      lstm_pointwise0(acc, bh, c, h, act);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rbase + r, b = b0 + row / W;
-        if constexpr (X3) store_h_split(h_hi, h_lo, row * LDH + j, b < Bend ? h[r] : 0.f);
-        else h_lds[row * HLD + j] = b < Bend ? h[r] : 0.f;
-        hp_lds[row * HLD + j] = c[r];                   // staged for (10)
-      }
-    }
+    for (int r = 0; r < 4; ++r) v.hp_lds[(rbase + r) * HLD + j] = c[r];      // staged for (10)
     __syncthreads();
     // (7) generator on the new h -> the workgroup's scratch rows
-#pragma unroll 1
-    for (int n = wave; n < ntile; n += NW) {
-      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (X3) mma_rows_hb<1>(acc, h_hi, h_lo, r_gen, HID, n, lane);
-      else mma_rows<1>(acc, h_lds, HLD, gp.w_gen + (long)n * (HID / 16) * 256, HID, 0, lane);   // (wave argument 0: see attn_greedy_kernel)
-      const int cls = n * 16 + col;
-      if (cls < C) {
-        const float bg = gp.b_gen[cls];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) row_scr[(long)(rbase + r) * CP + cls] = acc[0][r] * inv_gen + bg;
-      }
-    }
+    generator_tiles<X3>(v, gp, r_gen, inv_gen, [&](int r, int cls, float x) { row_scr[(long)(rbase + r) * CP + cls] = x; });
     __syncthreads();
     // (8) row `wave`: log-sum-exp and the W best classes
     {
@@ -1711,12 +1354,12 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int par = npar[rbase + r];
-      c[r] = hp_lds[par * HLD + j];
+      c[r] = v.hp_lds[par * HLD + j];
       if constexpr (X3) {
-        hh[r] = h_hi[par * LDH + j];
-        hl[r] = h_lo[par * LDH + j];
+        hh[r] = v.h_hi[par * LDH + j];
+        hl[r] = v.h_lo[par * LDH + j];
       } else {
-        hf[r] = h_lds[par * HLD + j];
+        hf[r] = v.h_lds[par * HLD + j];
       }
     }
     if (t_ < BT) {
@@ -1736,10 +1379,10 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
     for (int r = 0; r < 4; ++r) {
       const int row = rbase + r;
       if constexpr (X3) {
-        h_hi[row * LDH + j] = hh[r];
-        h_lo[row * LDH + j] = hl[r];
+        v.h_hi[row * LDH + j] = hh[r];
+        v.h_lo[row * LDH + j] = hl[r];
       } else {
-        h_lds[row * HLD + j] = hf[r];
+        v.h_lds[row * HLD + j] = hf[r];
       }
     }
     const int go_on = flag_lds[0];
@@ -1890,62 +1533,103 @@ MRN_EXPORT int mrn_lstm_layer_fwd_x3_save(const float* xproj, const void* w_hh, 
   return MRN_OK;
 }
 
-static int attn_fill(AttnDecParams& p, const float* Hb, const float* Hproj, const float* eproj, int64_t eproj_stride_b,
-                     int64_t eproj_stride_s, const float* w_h2h, const float* b_h2h, const float* w_score,
-                     const float* w_ih_ctx, const float* w_hh, const float* b_hh, float* hid, int64_t hid_stride_b,
-                     int64_t hid_stride_s, int B, int T, int D, int S) {
-  memset(&p, 0, sizeof(p));
-  p.Hb = Hb; p.Hproj = Hproj; p.eproj = eproj; p.w_h2h = w_h2h; p.b_h2h = b_h2h; p.w_score = w_score;
-  p.w_ih = w_ih_ctx; p.w_hh = w_hh; p.b_hh = b_hh; p.hid = hid;
-  p.B = B; p.T = T; p.D = D; p.S = S;
-  p.eproj_stride_b = eproj_stride_b; p.eproj_stride_s = eproj_stride_s;
-  p.hid_stride_b = hid_stride_b; p.hid_stride_s = hid_stride_s;
-  return MRN_OK;
+// ---- launch rules of the three attention decoder kernels ------------------------------------------------------
+// LDS bytes of AttnTile's map for dc context columns and T frames plus the launching kernel's own arrays.  ops.attn_decoder_whole_context,
+// ops.attn_greedy_whole_context and ops.attn_beam_whole_context restate the sum
+static size_t attn_tile_lds(bool x3, int dc, int T, size_t extra) {
+  return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra;
 }
 
-template <bool X3, bool WIDE>
-static void attn_kernel_launch(const AttnDecGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    hipFuncSetAttribute((const void*)attn_decoder_kernel<X3, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_decoder_kernel<X3, WIDE>), grid, dim3(NTH), lds, st, grp);
+// the placement of groups x tiles workgroups that group_tile reads back: `pinned` and the grid
+static dim3 attn_grid(int groups, int tiles, bool balance, int& pinned) {
+  pinned = groups > 1 && tiles * ceil_div(groups, 8) <= 32;
+  if (balance && groups > 1 && (groups * tiles) % 8 == 0 && groups * tiles <= 256) pinned = 2;
+  return dim3(pinned == 1 ? 8 * ceil_div(groups, 8) * tiles : groups * tiles);
 }
+
+// samples per workgroup: the fewest (from two) that keep the launch within one workgroup per CU
+static int attn_vb(int groups, int B) {
+  for (int v = 2; v < BT; v *= 2)
+    if ((long)groups * ceil_div(B, v) <= 256) return v;
+  return BT;
+}
+
+template <class Kernel, class Group>
+static void attn_kernel_launch(Kernel kernel, const Group& grp, dim3 grid, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, dim3(NTH), lds, st, grp);
+}
+#define MRN_ATTN_FORM(kernel, x3, wide) \
+  ((x3) ? ((wide) ? kernel<true, true> : kernel<true, false>) : ((wide) ? kernel<false, true> : kernel<false, false>))
 
 static int attn_launch(AttnDecGroup& grp, int groups, int D, int T, hipStream_t st) {
   grp.groups = groups;
   const int B = grp.g[0].B;
-  // samples per workgroup: the fewest (from two) that keep the launch within one workgroup per CU.  The step is a chain of dependent
-  // phases whose length grows with the samples a workgroup walks through (B = 256, one expert, us per launch: 1100 at 1, 1130 at 2, 1315 at
-  // 4, 1700 at 8, 2580 at 16 -- tools/bench_decoder.py with MRN_ATTN_VB), and a second round of workgroups doubles it (three experts:
-  // 2330 at 2, 1380 at 4).  Not one: a trained network's launch then fills the chip, and the DER step, which runs its two heads'
-  // decoders side by side, loses 3 % (loop A gains 1.5 %: tools/probe/vb_sweep.sh)
-  grp.vb = BT;
-  for (int v = 2; v < BT; v *= 2)
-    if ((long)groups * ceil_div(B, v) <= 256) { grp.vb = v; break; }
+  // attn_vb: the step is a chain of dependent phases whose length grows with the samples a workgroup walks through (B = 256, one expert,
+  // us per launch: 1100 at 1, 1130 at 2, 1315 at 4, 1700 at 8, 2580 at 16 -- tools/bench_decoder.py with MRN_ATTN_VB), and a second round
+  // of workgroups doubles it (three experts: 2330 at 2, 1380 at 4).  Not one: a trained network's launch then fills the chip, and the DER
+  // step, which runs its two heads' decoders side by side, loses 3 % (loop A gains 1.5 %: tools/probe/vb_sweep.sh)
+  grp.vb = attn_vb(groups, B);
   static const int forced_vb = getenv("MRN_ATTN_VB") ? atoi(getenv("MRN_ATTN_VB")) : 0;     // (A/B switch, read once)
   if (forced_vb == 1 || forced_vb == 2 || forced_vb == 4 || forced_vb == 8 || forced_vb == 16) grp.vb = forced_vb;
   grp.tiles = ceil_div(B, grp.vb);
-  grp.pinned = groups > 1 && grp.tiles * ceil_div(groups, 8) <= 32;
   static const bool balance = !(getenv("MRN_ATTN_BALANCE") && atoi(getenv("MRN_ATTN_BALANCE")) == 0);     // (A/B switch, read once)
-  if (balance && groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
+  const dim3 grid = attn_grid(groups, grp.tiles, balance, grp.pinned);
   const bool x3 = grp.g[0].w_inv != nullptr;
   // the single-launch form holds the tile's whole context (BT x (D + 4) floats) in LDS; where that breaks the 160 KB budget (D = 256 * G,
   // G >= 8 at T = 65) the WIDE form holds CTX_CHUNK columns of it at a time.  MRN_ATTN_CTX_CHUNK=1 takes the WIDE form at any D (test
   // switch, read per launch)
-  auto lds_for = [&](int dc) { return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0); };
   const char* force = getenv("MRN_ATTN_CTX_CHUNK");
-  const bool wide = lds_for(D) > 160 * 1024 || (force && atoi(force) == 1);
-  const size_t lds = lds_for(wide ? CTX_CHUNK : D);
+  const bool wide = attn_tile_lds(x3, D, T, 0) > 160 * 1024 || (force && atoi(force) == 1);
+  const size_t lds = attn_tile_lds(x3, wide ? CTX_CHUNK : D, T, 0);
   MRN_CHECK_ARG(lds <= 160 * 1024, "mrn_attn_decoder_fwd: LDS budget exceeded (D=%d T=%d)", D, T);
   MRN_CHECK_ARG(!x3 || D % 32 == 0, "mrn_attn_decoder_fwd (x3): D=%d must be a multiple of 32", D);
-  const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
-  if (x3) {
-    if (wide) attn_kernel_launch<true, true>(grp, grid, lds, st);
-    else attn_kernel_launch<true, false>(grp, grid, lds, st);
-  } else {
-    if (wide) attn_kernel_launch<false, true>(grp, grid, lds, st);
-    else attn_kernel_launch<false, false>(grp, grid, lds, st);
-  }
+  attn_kernel_launch(MRN_ATTN_FORM(attn_decoder_kernel, x3, wide), grp, grid, lds, st);
   MRN_LAUNCH_CHECK("attn_decoder");
+  return MRN_OK;
+}
+
+// The four teacher-forced entry points: `groups` experts of identical geometry, one launch per MAX_GROUPS of them.  Every operand is a
+// HOST array of `groups` device pointers (b_hh may be NULL); strides are shared.  x3 == false: w_inv is ignored.  The single-expert entry
+// points (`single`) pass arrays of one and may give the carried state and the training saves
+static int attn_decoder_fwd(const char* who, bool x3, bool single, const void* const* Hb, const void* const* Hproj,
+                            const void* const* eproj, int64_t eproj_stride_b, int64_t eproj_stride_s, const void* const* w_h2h,
+                            const void* const* b_h2h, const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                            const void* const* w_inv, const void* const* b_hh, const void* const* hid, int64_t hid_stride_b,
+                            int64_t hid_stride_s, float* h_state, float* c_state, float* alpha_out, float* gates_out, float* c_out,
+                            float* ctx_out, float* hp_out, int groups, int B, int T, int D, int S, int hidden, void* stream) {
+  auto given = [&](int g) {
+    return Hb[g] && Hproj[g] && eproj[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) && hid[g];
+  };
+  MRN_CHECK_ARG(Hb && Hproj && eproj && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && (!x3 || w_inv) && hid && groups >= 1 &&
+                    (!single || given(0)), "%s: null operand", who);
+  MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
+  MRN_CHECK_ARG(D % (x3 ? 32 : 16) == 0 && D > 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
+  MRN_CHECK_ARG((h_state == nullptr) == (c_state == nullptr), "%s: h_state/c_state must come together", who);
+  if (B == 0 || S == 0) return MRN_OK;
+  MRN_CHECK_ARG(!gates_out || (c_out && ctx_out && hp_out && alpha_out), "%s: training saves must all be given", who);
+  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
+    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
+    AttnDecGroup grp;
+    memset(&grp, 0, sizeof(grp));
+    for (int i = 0; i < n; ++i) {
+      const int g = g0 + i;
+      MRN_CHECK_ARG(given(g), "%s: null operand in group %d", who, g);
+      AttnDecParams& p = grp.g[i];
+      p.Hb = (const float*)Hb[g]; p.Hproj = (const float*)Hproj[g]; p.eproj = (const float*)eproj[g];
+      p.w_h2h = (const float*)w_h2h[g]; p.b_h2h = (const float*)b_h2h[g]; p.w_score = (const float*)w_score[g];
+      p.w_ih = (const float*)w_ih_ctx[g]; p.w_hh = (const float*)w_hh[g]; p.b_hh = b_hh ? (const float*)b_hh[g] : nullptr;
+      p.w_inv = x3 ? (const float*)w_inv[g] : nullptr;
+      p.hid = (float*)hid[g];
+      p.B = B; p.T = T; p.D = D; p.S = S;
+      p.eproj_stride_b = eproj_stride_b; p.eproj_stride_s = eproj_stride_s;
+      p.hid_stride_b = hid_stride_b; p.hid_stride_s = hid_stride_s;
+      p.h_state = h_state; p.c_state = c_state;
+      p.alpha_out = alpha_out; p.gates_out = gates_out; p.c_out = c_out; p.ctx_out = ctx_out; p.hp_out = hp_out;
+    }
+    const int rc = attn_launch(grp, n, D, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   return MRN_OK;
 }
 
@@ -1955,21 +1639,10 @@ MRN_EXPORT int mrn_attn_decoder_fwd_f32(const float* Hb, const float* Hproj, con
                                         const float* b_hh, float* hid, int64_t hid_stride_b, int64_t hid_stride_s, float* h_state,
                                         float* c_state, float* alpha_out, float* gates_out, float* c_out, float* ctx_out,
                                         float* hp_out, int B, int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && eproj && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && hid, "mrn_attn_decoder_fwd_f32: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_attn_decoder_fwd_f32: hidden=%d unsupported (library is built for %d)", hidden, HID);
-  MRN_CHECK_ARG(D % 16 == 0 && D > 0, "mrn_attn_decoder_fwd_f32: D=%d must be a multiple of 16", D);
-  MRN_CHECK_ARG((h_state == nullptr) == (c_state == nullptr), "mrn_attn_decoder_fwd_f32: h_state/c_state must come together");
-  if (B == 0 || S == 0) return MRN_OK;
-  MRN_CHECK_ARG(!gates_out || (c_out && ctx_out && hp_out && alpha_out), "mrn_attn_decoder_fwd_f32: training saves must all be given");
-  AttnDecGroup grp;
-  memset(&grp, 0, sizeof(grp));
-  AttnDecParams& p = grp.g[0];
-  attn_fill(p, Hb, Hproj, eproj, eproj_stride_b, eproj_stride_s, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, hid, hid_stride_b,
-            hid_stride_s, B, T, D, S);
-  p.h_state = h_state; p.c_state = c_state;
-  p.alpha_out = alpha_out; p.gates_out = gates_out; p.c_out = c_out; p.ctx_out = ctx_out; p.hp_out = hp_out;
-  grp.tiles = ceil_div(B, BT);
-  return attn_launch(grp, 1, D, T, (hipStream_t)stream);
+  const void* const a[] = {Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, hid};
+  return attn_decoder_fwd("mrn_attn_decoder_fwd_f32", false, true, a, a + 1, a + 2, eproj_stride_b, eproj_stride_s, a + 3, a + 4, a + 5,
+                          a + 6, a + 7, nullptr, a + 8, a + 9, hid_stride_b, hid_stride_s, h_state, c_state, alpha_out, gates_out, c_out,
+                          ctx_out, hp_out, 1, B, T, D, S, hidden, stream);
 }
 
 // Teacher-forced decoders of `groups` experts (identical geometry) in one launch.  Every pointer argument is a HOST
@@ -1980,28 +1653,9 @@ MRN_EXPORT int mrn_attn_decoder_fwd_grouped_f32(const void* const* Hb, const voi
                                                 const void* const* w_ih_ctx, const void* const* w_hh, const void* const* b_hh,
                                                 const void* const* hid, int64_t hid_stride_b, int64_t hid_stride_s, int groups,
                                                 int B, int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && eproj && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && hid && groups >= 1,
-                "mrn_attn_decoder_fwd_grouped_f32: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_attn_decoder_fwd_grouped_f32: hidden=%d unsupported (library is built for %d)", hidden, HID);
-  MRN_CHECK_ARG(D % 16 == 0 && D > 0, "mrn_attn_decoder_fwd_grouped_f32: D=%d must be a multiple of 16", D);
-  if (B == 0 || S == 0) return MRN_OK;
-  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-    AttnDecGroup grp;
-    memset(&grp, 0, sizeof(grp));
-    for (int i = 0; i < n; ++i) {
-      const int g = g0 + i;
-      MRN_CHECK_ARG(Hb[g] && Hproj[g] && eproj[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && hid[g],
-                    "mrn_attn_decoder_fwd_grouped_f32: null operand in group %d", g);
-      attn_fill(grp.g[i], (const float*)Hb[g], (const float*)Hproj[g], (const float*)eproj[g], eproj_stride_b, eproj_stride_s,
-                (const float*)w_h2h[g], (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g],
-                (const float*)w_hh[g], b_hh ? (const float*)b_hh[g] : nullptr, (float*)hid[g], hid_stride_b, hid_stride_s, B, T, D, S);
-    }
-    grp.tiles = ceil_div(B, BT);
-    const int rc = attn_launch(grp, n, D, T, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return MRN_OK;
+  return attn_decoder_fwd("mrn_attn_decoder_fwd_grouped_f32", false, false, Hb, Hproj, eproj, eproj_stride_b, eproj_stride_s, w_h2h, b_h2h,
+                          w_score, w_ih_ctx, w_hh, nullptr, b_hh, hid, hid_stride_b, hid_stride_s, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, groups, B, T, D, S, hidden, stream);
 }
 
 // The same decoders with the three recurrent products as split-fp16 x3: w_h2h / w_ih_ctx / w_hh are the fragment-major fp16 hi / lo
@@ -2012,22 +1666,10 @@ MRN_EXPORT int mrn_attn_decoder_fwd_x3(const float* Hb, const float* Hproj, cons
                                        int64_t hid_stride_b, int64_t hid_stride_s, float* h_state, float* c_state, float* alpha_out,
                                        float* gates_out, float* c_out, float* ctx_out, float* hp_out, int B, int T, int D, int S,
                                        int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && eproj && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && hid, "mrn_attn_decoder_fwd_x3: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_attn_decoder_fwd_x3: hidden=%d unsupported (library is built for %d)", hidden, HID);
-  MRN_CHECK_ARG(D % 32 == 0 && D > 0, "mrn_attn_decoder_fwd_x3: D=%d must be a multiple of 32", D);
-  MRN_CHECK_ARG((h_state == nullptr) == (c_state == nullptr), "mrn_attn_decoder_fwd_x3: h_state/c_state must come together");
-  if (B == 0 || S == 0) return MRN_OK;
-  MRN_CHECK_ARG(!gates_out || (c_out && ctx_out && hp_out && alpha_out), "mrn_attn_decoder_fwd_x3: training saves must all be given");
-  AttnDecGroup grp;
-  memset(&grp, 0, sizeof(grp));
-  AttnDecParams& p = grp.g[0];
-  attn_fill(p, Hb, Hproj, eproj, eproj_stride_b, eproj_stride_s, (const float*)w_h2h, b_h2h, w_score, (const float*)w_ih_ctx,
-            (const float*)w_hh, b_hh, hid, hid_stride_b, hid_stride_s, B, T, D, S);
-  p.w_inv = w_inv;
-  p.h_state = h_state; p.c_state = c_state;
-  p.alpha_out = alpha_out; p.gates_out = gates_out; p.c_out = c_out; p.ctx_out = ctx_out; p.hp_out = hp_out;
-  grp.tiles = ceil_div(B, BT);
-  return attn_launch(grp, 1, D, T, (hipStream_t)stream);
+  const void* const a[] = {Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, hid};
+  return attn_decoder_fwd("mrn_attn_decoder_fwd_x3", true, true, a, a + 1, a + 2, eproj_stride_b, eproj_stride_s, a + 3, a + 4, a + 5,
+                          a + 6, a + 7, a + 8, a + 9, a + 10, hid_stride_b, hid_stride_s, h_state, c_state, alpha_out, gates_out, c_out,
+                          ctx_out, hp_out, 1, B, T, D, S, hidden, stream);
 }
 
 MRN_EXPORT int mrn_attn_decoder_fwd_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* eproj,
@@ -2036,39 +1678,12 @@ MRN_EXPORT int mrn_attn_decoder_fwd_x3_grouped(const void* const* Hb, const void
                                                const void* const* w_hh, const void* const* w_inv, const void* const* b_hh,
                                                const void* const* hid, int64_t hid_stride_b, int64_t hid_stride_s, int groups, int B,
                                                int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && eproj && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && hid && groups >= 1,
-                "mrn_attn_decoder_fwd_x3_grouped: null operand");
-  MRN_CHECK_ARG(hidden == HID, "mrn_attn_decoder_fwd_x3_grouped: hidden=%d unsupported (library is built for %d)", hidden, HID);
-  MRN_CHECK_ARG(D % 32 == 0 && D > 0, "mrn_attn_decoder_fwd_x3_grouped: D=%d must be a multiple of 32", D);
-  if (B == 0 || S == 0) return MRN_OK;
-  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-    AttnDecGroup grp;
-    memset(&grp, 0, sizeof(grp));
-    for (int i = 0; i < n; ++i) {
-      const int g = g0 + i;
-      MRN_CHECK_ARG(Hb[g] && Hproj[g] && eproj[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && w_inv[g] && hid[g],
-                    "mrn_attn_decoder_fwd_x3_grouped: null operand in group %d", g);
-      attn_fill(grp.g[i], (const float*)Hb[g], (const float*)Hproj[g], (const float*)eproj[g], eproj_stride_b, eproj_stride_s,
-                (const float*)w_h2h[g], (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g],
-                (const float*)w_hh[g], b_hh ? (const float*)b_hh[g] : nullptr, (float*)hid[g], hid_stride_b, hid_stride_s, B, T, D, S);
-      grp.g[i].w_inv = (const float*)w_inv[g];
-    }
-    grp.tiles = ceil_div(B, BT);
-    const int rc = attn_launch(grp, n, D, T, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return MRN_OK;
+  return attn_decoder_fwd("mrn_attn_decoder_fwd_x3_grouped", true, false, Hb, Hproj, eproj, eproj_stride_b, eproj_stride_s, w_h2h, b_h2h,
+                          w_score, w_ih_ctx, w_hh, w_inv, b_hh, hid, hid_stride_b, hid_stride_s, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, groups, B, T, D, S, hidden, stream);
 }
 
 // ---- greedy decoding: attn_greedy_kernel ----------------------------------------------------------------
-template <bool X3, bool WIDE>
-static void greedy_kernel_launch(const GreedyGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    hipFuncSetAttribute((const void*)attn_greedy_kernel<X3, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_greedy_kernel<X3, WIDE>), grid, dim3(NTH), lds, st, grp);
-}
-
 static int greedy_launch(GreedyGroup& grp, int groups, int D, int T, hipStream_t st) {
   grp.groups = groups;
   const int B = grp.g[0].a.B;
@@ -2076,37 +1691,24 @@ static int greedy_launch(GreedyGroup& grp, int groups, int D, int T, hipStream_t
   // samples' Hproj / Hb slices, so fewer, fuller workgroups cut that stream and lengthen the dependent chain.  Measured (B = 256, T = 65,
   // S = 26, ms per launch at 2 / 4 / 8 / 16 samples, tools/bench_greedy.py --vb-sweep): one expert of 2091 classes 1.93 / 2.14 / 2.53 /
   // 3.43, of 5374 classes 2.92 / 3.19 / 3.61 / 4.53, six experts 8.40 / 5.91 / 4.71 / 5.60 -- the chain wins until the launch no longer
-  // fits one round of workgroups, so the rule is attn_launch's: the fewest samples (from two) that keep the launch within 256
-  // workgroups.  MRN_GREEDY_VB (2, 4, 8, 16; read per launch) overrides it for tests and sweeps
-  grp.vb = BT;
-  for (int v = 2; v < BT; v *= 2)
-    if ((long)groups * ceil_div(B, v) <= 256) { grp.vb = v; break; }
+  // fits one round of workgroups, so the rule is attn_launch's (attn_vb).  MRN_GREEDY_VB (2, 4, 8, 16; read per launch) overrides it for
+  // tests and sweeps
+  grp.vb = attn_vb(groups, B);
   const char* fvb = getenv("MRN_GREEDY_VB");
   if (fvb) {
     const int v = atoi(fvb);
     if (v == 2 || v == 4 || v == 8 || v == 16) grp.vb = v;
   }
   grp.tiles = ceil_div(B, grp.vb);
-  grp.pinned = groups > 1 && grp.tiles * ceil_div(groups, 8) <= 32;
-  if (groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
+  const dim3 grid = attn_grid(groups, grp.tiles, true, grp.pinned);
   const bool x3 = grp.g[0].a.w_inv != nullptr;
-  // the LDS of attn_launch plus the tokens and the argmax pairs; the WIDE form wherever the whole-context form with that extra passes
-  // 160 KiB, or under MRN_ATTN_CTX_CHUNK=1 (read per launch).  ops.attn_greedy_whole_context restates the rule
-  auto lds_for = [&](int dc) {
-    return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + GREEDY_LDS_EXTRA;
-  };
+  // the WIDE form wherever the whole-context tile with the tokens and the argmax pairs passes 160 KiB, or under MRN_ATTN_CTX_CHUNK=1
+  // (read per launch).  ops.attn_greedy_whole_context restates the rule
   const char* force = getenv("MRN_ATTN_CTX_CHUNK");
-  const bool wide = lds_for(D) > 160 * 1024 || (force && atoi(force) == 1);
-  const size_t lds = lds_for(wide ? CTX_CHUNK : D);
+  const bool wide = attn_tile_lds(x3, D, T, GREEDY_LDS_EXTRA) > 160 * 1024 || (force && atoi(force) == 1);
+  const size_t lds = attn_tile_lds(x3, wide ? CTX_CHUNK : D, T, GREEDY_LDS_EXTRA);
   MRN_CHECK_ARG(lds <= 160 * 1024, "mrn_attn_greedy_decode: LDS budget exceeded (D=%d T=%d)", D, T);
-  const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
-  if (x3) {
-    if (wide) greedy_kernel_launch<true, true>(grp, grid, lds, st);
-    else greedy_kernel_launch<true, false>(grp, grid, lds, st);
-  } else {
-    if (wide) greedy_kernel_launch<false, true>(grp, grid, lds, st);
-    else greedy_kernel_launch<false, false>(grp, grid, lds, st);
-  }
+  attn_kernel_launch(MRN_ATTN_FORM(attn_greedy_kernel, x3, wide), grp, grid, lds, st);
   MRN_LAUNCH_CHECK("attn_greedy");
   return MRN_OK;
 }
@@ -2238,29 +1840,16 @@ MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, cons
 }
 
 // ---- beam-search decoding on the attention head: attn_beam_kernel (include/mrn_attn_beam.h) ----------------
-template <bool X3>
-static void beam_kernel_launch(const BeamGroup& grp, dim3 grid, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    hipFuncSetAttribute((const void*)attn_beam_kernel<X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_beam_kernel<X3>), grid, dim3(NTH), lds, st, grp);
-}
-
-// the whole-context tile of greedy_launch plus the beam state; there is no chunked form (ops.attn_beam_whole_context restates the sum)
-static size_t beam_lds(bool x3, int D, int T) {
-  return sizeof(float) * (2 * BT * HLD + BT * (D + 4) + BT * T + HID) + (x3 ? 1024 : 0) + BEAM_LDS_EXTRA;
-}
-
+// the whole-context tile plus the beam state (BEAM_LDS_EXTRA); there is no chunked form
 static int beam_launch(BeamGroup& grp, int groups, int D, int T, hipStream_t st) {
   grp.groups = groups;
   const int B = grp.g[0].g.a.B;
   grp.tiles = ceil_div(B, BT / grp.W);       // 16 / W samples per workgroup
-  grp.pinned = groups > 1 && grp.tiles * ceil_div(groups, 8) <= 32;
-  if (groups > 1 && (groups * grp.tiles) % 8 == 0 && groups * grp.tiles <= 256) grp.pinned = 2;
+  const dim3 grid = attn_grid(groups, grp.tiles, true, grp.pinned);
   const bool x3 = grp.g[0].g.a.w_inv != nullptr;
-  const size_t lds = beam_lds(x3, D, T);
-  const dim3 grid(grp.pinned == 1 ? 8 * ceil_div(groups, 8) * grp.tiles : groups * grp.tiles);
-  if (x3) beam_kernel_launch<true>(grp, grid, lds, st);
-  else beam_kernel_launch<false>(grp, grid, lds, st);
+  const size_t lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA);
+  if (x3) attn_kernel_launch(attn_beam_kernel<true>, grp, grid, lds, st);
+  else attn_kernel_launch(attn_beam_kernel<false>, grp, grid, lds, st);
   MRN_LAUNCH_CHECK("attn_beam");
   return MRN_OK;
 }
@@ -2281,7 +1870,7 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
   MRN_CHECK_ARG(S >= 1 && S <= 512, "%s: S=%d steps outside 1 ... 512", who, S);
   MRN_CHECK_ARG(D > 0 && D % (x3 ? 32 : 16) == 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
   MRN_CHECK_ARG(B >= 0 && T > 0, "%s: bad geometry (B=%d T=%d)", who, B, T);
-  MRN_CHECK_ARG(beam_lds(x3, D, T) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+  MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
   const long tiles = ceil_div(B, BT / W);
   for (int g = 0; g < groups; ++g) {
     MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&

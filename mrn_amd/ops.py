@@ -1411,7 +1411,7 @@ DECODER_X3 = os.environ.get("MRN_DECODER_X3", "1") == "1"     # attention decode
 
 def attn_decoder_whole_context(D, T, x3=None):
     """does the decoder forward hold a 16-sample tile's whole [16, D] context in LDS (its single-launch form) for T frames, or does it
-    take the chunked WIDE form -- the rule of csrc/rnn.hip attn_launch, restated for callers and tests: 4 * (2 * 16 * 260 + 16 * (D + 4)
+    take the chunked WIDE form -- the rule of csrc/rnn.hip attn_launch (attn_tile_lds), restated for callers and tests: 4 * (2 * 16 * 260 + 16 * (D + 4)
     + 16 * T + 256) bytes (+ 1024 in the x3 form) within 160 KiB.  DERNet's D = 256 * G fits up to G = 7 at every supported width
     (T <= 129), as at T = 65."""
     x3 = DECODER_X3 if x3 is None else x3
@@ -1517,7 +1517,7 @@ ATTN_BEAM_LDS_EXTRA = 4 * (8 * 16 + 3 * 16 * 16)      # attn_beam_kernel: eight 
 
 
 def attn_beam_whole_context(D, T, W, x3=None):
-    """does the fused beam decoder (csrc/rnn.hip beam_lds / beam_grouped) take D context columns, T frames and beam width W: the
+    """does the fused beam decoder (csrc/rnn.hip beam_launch / beam_grouped) take D context columns, T frames and beam width W: the
     whole-context tile of attn_greedy_whole_context with ATTN_BEAM_LDS_EXTRA bytes in place of the arg-max pairs within 160 KiB (the 16
     rows are 16 // W samples x W entries, so the tile does not grow with W), 1 <= W <= 16, D a multiple of 16 (32 in the x3 form).  There
     is no chunked form: what does not fit is decoded stepwise (Attention.beam_search)"""

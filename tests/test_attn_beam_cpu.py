@@ -200,14 +200,19 @@ def test_entry_points_are_declared_bound_exported_and_cited():
 
 
 def test_rule_matches_the_launch_helper():
-    """ops.attn_beam_whole_context restates beam_lds of csrc/rnn.hip and the limits beam_grouped checks before any launch"""
+    """ops.attn_beam_whole_context restates the beam launch's LDS sum in csrc/rnn.hip (the tile of attn_tile_lds, the three decoder
+    kernels' one definition, at dc = D plus BEAM_LDS_EXTRA) and the limits beam_grouped checks before any launch"""
     from mrn_amd import ops
     src = open(os.path.join(ROOT, "mrn_amd", "csrc", "rnn.hip")).read()
-    flat = re.sub(r"\s+", " ", src[src.index("static size_t beam_lds("):src.index("static int beam_launch(")])
-    assert "sizeof(float) * (2 * BT * HLD + BT * (D + 4) + BT * T + HID) + (x3 ? 1024 : 0) + BEAM_LDS_EXTRA" in flat
+    flat = re.sub(r"\s+", " ", src[src.index("static size_t attn_tile_lds("):src.index("static dim3 attn_grid(")])
+    assert "(bool x3, int dc, int T, size_t extra)" in flat
+    assert "sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra" in flat
+    launch = re.sub(r"\s+", " ", src[src.index("static int beam_launch("):src.index("static int beam_grouped(")])
+    assert "lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA)" in launch and "CTX_CHUNK" not in launch
     body = re.sub(r"\s+", " ", src[src.index("static int beam_grouped("):src.index("MRN_EXPORT int mrn_attn_beam_decode_grouped_f32")])
-    assert "beam_lds(x3, D, T) <= 160 * 1024" in body and "W >= 1 && W <= BT" in body and "S >= 1 && S <= 512" in body
-    assert body.index("beam_lds(x3, D, T) <= 160 * 1024") < body.index("beam_launch(")      # refused before the first launch
+    fits = "attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) <= 160 * 1024"
+    assert fits in body and "W >= 1 && W <= BT" in body and "S >= 1 && S <= 512" in body
+    assert body.index(fits) < body.index("beam_launch(")      # refused before the first launch
     consts = dict(re.findall(r"(?m)^constexpr int (\w+) = ([^;]+);", src))
     assert re.sub(r"\s+", " ", consts["BEAM_LDS_EXTRA"]).strip() == "4 * (8 * BT + 3 * BT * BT)"
     assert ops.ATTN_BEAM_LDS_EXTRA == 4 * (8 * 16 + 3 * 16 * 16) == 3584

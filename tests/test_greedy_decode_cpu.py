@@ -39,12 +39,17 @@ def test_whole_context_rule_over_widths_and_task_counts():
 
 
 def test_rule_matches_the_launch_helper():
-    """the terms of greedy_launch's budget in csrc/rnn.hip are the ones ops.attn_greedy_whole_context restates"""
+    """the terms of greedy_launch's budget in csrc/rnn.hip (the tile of attn_tile_lds, the three decoder kernels' one definition, plus
+    GREEDY_LDS_EXTRA) are the ones ops.attn_greedy_whole_context restates"""
     src = _source()
+    tile = re.sub(r"\s+", " ", src[src.index("static size_t attn_tile_lds("):src.index("static dim3 attn_grid(")])
+    assert "(bool x3, int dc, int T, size_t extra)" in tile
+    assert "sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra" in tile
     body = src[src.index("static int greedy_launch("):src.index("static void greedy_fill(")]
     flat = re.sub(r"\s+", " ", body)
-    assert "sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + GREEDY_LDS_EXTRA" in flat
-    assert "lds_for(D) > 160 * 1024" in flat and 'getenv("MRN_ATTN_CTX_CHUNK")' in flat and 'getenv("MRN_GREEDY_VB")' in flat
+    assert "attn_tile_lds(x3, wide ? CTX_CHUNK : D, T, GREEDY_LDS_EXTRA)" in flat and "lds <= 160 * 1024" in flat
+    assert "attn_tile_lds(x3, D, T, GREEDY_LDS_EXTRA) > 160 * 1024" in flat
+    assert 'getenv("MRN_ATTN_CTX_CHUNK")' in flat and 'getenv("MRN_GREEDY_VB")' in flat
     assert "static const" not in body                                # both switches are read per launch
     consts = dict(re.findall(r"(?m)^constexpr int (\w+) = ([^;]+);", src))
     assert consts["BT"].strip() == "16" and consts["NW"].strip() == "16" and consts["HID"].strip() == "256"
