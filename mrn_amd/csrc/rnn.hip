@@ -1191,8 +1191,29 @@ constexpr int BEAM_LDS_EXTRA = 4 * (8 * BT + 3 * BT * BT);   // token, score, fi
 
 __device__ __forceinline__ bool beam_before(float va, int ia, float vb_, int ib) { return va > vb_ || (va == vb_ && ia < ib); }
 
-template <bool X3>
-__global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
+// Lexicon-constrained beam search (attn_lexicon_kernel, include/mrn_attn_lexicon.h): the beam search walked along a trie of the
+// lexicon, one trie for all experts of a launch.  Node 0 is the root; the children of node n are the edges child_off[n] ...
+// child_off[n + 1] - 1 with class child_tok[e] and node child_node[e]; word_of[n] >= 0 where a word ends.  What differs from the beam:
+//   a node id per row in LDS (0 at the start, the chosen child's in (10); a finished or dead row keeps its node)
+//   (8) the log-sum-exp is over all C classes as before; the W best are taken among the row's ADMISSIBLE candidates only: the
+//       children of its node whose class is inside the expert's C classes (the guard is the bounds check of the scratch row), and eos
+//       where a word ends at the node.  Same order, same exclusion of the pairs already taken, same NaN rule; the child node travels
+//       with (value, class) through the wave reduction into a fourth candidate plane
+//   (9) also writes the next node; the tail also writes word [B][W] = word_of of the entry's node, -1 for a dead slot
+// The host checks the arrays once per lexicon (ops.upload_trie): every child_node and every node id a row can hold is inside the arrays
+struct LexTrie {
+  const int32_t* child_off;         // [nodes + 1]
+  const int32_t* child_tok;         // [nodes - 1]
+  const int32_t* child_node;        // [nodes - 1]
+  const int32_t* word_of;           // [nodes]
+  int32_t* word[MAX_GROUPS];        // per group [B][W]
+  int nodes;
+};
+constexpr int LEX_LDS_MORE = 4 * (2 * BT + BT * BT);         // the node row, its next-step twin and the candidate-node plane
+
+// the body of attn_beam_kernel (LEX = false: `lex` is not read) and attn_lexicon_kernel (LEX = true)
+template <bool X3, bool LEX>
+__device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTrie* lex) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int gi, tile_;
   group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
@@ -1217,6 +1238,9 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
   float* cand_v = reinterpret_cast<float*>(flag_lds + BT);
   int* cand_c = reinterpret_cast<int*>(cand_v + BT * BT);
   float* cand_lp = reinterpret_cast<float*>(cand_c + BT * BT);
+  int* node_lds = reinterpret_cast<int*>(cand_lp + BT * BT);      // LEX only: LEX_LDS_MORE
+  int* nnode = node_lds + BT;
+  int* cand_n = nnode + BT;
   const int b0 = v.b0, Bend = v.Bend, nrows = v.nrows, t_ = v.t_, lane = v.lane, wave = v.wave, rbase = v.rbase, j = v.j;
   float* const row_scr = bp.scratch + (long)tile_ * BT * (CP + 3 * S);      // [16][CP]
   int* const hist_par = reinterpret_cast<int*>(row_scr + (long)BT * CP);   // [S][16]
@@ -1228,6 +1252,7 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
     tok_lds[t_] = (k >= C || k < 0) ? 0 : (int)k;
     score_lds[t_] = (t_ < nrows && t_ % W == 0 && b0 + t_ / W < Bend) ? 0.f : -INFINITY;      // one live entry per sample
     fin_lds[t_] = 0;
+    if constexpr (LEX) node_lds[t_] = 0;
   }
   float c[4] = {0.f, 0.f, 0.f, 0.f};
   __syncthreads();
@@ -1260,17 +1285,21 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
         cand_v[row * BT + lane] = -INFINITY;
         cand_c[row * BT + lane] = 0x7fffffff;
         cand_lp[row * BT + lane] = 0.f;
+        if constexpr (LEX) cand_n[row * BT + lane] = 0;
       }
+      const int node = LEX ? node_lds[row] : 0;
       if (lane == 0) {                       // the next step's row, dead until (9) fills it
         nsc[row] = -INFINITY;
         npar[row] = row;
         ntok[row] = eos;
         nlp[row] = 0.f;
+        if constexpr (LEX) nnode[row] = node;
       }
       if (live && fin_lds[row]) {
         if (lane == 0) {
           cand_v[row * BT] = sc;
           cand_c[row * BT] = eos;
+          if constexpr (LEX) cand_n[row * BT] = node;
         }
       } else if (live) {
         const float* x = row_scr + (long)row * CP;
@@ -1289,24 +1318,57 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
         const float lse = m + logf(sum);
         float pv = INFINITY;
         int pc = -1;
+        int e0 = 0, e1 = 0;                   // LEX: the node's edges, and whether a word ends here
+        bool ends = false;
+        if constexpr (LEX) {
+          e0 = lex->child_off[node];
+          e1 = lex->child_off[node + 1];
+          ends = lex->word_of[node] >= 0;
+        }
         for (int q = 0; q < W; ++q) {
           float bv = -INFINITY;
           int bc = 0x7fffffff;
-          for (int k = lane; k < C; k += 64) {
-            float v = x[k];
-            v = v == v ? v : -INFINITY;
-            if ((v < pv || (v == pv && k > pc)) && beam_before(v, k, bv, bc)) {
-              bv = v;
-              bc = k;
+          int bn = 0;
+          if constexpr (LEX) {
+            for (int e = e0 + lane; e < e1; e += 64) {
+              const int k = lex->child_tok[e];
+              if (k < 0 || k >= C) continue;          // a class this expert does not have: outside its scratch row
+              float v = x[k];
+              v = v == v ? v : -INFINITY;
+              if ((v < pv || (v == pv && k > pc)) && beam_before(v, k, bv, bc)) {
+                bv = v;
+                bc = k;
+                bn = lex->child_node[e];
+              }
+            }
+            if (ends && lane == 0) {                  // the one virtual candidate: the word ends, the entry stays at its node
+              float v = x[eos];
+              v = v == v ? v : -INFINITY;
+              if ((v < pv || (v == pv && eos > pc)) && beam_before(v, eos, bv, bc)) {
+                bv = v;
+                bc = eos;
+                bn = node;
+              }
+            }
+          } else {
+            for (int k = lane; k < C; k += 64) {
+              float v = x[k];
+              v = v == v ? v : -INFINITY;
+              if ((v < pv || (v == pv && k > pc)) && beam_before(v, k, bv, bc)) {
+                bv = v;
+                bc = k;
+              }
             }
           }
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o);
             const int oc = __shfl_xor(bc, o);
+            const int on = LEX ? __shfl_xor(bn, o) : 0;
             if (beam_before(ov, oc, bv, bc)) {
               bv = ov;
               bc = oc;
+              bn = on;
             }
           }
           if (bc >= C) break;                 // fewer than W classes
@@ -1316,6 +1378,7 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
             cand_v[row * BT + q] = cv == cv ? cv : -INFINITY;
             cand_c[row * BT + q] = bc;
             cand_lp[row * BT + q] = lp;
+            if constexpr (LEX) cand_n[row * BT + q] = bn;
           }
           pv = bv;
           pc = bc;
@@ -1343,6 +1406,7 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
             npar[r0 + rank] = row;
             ntok[r0 + rank] = cc;
             nlp[r0 + rank] = cand_lp[t_];
+            if constexpr (LEX) nnode[r0 + rank] = cand_n[t_];
           }
         }
       }
@@ -1371,6 +1435,7 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
       score_lds[t_] = v;
       tok_lds[t_] = tk;
       fin_lds[t_] = tk == eos ? 1 : 0;
+      if constexpr (LEX) node_lds[t_] = nnode[t_];
       const unsigned long long open = __ballot(v > -INFINITY && tk != eos);    // (threads 0 ... 15: one wave)
       if (t_ == 0) flag_lds[0] = (open & 0xffffull) != 0 ? 1 : 0;
     }
@@ -1419,8 +1484,19 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
       }
       bp.length[(long)b * W + q] = live ? (first < S ? first + 1 : S) : -1;
       bp.score[(long)b * W + q] = live ? sc : -INFINITY;
+      if constexpr (LEX) lex->word[gi][(long)b * W + q] = live ? lex->word_of[node_lds[row]] : -1;
     }
   }
+}
+
+template <bool X3>
+__global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
+  attn_beam_body<X3, false>(grp, nullptr);
+}
+
+template <bool X3>
+__global__ __launch_bounds__(NTH) void attn_lexicon_kernel(const BeamGroup grp, const LexTrie lex) {
+  attn_beam_body<X3, true>(grp, &lex);
 }
 
 }  // namespace
@@ -1840,14 +1916,25 @@ MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, cons
 }
 
 // ---- beam-search decoding on the attention head: attn_beam_kernel (include/mrn_attn_beam.h) ----------------
-// the whole-context tile plus the beam state (BEAM_LDS_EXTRA); there is no chunked form
-static int beam_launch(BeamGroup& grp, int groups, int D, int T, hipStream_t st) {
+// the whole-context tile plus the beam state (BEAM_LDS_EXTRA); there is no chunked form.  lex: null, or the trie of attn_lexicon_kernel
+// (include/mrn_attn_lexicon.h), whose node rows and candidate-node plane are LEX_LDS_MORE bytes on top
+static int beam_launch(BeamGroup& grp, const LexTrie* lex, int groups, int D, int T, hipStream_t st) {
   grp.groups = groups;
   const int B = grp.g[0].g.a.B;
   grp.tiles = ceil_div(B, BT / grp.W);       // 16 / W samples per workgroup
   const dim3 grid = attn_grid(groups, grp.tiles, true, grp.pinned);
   const bool x3 = grp.g[0].g.a.w_inv != nullptr;
-  const size_t lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA);
+  const size_t lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) + (lex ? LEX_LDS_MORE : 0);
+  if (lex) {
+    if (lds > 64 * 1024) {
+      (void)hipFuncSetAttribute(x3 ? (const void*)attn_lexicon_kernel<true> : (const void*)attn_lexicon_kernel<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    if (x3) hipLaunchKernelGGL(attn_lexicon_kernel<true>, grid, dim3(NTH), lds, st, grp, *lex);
+    else hipLaunchKernelGGL(attn_lexicon_kernel<false>, grid, dim3(NTH), lds, st, grp, *lex);
+    MRN_LAUNCH_CHECK("attn_lexicon");
+    return MRN_OK;
+  }
   if (x3) attn_kernel_launch(attn_beam_kernel<true>, grp, grid, lds, st);
   else attn_kernel_launch(attn_beam_kernel<false>, grp, grid, lds, st);
   MRN_LAUNCH_CHECK("attn_beam");
@@ -1862,7 +1949,9 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
                         const void* const* w_gen, const void* const* b_gen, const int* num_class, int eos, int W,
                         const void* const* scratch, int64_t scratch_floats, const void* const* tokens, const void* const* length,
                         const void* const* score, const void* const* logp, const void* const* path, const void* const* prob,
-                        int groups, int B, int T, int D, int S, int hidden, void* stream) {
+                        int groups, int B, int T, int D, int S, int hidden, void* stream, bool lexicon = false,
+                        const void* child_off = nullptr, const void* child_tok = nullptr, const void* child_node = nullptr,
+                        const void* word_of = nullptr, int nodes = 0, int depth = 0, const void* const* word = nullptr) {
   MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && (!x3 || w_inv) && w_gen && b_gen &&
                     num_class && scratch && tokens && length && score && logp && path && prob && groups >= 1, "%s: null operand", who);
   MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
@@ -1871,6 +1960,14 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
   MRN_CHECK_ARG(D > 0 && D % (x3 ? 32 : 16) == 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
   MRN_CHECK_ARG(B >= 0 && T > 0, "%s: bad geometry (B=%d T=%d)", who, B, T);
   MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+  if (lexicon) {
+    MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA + LEX_LDS_MORE) <= 160 * 1024,
+                  "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+    MRN_CHECK_ARG(child_off && child_tok && child_node && word_of && word, "%s: null trie operand", who);
+    MRN_CHECK_ARG(nodes >= 1, "%s: a trie of nodes=%d (at least the root)", who, nodes);
+    MRN_CHECK_ARG(depth >= 0 && depth <= S - 1, "%s: trie depth=%d outside 0 ... S - 1 = %d (the longest word and its end token take S steps)", who, depth, S - 1);
+    for (int g = 0; g < groups; ++g) MRN_CHECK_ARG(B == 0 || word[g], "%s: null operand in group %d", who, g);
+  }
   const long tiles = ceil_div(B, BT / W);
   for (int g = 0; g < groups; ++g) {
     MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&
@@ -1903,7 +2000,12 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
       bp.path = (int64_t*)path[g];
       bp.prob = (float*)prob[g];
     }
-    const int rc = beam_launch(grp, n, D, T, (hipStream_t)stream);
+    LexTrie lex;
+    if (lexicon) {
+      lex = LexTrie{(const int32_t*)child_off, (const int32_t*)child_tok, (const int32_t*)child_node, (const int32_t*)word_of, {}, nodes};
+      for (int i = 0; i < n; ++i) lex.word[i] = (int32_t*)word[g0 + i];
+    }
+    const int rc = beam_launch(grp, lexicon ? &lex : nullptr, n, D, T, (hipStream_t)stream);
     if (rc) return rc;
   }
   return MRN_OK;
@@ -1934,4 +2036,37 @@ MRN_EXPORT int mrn_attn_beam_decode_x3_grouped(const void* const* Hb, const void
   return beam_grouped("mrn_attn_beam_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv,
                       b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob, groups, B,
                       T, D, S, hidden, stream);
+}
+
+// ---- lexicon-constrained beam search on the attention head: attn_lexicon_kernel (include/mrn_attn_lexicon.h) ----
+MRN_EXPORT int mrn_attn_lexicon_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                   const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                   const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                   const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                                   const int* num_class, int eos, int W, const int32_t* child_off,
+                                                   const int32_t* child_tok, const int32_t* child_node, const int32_t* word_of, int nodes,
+                                                   int depth, const void* const* scratch, int64_t scratch_floats,
+                                                   const void* const* tokens, const void* const* length, const void* const* score,
+                                                   const void* const* logp, const void* const* path, const void* const* prob,
+                                                   const void* const* word, int groups, int B, int T, int D, int S, int hidden,
+                                                   void* stream) {
+  return beam_grouped("mrn_attn_lexicon_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
+                      nullptr, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, B, T, D, S, hidden, stream, true, child_off, child_tok, child_node, word_of, nodes, depth, word);
+}
+
+MRN_EXPORT int mrn_attn_lexicon_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                  const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                  const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                  const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                                  const void* const* b_gen, const int* num_class, int eos, int W,
+                                                  const int32_t* child_off, const int32_t* child_tok, const int32_t* child_node,
+                                                  const int32_t* word_of, int nodes, int depth, const void* const* scratch,
+                                                  int64_t scratch_floats, const void* const* tokens, const void* const* length,
+                                                  const void* const* score, const void* const* logp, const void* const* path,
+                                                  const void* const* prob, const void* const* word, int groups, int B, int T, int D, int S,
+                                                  int hidden, void* stream) {
+  return beam_grouped("mrn_attn_lexicon_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
+                      w_inv, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob, groups,
+                      B, T, D, S, hidden, stream, true, child_off, child_tok, child_node, word_of, nodes, depth, word);
 }

@@ -197,11 +197,17 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
     float32 [B][S]): the outputs of ops.attn_beam_decode, for CPU tensors and as the kernel's yardstick.  Any width >= 1.
     want_margin adds margin float64 [B]: the smallest gap, over the steps, between neighbouring kept candidates and between the last
     kept and the best dropped one, divided by the step's token count (a score of n tokens is known to n times a token's band)"""
+    return _attn_search_host("attn_beam_host", sd, batch_H, sos, eos, width, batch_max_length, None, want_margin)
+
+
+def _attn_search_host(who, sd, batch_H, sos, eos, width, batch_max_length, trie, want_margin):
+    """attn_beam_host (trie None) and attn_lexicon_host (a Trie: the candidates of an unfinished entry are those its node admits, a node
+    id is carried per entry, and `word` is one more output in front of the margin)"""
     W, S = int(width), int(batch_max_length) + 1
     w = {k: _f64(v) for k, v in sd.items()}
     Hb = _f64(batch_H)
     if Hb.ndim != 3 or W < 1 or S < 1:
-        raise ValueError(f"attn_beam_host needs batch_H [B][T][D], width >= 1 and batch_max_length >= 0, got {Hb.shape}, {W}, {S - 1}")
+        raise ValueError(f"{who} needs batch_H [B][T][D], width >= 1 and batch_max_length >= 0, got {Hb.shape}, {W}, {S - 1}")
     B, T, D = Hb.shape
     emb, gen_w, gen_b = w["char_embeddings.weight"], w["generator.weight"], w["generator.bias"]
     C, Hd = gen_w.shape
@@ -218,6 +224,7 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
     logp = np.zeros((B, W, S))
     margin = np.full(B, np.inf)
     rows = np.arange(B)[:, None]
+    node = np.zeros((B, W), dtype=np.int64)
     for s in range(S):
         if not ((score > -np.inf) & ~finished).any():
             break
@@ -240,6 +247,9 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
             cand = score[:, :, None] + lp
         done = np.full((B, W, C), -np.inf)
         done[:, :, eos] = score
+        if trie is not None:
+            admitted, step_to = _admitted(trie, node, C, eos)
+            cand = np.where(admitted, cand, -np.inf)
         cand = np.where(finished[:, :, None], done, cand)
         cand[np.isnan(cand)] = -np.inf
         flat = cand.reshape(B, W * C)                                     # candidate order (i, c)
@@ -262,6 +272,8 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
         logp[:, :, s] = np.where(alive & ~was_done, lp[rows, par, cls], 0.0)
         tokens[~alive], logp[~alive] = eos, 0.0
         h, c = h2[rows, par], c2[rows, par]
+        if trie is not None:                                              # a finished or dead entry keeps its node
+            node = np.where(alive & ~was_done, step_to[rows, par, cls], node[rows, par])
         last = np.where(alive, cls, eos)
         finished = alive & (cls == eos)
         score = new_score
@@ -270,6 +282,8 @@ def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=F
     length = np.where(is_eos.any(axis=2), is_eos.argmax(axis=2) + 1, S).astype(np.int32)
     length[~alive] = -1
     out = (tokens, length, score, logp, tokens[:, 0].astype(np.int64), np.exp(logp[:, 0]).astype(np.float32))
+    if trie is not None:
+        out += (np.where(alive, trie.word_of[node], -1).astype(np.int32),)
     return out + (margin,) if want_margin else out
 
 
@@ -432,3 +446,186 @@ def ctc_lexicon_host(logits, lex_tokens, lex_len, n, cand=None):
         else:
             prob[b, 0] = 0.0
     return index, score, score_all, path, prob
+
+
+# ---- lexicon-constrained decoding on the attention head ------------------------------------------------------------------------------
+# With opt.attn_lexicon (a sequence of words) an attention head is decoded by the beam search above walked along a trie of the lexicon:
+# mrn_attn_lexicon_decode_* (mrn_amd/csrc/rnn.hip attn_lexicon_kernel) runs it in float32, all steps of all experts in one launch,
+# attn_lexicon_host below in float64.  (Scoring every (sample, word) pair, as the CTC lexicon decoder does, would give every pair a
+# recurrent roll-out of its own.)  The trie: node 0 is the root, nodes are numbered breadth-first with a node's children in ascending
+# class order, so the numbering does not depend on the order of the words and a child's index is above its parent's; the children of
+# node n are the edges child_off[n] ... child_off[n + 1] - 1 with class child_tok[e] and node child_node[e]; word_of[n] is the lowest
+# lexicon index of a word that ends at n, else -1.  Every entry carries a node, the start entry the root.  The search is the beam
+# search with step 2 replaced:
+#
+#   2. a live unfinished entry i at node n gives the candidates (i, child_tok[e]) with score_i + lp[child_tok[e]] for the children e
+#      of n whose class is below num_class, and (i, eos) with score_i + lp[eos] if a word ends at n (word_of[n] >= 0); lp is still the
+#      log-softmax over all num_class classes: nothing is renormalised, so a finished entry's score is log p(word, eos | image) of the
+#      model.  A finished entry gives (i, eos) with its score unchanged, as before.  An entry without a candidate contributes nothing.
+#   4. a survivor takes its parent's new (h, c) and the chosen child's node; a finished or dead entry keeps its node.
+#
+# With W >= the number of distinct words nothing is pruned and entry 0 is the exact arg-max over the lexicon.  The longest word must
+# fit: trie.depth <= batch_max_length, and then every live entry ends in eos within the S steps.  A sample may end without a live
+# entry (an expert whose classes stop below every word's first class): path all eos, prob all 1, every length -1, every score -inf.
+# Outputs: the beam's six and word int32 [W] = word_of of the entry's node, -1 for a dead slot.
+from collections import namedtuple
+
+Trie = namedtuple("Trie", "child_off child_tok child_node word_of depth words")      # words: the size of the lexicon word_of indexes
+ATTN_SPECIALS = ("[UNK]", "[PAD]", "[SOS]", "[EOS]")
+
+
+def attn_lexicon_options(opt):
+    """(words or None, width) of an options object: opt.attn_lexicon is absent / None (off) or a sequence of str, the width is
+    opt.beam_width (default 8) whatever attn_decode says: a lexicon makes the search a constrained beam search"""
+    width = _positive_int(opt, "beam_width", DEFAULT_BEAM_WIDTH)
+    words = getattr(opt, "attn_lexicon", None)
+    if words is None:
+        return None, width
+    if isinstance(words, (str, bytes)) or not hasattr(words, "__iter__"):
+        raise ValueError(f"attn_lexicon must be a sequence of words (str), got {type(words).__name__}")
+    words = list(words)
+    for w in words:
+        if not isinstance(w, str):
+            raise ValueError(f"attn_lexicon must be a sequence of words (str), got an entry {w!r}")
+    return words, width
+
+
+def encode_attn_lexicon(converter, words, batch_max_length):
+    """words -> (tokens int32 [N][Lmax] (0 behind a word), lengths int32 [N], kept_words): the words an AttnLabelConverter can spell, in
+    their order, duplicates kept, the empty word too.  A word with a character outside converter.dict, or one of the [UNK] / [PAD] /
+    [SOS] / [EOS] classes, or longer than batch_max_length (its [EOS] would not fit the S = batch_max_length + 1 steps) is dropped;
+    ValueError if nothing is left.  Case-sensitive, like encode_lexicon"""
+    table = converter.dict
+    banned = {table[s] for s in ATTN_SPECIALS if s in table}
+    words = list(words)
+    rows, kept = [], []
+    for w in words:
+        row = [table.get(ch) for ch in w]
+        if len(row) > batch_max_length or any(c is None or c in banned for c in row):
+            continue
+        rows.append(row)
+        kept.append(w)
+    if not kept:
+        raise ValueError(f"attn_lexicon: none of the {len(words)} words can be spelled with the converter's characters within "
+                         f"{batch_max_length} of them")
+    lengths = np.fromiter((len(r) for r in rows), dtype=np.int32, count=len(rows))
+    tokens = np.zeros((len(rows), max(int(lengths.max()), 1)), dtype=np.int32)
+    for i, r in enumerate(rows):
+        tokens[i, :len(r)] = r
+    return tokens, lengths, kept
+
+
+def build_trie(tokens, lengths):
+    """tokens int [N][Lmax], lengths int [N] (N >= 1, classes >= 0) -> Trie of int32 arrays: child_off [M + 1], child_tok [M - 1],
+    child_node [M - 1] in CSR form, word_of [M] (the lowest index of a word ending at the node, else -1), depth = the longest word,
+    words = N.  Nodes are numbered breadth-first, children in ascending class order; level by level over the sorted words, no
+    per-node work"""
+    tokens = np.asarray(tokens).astype(np.int64)
+    lengths = np.asarray(lengths).astype(np.int64)
+    if tokens.ndim != 2 or lengths.shape != tokens.shape[:1] or len(lengths) < 1:
+        raise ValueError(f"build_trie needs tokens [N >= 1][Lmax] and lengths [N], got {tokens.shape}, {lengths.shape}")
+    N, Lmax = tokens.shape
+    if lengths.min() < 0 or lengths.max() > Lmax:
+        raise ValueError(f"build_trie: word lengths outside 0..{Lmax}")
+    used = np.arange(Lmax)[None, :] < lengths[:, None]
+    if (tokens[used] < 0).any():
+        raise ValueError("build_trie: negative class in a word")
+    padded = np.where(used, tokens, -1)
+    depth = int(lengths.max())
+    order = np.lexsort(padded.T[::-1]) if Lmax else np.arange(N)        # the words in lexicographic order, a prefix before its extensions
+    at = np.zeros(N, dtype=np.int64)               # node of every word's prefix of the current length; a word that has ended keeps its node
+    parents, toks = [], []
+    M = 1
+    for d in range(depth):
+        act = order[lengths[order] > d]            # in sorted order (node of the prefix, next class) is non-decreasing: one run per child
+        par, tk = at[act], padded[act, d]
+        new = np.ones(len(act), dtype=bool)
+        new[1:] = (par[1:] != par[:-1]) | (tk[1:] != tk[:-1])
+        at[act] = M + np.cumsum(new) - 1
+        parents.append(par[new])
+        toks.append(tk[new])
+        M += int(new.sum())
+    word_of = np.full(M, N, dtype=np.int64)
+    np.minimum.at(word_of, at, np.arange(N))
+    word_of[word_of == N] = -1
+    parents = np.concatenate(parents) if parents else np.zeros(0, dtype=np.int64)
+    child_tok = np.concatenate(toks) if toks else np.zeros(0, dtype=np.int64)
+    child_off = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(np.bincount(parents, minlength=M), out=child_off[1:])
+    return Trie(child_off.astype(np.int32), child_tok.astype(np.int32), np.arange(1, M, dtype=np.int32), word_of.astype(np.int32),
+                depth, N)
+
+
+def check_trie(trie):
+    """the host check every trie passes once before it is uploaded (ops.upload_trie): the kernel trusts the arrays, so whatever could
+    send a read outside them is a ValueError here -- int32, one-dimensional and contiguous; offsets monotone from 0 to E = M - 1;
+    parent < child_node[e] < M; classes >= 0; -1 <= word_of < words; no path from the root longer than depth.  -> (M, E)"""
+    arrays = {k: getattr(trie, k) for k in ("child_off", "child_tok", "child_node", "word_of")}
+    for k, a in arrays.items():
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"trie: {k} must be a contiguous one-dimensional int32 array")
+    off, tok, child, word_of = arrays.values()
+    M, E = len(word_of), len(tok)
+    depth, words = trie.depth, trie.words
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (depth, words)) or depth < 0 or words < 1:
+        raise ValueError(f"trie: depth={depth!r} and words={words!r} must be integers >= 0 and >= 1")
+    if M < 1 or len(off) != M + 1 or len(child) != E or E != M - 1:
+        raise ValueError(f"trie: {M} nodes need {M + 1} offsets and {M - 1} edges, got {len(off)}, {E} classes and {len(child)} children")
+    if off[0] != 0 or off[-1] != E or (np.diff(off) < 0).any():
+        raise ValueError(f"trie: child_off must rise from 0 to {E}")
+    parent = np.repeat(np.arange(M), np.diff(off))
+    if E and ((child <= parent).any() or (child >= M).any()):
+        raise ValueError(f"trie: child_node must lie between its parent and {M}")
+    if E and tok.min() < 0:
+        raise ValueError("trie: negative class in child_tok")
+    if word_of.min() < -1 or word_of.max() >= words:
+        raise ValueError(f"trie: word_of outside -1..{words - 1}")
+    level = np.zeros(M, dtype=np.int64)             # longest path from the root: a child is above its parent, so depth + 1 sweeps settle it
+    for _ in range(int(depth) + 1):
+        deeper = level.copy()
+        np.maximum.at(deeper, child, level[parent] + 1)
+        if np.array_equal(deeper, level):
+            break
+        level = deeper
+    else:
+        raise ValueError(f"trie: a path from the root is longer than depth={depth}")
+    return M, E
+
+
+def _admitted(trie, node, C, eos):
+    """node int [B][W] -> (admitted bool [B][W][C], step_to int64 [B][W][C]): the classes the entries' nodes admit and the node each
+    leads to, a ragged expand of the CSR rows; eos is admitted where a word ends and leads nowhere"""
+    B, W = node.shape
+    flat = node.reshape(-1)
+    lo = trie.child_off[flat].astype(np.int64)
+    count = trie.child_off[flat + 1] - lo
+    row = np.repeat(np.arange(B * W), count)
+    edge = np.arange(int(count.sum())) - np.repeat(np.cumsum(count) - count, count) + np.repeat(lo, count)
+    cls = trie.child_tok[edge].astype(np.int64)
+    ok = cls < C
+    admitted = np.zeros((B * W, C), dtype=bool)
+    step_to = np.repeat(flat[:, None], C, axis=1)
+    admitted[row[ok], cls[ok]] = True
+    step_to[row[ok], cls[ok]] = trie.child_node[edge[ok]]
+    ends = trie.word_of[flat] >= 0
+    admitted[ends, eos] = True
+    step_to[ends, eos] = flat[ends]
+    return admitted.reshape(B, W, C), step_to.reshape(B, W, C)
+
+
+def attn_lexicon_host(sd, batch_H, sos, eos, width, batch_max_length, trie, want_margin=False):
+    """float64 lexicon-constrained beam search on the attention head: the operands of attn_beam_host and a Trie (build_trie) ->
+    attn_beam_host's six outputs and word int32 [B][W] (word_of of the entry's node, -1 for a dead slot): the outputs of
+    ops.attn_lexicon_decode, for CPU tensors and as the kernel's yardstick.  want_margin adds margin float64 [B] as attn_beam_host
+    does, the gaps taken over admissible candidates only"""
+    check_trie(trie)
+    if trie.depth > int(batch_max_length):
+        raise ValueError(f"attn_lexicon_host: the longest word has {trie.depth} classes, more than batch_max_length={batch_max_length}")
+    return _attn_search_host("attn_lexicon_host", sd, batch_H, sos, eos, width, batch_max_length, trie, want_margin)
+
+
+def attn_lexicon_request(attn_lexicon, width):
+    """the trie handle an evaluation forward constrains its beam search with, or None; without a beam width the handle is an error"""
+    if attn_lexicon is not None and width is None:
+        raise ValueError("attn_lexicon constrains the beam search of attn_beam=<width>: pass both (evaluation under no_grad, attention head)")
+    return attn_lexicon

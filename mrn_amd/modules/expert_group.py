@@ -730,8 +730,9 @@ class HeadsGroup(SequenceGroup):
 
     def run_greedy(self, visual, start, feats_out, logits_out, beam=None):
         """run() for attention experts at evaluation time: start = device int64 tensor whose first element is the start token ([SOS]);
-        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  beam = (width, eos): one more launch
-        for the group on the same features, Hproj and operands (run_beam) -> (path [G,B,S], prob [G,B,S]), else None."""
+        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  beam = (width, eos) or (width, eos,
+        trie handle or None): one more launch for the group on the same features, Hproj and operands (run_beam) -> (path [G,B,S], prob
+        [G,B,S]), with a trie also word [G,B]; else None."""
         G = self.G
         _, B, _, T, Cf = visual.shape
         feat = self.sequence(visual)                                              # [G,B,T,hidden]
@@ -745,15 +746,23 @@ class HeadsGroup(SequenceGroup):
         cols = list(zip(*args))
         ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out,
                                        w_inv=cols[9] if args[0][9] is not None else None)
-        return None if beam is None else self.run_beam(feat, Hproj, start, cols, beam[0], beam[1])
+        return None if beam is None else self.run_beam(feat, Hproj, start, cols, *beam)
 
-    def run_beam(self, feat, Hproj, start, cols, width, eos):
+    def run_beam(self, feat, Hproj, start, cols, width, eos, attn_lexicon=None):
         """beam search of all G attention experts in lock-step: ONE mrn_attn_beam_decode_* launch on run_greedy's features, Hproj and
         greedy_args() columns where every head takes the fused form; else every head's own Attention.beam_search (stepwise)
-        -> (path int64 [G,B,S], prob [G,B,S])"""
+        -> (path int64 [G,B,S], prob [G,B,S]).  attn_lexicon (the handle of ops.upload_trie, one trie for all experts): the same with
+        mrn_attn_lexicon_decode_* / Attention.lexicon_search -> (path, prob, word int32 [G,B])"""
         heads = [e.Prediction for e in self.experts]
         G, B, T, D = feat.shape
         L = self.experts[0].opt.batch_max_length
+        if attn_lexicon is not None:
+            if all(h.lexicon_fused(D, T, L + 1, eos, width, attn_lexicon) for h in heads):
+                res = ops.attn_lexicon_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,
+                                                      attn_lexicon, w_inv=cols[9] if cols[9][0] is not None else None)
+                return res[4], res[5], res[6][:, :, 0]
+            each = [h.lexicon_search(feat[g], start, eos, width, attn_lexicon, L) for g, h in enumerate(heads)]
+            return torch.stack([r[4] for r in each]), torch.stack([r[5] for r in each]), torch.stack([r[6][:, 0] for r in each])
         if all(h.beam_fused(D, T, L + 1, eos, width) for h in heads):
             res = ops.attn_beam_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,
                                                w_inv=cols[9] if cols[9][0] is not None else None)

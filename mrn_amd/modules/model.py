@@ -18,7 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
-from .decoding import ATTN_EOS, attn_beam_request
+from .decoding import ATTN_EOS, attn_beam_request, attn_lexicon_request
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import check_call, frames
@@ -123,13 +123,15 @@ class Model(nn.Module):
             raise Exception("Prediction is neither CTC or Attn")
         self.Prediction.to(device)
 
-    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None):
-        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam)
+    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None):
+        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam, attn_lexicon=attn_lexicon)
 
-    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None):
+    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None):
         """SequenceModeling + Prediction on precomputed backbone features.  attn_beam (a width; attention head, evaluation under
         no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of a beam search on the same features
-        (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's"""
+        (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's.  attn_lexicon (the handle of
+        ops.upload_trie, beside attn_beam): the search is walked along the lexicon's trie, and the dict also has beam_word [B], the
+        lexicon index of the best entry (-1: no word of the lexicon can be spelled)"""
         feat = self.model.sequence(visual, out=feature_out)
         if self.stages["Pred"] == "CTC":
             if needs_grad(self.Prediction, feat):
@@ -140,7 +142,11 @@ class Model(nn.Module):
             pred = self.Prediction(feat, text, is_train, batch_max_length=self.opt.batch_max_length, out=predict_out)
         out = {"predict": pred, "feature": feat}
         width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
-        if width is not None:
+        trie = attn_lexicon_request(attn_lexicon, attn_beam)
+        if width is not None and trie is not None:
+            res = self.Prediction.lexicon_search(feat, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
+            out["beam_path"], out["beam_prob"], out["beam_word"] = res[4], res[5], res[6][:, 0]
+        elif width is not None:
             out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(feat, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
         return out
 
@@ -301,16 +307,22 @@ class DERNet(Model):
             return ops.linear(feat, head.weight, head.bias)
         return head(feat if feat.is_contiguous() else feat.contiguous(), text, is_train, batch_max_length=self.opt.batch_max_length)
 
-    def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None):
-        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam: as Model.heads (the main head's beam pair)"""
+    def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None, attn_lexicon=None):
+        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon: as Model.heads (the main head's beam
+        pair and beam_word)"""
         feat = self._features(image, frozen)
         logits = self._head(self.Prediction, feat, text, is_train)
         aux = self._head(self.aux_Prediction, feat[:, :, -self.out_dim:], text, is_train)
         out = {"logits": logits, "aux_logits": aux, "features": feat}
         width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
+        trie = attn_lexicon_request(attn_lexicon, attn_beam)
         if width is not None:
             rows = feat if feat.is_contiguous() else feat.contiguous()
-            out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(rows, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
+            if trie is not None:
+                res = self.Prediction.lexicon_search(rows, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
+                out["beam_path"], out["beam_prob"], out["beam_word"] = res[4], res[5], res[6][:, 0]
+            else:
+                out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(rows, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
         return out
 
     def update_fc(self, hidden_size, nb_classes, device=None):
@@ -460,29 +472,35 @@ class MRNNet(nn.Module):
                 and HeadsGroup.greedy_supported(list(self.model)))
 
     def _run_heads(self, hg, visual, text, is_train, feats, logits, beam=None, first=0):
-        """beam: None or (width, list that takes (first expert, path [G,B,S], prob [G,B,S]) of the group's beam launch)"""
+        """beam: None or (width, list that takes (first expert, path [G,B,S], prob [G,B,S]) of the group's beam launch, trie handle or
+        None: with a trie the launch is the lexicon-constrained one and the record also has word [G,B])"""
         if self._greedy_heads(is_train):
-            pair = hg.run_greedy(visual, text, feats, logits, beam=None if beam is None else (beam[0], ATTN_EOS))
+            pair = hg.run_greedy(visual, text, feats, logits, beam=None if beam is None else (beam[0], ATTN_EOS, beam[2]))
             if beam is not None:
                 beam[1].append((first,) + pair)
         else:
             hg.run(visual, text, feats, logits)
 
-    def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None):
+    def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None, attn_lexicon=None):
         """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier.
         attn_beam (a width; attention experts, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of
         a beam search (modules/decoding.py) of the expert the hard routing index picks for each sample, for cross=False of the newest
-        expert; one more launch per heads group on the same features, `logits` is still the greedy decoder's"""
+        expert; one more launch per heads group on the same features, `logits` is still the greedy decoder's.  attn_lexicon (the handle
+        of ops.upload_trie, beside attn_beam): the search of every expert is walked along the one trie, and the dict also has beam_word
+        [B], as Model.heads"""
         check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         width = attn_beam_request(attn_beam, self.opt.Prediction, is_train)
+        trie = attn_lexicon_request(attn_lexicon, attn_beam)
+        if width is None:                      # (a CTC head, training: the request is ignored like attn_beam)
+            trie = None
         pair = None
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
-            newest = self.model[-1](image, text, is_train, attn_beam=width)
+            newest = self.model[-1](image, text, is_train, attn_beam=width, attn_lexicon=trie)
             features, index = newest["predict"], None
             if width is not None:
-                pair = (newest["beam_path"], newest["beam_prob"])
+                pair = (newest["beam_path"], newest["beam_prob"]) + ((newest["beam_word"],) if trie is not None else ())
         elif is_train == False:  # noqa: E712
-            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width)
+            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width, attn_lexicon=trie)
             features, index = routed[:2]
             if width is not None:
                 pair = routed[2]
@@ -490,7 +508,9 @@ class MRNNet(nn.Module):
             features, index = self.cross_forward(image, text, is_train, experts=experts)
         out = {"logits": features, "index": index, "aux_logits": None}
         if pair is not None:
-            out["beam_path"], out["beam_prob"] = pair
+            out["beam_path"], out["beam_prob"] = pair[:2]
+            if len(pair) == 3:
+                out["beam_word"] = pair[2]
         return out
 
     # -- shared by both routed paths -------------------------------------------------------------------
@@ -553,7 +573,8 @@ class MRNNet(nn.Module):
             return {"parts": parts, "batch": B, "feats": feats}
 
     def _experts_and_gate(self, image, text, is_train, experts=None, beam=None):
-        """beam: None or (width, empty list): the list takes (first expert, path [G,B,S], prob [G,B,S]) per heads group / expert"""
+        """beam: None or (width, empty list, trie handle or None): the list takes (first expert, path [G,B,S], prob [G,B,S]) per heads
+        group / expert, with a trie also word [G,B]"""
         I = len(self.model)
         B = image.shape[0]
         dev = image.device
@@ -610,23 +631,23 @@ class MRNNet(nn.Module):
                 for i, expert in enumerate(self.model):
                     streams[i].wait_stream(main)
                     with torch.cuda.stream(streams[i]):
-                        kw = {} if beam is None else {"attn_beam": beam[0]}
+                        kw = {} if beam is None else {"attn_beam": beam[0], "attn_lexicon": beam[2]}
                         if visuals is None:
                             res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
                         else:
                             res = expert.heads(visuals[i], text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
                             visuals[i].record_stream(streams[i])
                         if beam is not None:
-                            beam[1].append((i, res["beam_path"].unsqueeze(0), res["beam_prob"].unsqueeze(0)))
+                            beam[1].append(self._beam_part(i, res))
                 for st in streams[:I]:
                     main.wait_stream(st)
                     image.record_stream(st)
             else:
                 for i, expert in enumerate(self.model):
                     res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i],
-                                 **({} if beam is None else {"attn_beam": beam[0]}))
+                                 **({} if beam is None else {"attn_beam": beam[0], "attn_lexicon": beam[2]}))
                     if beam is not None:
-                        beam[1].append((i, res["beam_path"].unsqueeze(0), res["beam_prob"].unsqueeze(0)))
+                        beam[1].append(self._beam_part(i, res))
         r = self.dm_router[0].forward_l2(feats)               # [B,P,I,C]
         r = LinearFn.apply(r.view(B * self.patch, I * self.out_dim), self.channel_route.weight, self.channel_route.bias)
         return logits, r.view(B, self.patch, I)
@@ -640,24 +661,30 @@ class MRNNet(nn.Module):
         w = GateTailFn.apply(r, self.route.weight, self.route.bias, float(self.beta))
         return FaninFn.apply(w, *logits), w
 
-    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None):
+    @staticmethod
+    def _beam_part(i, res):
+        """expert i's record for cross_forward_expert from its own forward's dict"""
+        keys = ("beam_path", "beam_prob") + (("beam_word",) if "beam_word" in res else ())
+        return (i,) + tuple(res[k].unsqueeze(0) for k in keys)
+
+    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None, attn_lexicon=None):
         """-> (the routed expert's logits, the hard routing index); with attn_beam (a width) also the routed expert's beam pair
-        (path, prob) [B,S] as a third value"""
+        (path, prob) [B,S] as a third value, with attn_lexicon (a trie handle) beside it (path, prob, word [B])"""
         with torch.no_grad():
-            beam = None if attn_beam is None else (attn_beam, [])
+            beam = None if attn_beam is None else (attn_beam, [], attn_lexicon_request(attn_lexicon, attn_beam))
             logits, r = self._experts_and_gate(image, text, is_train, beam=beam)
             _, index = ops.gate_tail_fwd(r.contiguous(), self.route.weight.view(-1), self.route.bias, float(self.beta), hard=True)
             pair = None
             if beam is not None:
                 main = torch.cuda.current_stream() if image.is_cuda else None
                 parts = sorted(beam[1], key=lambda p: p[0])
-                for _, path, prob in parts:
+                for part in parts:
                     if main is not None:              # (decoded on a side stream that this stream has waited for)
-                        path.record_stream(main)
-                        prob.record_stream(main)
-                paths, probs = torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])      # [I,B,S]
-                pick, rows = index.view(-1).long(), torch.arange(paths.shape[1], device=paths.device)
-                pair = (paths[pick, rows], probs[pick, rows])
+                        for t in part[1:]:
+                            t.record_stream(main)
+                stacks = [torch.cat(col) for col in list(zip(*parts))[1:]]      # paths, probs [I,B,S] (and words [I,B])
+                pick, rows = index.view(-1).long(), torch.arange(stacks[0].shape[1], device=stacks[0].device)
+                pair = tuple(t[pick, rows] for t in stacks)
             routed = ops.select_expert(logits, index)
             return (routed, index) if beam is None else (routed, index, pair)
 

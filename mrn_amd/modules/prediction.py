@@ -126,7 +126,69 @@ class Attention(nn.Module):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
             return ops.attn_beam_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
                                         self.hidden_size, S, eos, W, w_inv=w_inv)
-        # stepwise: gather, Linear, one decoder step with carried state and the generator on B * W rows; the selection on the sorted candidates
+        return self._search_stepwise(batch_H, Hproj, start, eos, W, S, None)
+
+    def lexicon_fused(self, D, T, S, eos, width, trie):
+        """does lexicon_search take the fused launch (mrn_attn_lexicon_decode_*): beam_fused's limits with the lexicon launch's LDS sum"""
+        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and self.num_class >= 2
+                and 0 <= eos < self.num_class and trie.depth <= S - 1 and ops.attn_lexicon_whole_context(D, T, width, self.x3_ok()))
+
+    @torch.no_grad()
+    def lexicon_search(self, batch_H, sos, eos, width, trie_handle, batch_max_length=25):
+        """beam search of width `width` walked along the trie of a lexicon (modules/decoding.py states the algorithm): the operands of
+        beam_search and the handle of ops.upload_trie -> beam_search's six outputs and word int32 [B,W] (the lexicon index of the
+        entry's word, -1 for a dead slot).  One launch where the kernel's limits and the LDS budget allow, otherwise (or under
+        MRN_ATTN_BEAM=stepwise) beam_search's step loop with the same constraint; CPU tensors go to decoding.attn_lexicon_host"""
+        from .decoding import attn_lexicon_host
+        check_hidden(None, "Attn", self.hidden_size)
+        W, S, eos = int(width), int(batch_max_length) + 1, int(eos)
+        if W < 1 or not 0 <= eos < self.num_class:
+            raise ValueError(f"lexicon_search needs width >= 1 and 0 <= eos < {self.num_class}, got {width}, {eos}")
+        if not isinstance(trie_handle, ops.TrieHandle):
+            raise ValueError(f"lexicon_search needs the handle of ops.upload_trie, got {type(trie_handle).__name__}")
+        if trie_handle.depth > S - 1:
+            raise ValueError(f"lexicon_search: the longest word has {trie_handle.depth} classes, more than batch_max_length={S - 1}")
+        if not batch_H.is_cuda:
+            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
+            res = attn_lexicon_host(self.state_dict(), batch_H, first, eos, W, S - 1, trie_handle.trie)
+            return tuple(torch.from_numpy(r).to(torch.float32) if r.dtype == "float64" else torch.from_numpy(r) for r in res)
+        cell = self.attention_cell
+        B, T, D = batch_H.shape
+        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
+        batch_H = batch_H.contiguous()
+        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        if self.lexicon_fused(D, T, S, eos, W, trie_handle):
+            etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+            return ops.attn_lexicon_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                           self.hidden_size, S, eos, W, trie_handle, w_inv=w_inv)
+        return self._search_stepwise(batch_H, Hproj, start, eos, W, S, trie_handle)
+
+    @staticmethod
+    def _admitted(trie, node, C, eos):
+        """node int64 [B * W] -> (admitted bool [B * W, C], step_to int64 [B * W, C]): the classes the rows' nodes admit and the node
+        each leads to, a ragged expand of the trie's CSR rows; eos is admitted where a word ends and leads nowhere"""
+        dev = node.device
+        lo = trie.child_off[node].to(torch.int64)
+        count = trie.child_off[node + 1].to(torch.int64) - lo
+        row = torch.repeat_interleave(torch.arange(node.numel(), device=dev), count)
+        edge = torch.arange(row.numel(), device=dev) - torch.repeat_interleave(torch.cumsum(count, 0) - count, count) + torch.repeat_interleave(lo, count)
+        cls = trie.child_tok[edge].to(torch.int64)
+        ok = cls < C
+        row, cls, edge = row[ok], cls[ok], edge[ok]
+        admitted = torch.zeros(node.numel(), C, dtype=torch.bool, device=dev)
+        step_to = node.view(-1, 1).repeat(1, C)
+        admitted[row, cls] = True
+        step_to[row, cls] = trie.child_node[edge].to(torch.int64)
+        admitted[:, eos] |= trie.word_of[node] >= 0
+        return admitted, step_to
+
+    def _search_stepwise(self, batch_H, Hproj, start, eos, W, S, trie):
+        """the step loop of beam_search (trie None) and lexicon_search (a TrieHandle: only the classes an entry's node admits are
+        candidates, a node is carried per row, and word is one more output): gather, Linear, one decoder step with carried state and the
+        generator on B * W rows; the selection on the sorted candidates"""
+        cell = self.attention_cell
+        B, T, D = batch_H.shape
+        dev = batch_H.device
         C, H = self.num_class, self.hidden_size
         w_emb = cell.rnn.weight_ih[:, D:]
         Hb_rows = batch_H.repeat_interleave(W, dim=0)
@@ -142,6 +204,7 @@ class Attention(nn.Module):
         tokens = torch.full((B, W, S), eos, dtype=torch.int32, device=dev)
         logp = torch.zeros(B, W, S, device=dev)
         rows = torch.arange(B, device=dev).view(B, 1)
+        node = torch.zeros(B, W, dtype=torch.int64, device=dev)
         for s in range(S):
             emb = ops.embed_gather(targets, self.char_embeddings.weight, C)
             eproj = ops.linear(emb, w_emb, cell.rnn.bias_ih)
@@ -150,7 +213,11 @@ class Attention(nn.Module):
             lp = torch.log_softmax(torch.where(torch.isnan(x), neg, x), dim=2)
             done = torch.full((B, W, C), float("-inf"), device=dev)
             done[:, :, eos] = score
-            cand = torch.where(finished.unsqueeze(2), done, score.unsqueeze(2) + lp)
+            cand = score.unsqueeze(2) + lp
+            if trie is not None:
+                admitted, step_to = self._admitted(trie, node.view(-1), C, eos)
+                cand = torch.where(admitted.view(B, W, C), cand, neg)
+            cand = torch.where(finished.unsqueeze(2), done, cand)
             cand = torch.where(torch.isnan(cand), neg, cand).view(B, W * C)               # candidate order (i, c)
             val, idx = torch.sort(cand, dim=1, descending=True, stable=True)
             val, idx = val[:, :W], idx[:, :W]
@@ -167,13 +234,18 @@ class Attention(nn.Module):
             h = h.view(B, W, H)[rows, par].reshape(B * W, H).contiguous()
             c = c.view(B, W, H)[rows, par].reshape(B * W, H).contiguous()
             targets = torch.where(alive, cls, eos).reshape(B * W, 1).contiguous()
+            if trie is not None:                   # a finished or dead entry keeps its node
+                node = torch.where(alive & ~was_done, step_to.view(B, W, C)[rows, par, cls], node[rows, par])
             finished = alive & (cls == eos)
             score = val
         alive = score > float("-inf")
         is_eos = tokens == eos
         length = torch.where(is_eos.any(dim=2), is_eos.to(torch.int32).argmax(dim=2) + 1, S).to(torch.int32)
         length[~alive] = -1
-        return tokens, length, score, logp, tokens[:, 0].to(torch.int64), torch.exp(logp[:, 0])
+        out = (tokens, length, score, logp, tokens[:, 0].to(torch.int64), torch.exp(logp[:, 0]))
+        if trie is not None:
+            out += (torch.where(alive, trie.word_of[node], -1).to(torch.int32),)
+        return out
 
     def forward(self, batch_H, text, is_train=True, batch_max_length=25, out=None):
         """batch_H [B,T,D]; text [B,S] (teacher forcing) or [B] of [SOS] (greedy) -> logits [B,S,num_class].

@@ -1540,6 +1540,12 @@ def attn_beam_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih
     the operands of attn_greedy_decode_grouped, the end token and the beam width -> (tokens int32 [G,B,W,S], length int32 [G,B,W], score
     fp32 [G,B,W], logp fp32 [G,B,W,S], path int64 [G,B,S], prob fp32 [G,B,S]), entries in descending score (modules/decoding.py).  The
     limits are the caller's to keep (attn_beam_whole_context, S <= 512, 2 <= classes, hidden 256): outside them the call is an error"""
+    return _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, None)
+
+
+def _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, trie):
+    """attn_beam_decode_grouped (trie None) and attn_lexicon_decode_grouped (a TrieHandle: the trie operands go in behind W, the word
+    output behind prob)"""
     import ctypes
     _chk(Hb, Hproj)
     G, B, T, D = Hb.shape
@@ -1566,6 +1572,18 @@ def attn_beam_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih
         return _ptr_array([t.data_ptr() for t in ts])
     outs = (arr(scratch), per, arr(tokens), arr(length), arr(score), arr(logp), arr(path), arr(prob))
     ncls = (ctypes.c_int * G)(*classes)
+    if trie is not None:
+        if not isinstance(trie, TrieHandle) or trie.child_off.device != dev:
+            raise ValueError("attn_lexicon_decode needs the handle of upload_trie on the device of the features")
+        word = torch.empty(G, B, Wd, device=dev, dtype=torch.int32)
+        lex = (_p(trie.child_off), _p(trie.child_tok), _p(trie.child_node), _p(trie.word_of), trie.nodes, trie.depth)
+        operands = (arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score), arr(w_ih), arr(w_hh))
+        tail = (arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *lex, *outs, arr(word), G, B, T, D, S, hidden, _stream())
+        if w_inv is not None:
+            call("mrn_attn_lexicon_decode_x3_grouped", *operands, arr(w_inv), *tail)
+        else:
+            call("mrn_attn_lexicon_decode_grouped_f32", *operands, *tail)
+        return tokens, length, score, logp, path, prob, word
     if w_inv is not None:
         call("mrn_attn_beam_decode_x3_grouped", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
              arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *outs, G, B, T, D, S, hidden, _stream())
@@ -1580,6 +1598,58 @@ def attn_beam_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, 
     without the expert dimension"""
     res = attn_beam_decode_grouped(Hb.unsqueeze(0), Hproj.unsqueeze(0), [etab], start, [w_h2h], [b_h2h], [w_score], [w_ih], [w_hh], [b_hh],
                                    [w_gen], [b_gen], hidden, S, eos, width, w_inv=None if w_inv is None else [w_inv])
+    return tuple(r[0] for r in res)
+
+
+ATTN_LEXICON_LDS_EXTRA = ATTN_BEAM_LDS_EXTRA + 4 * (2 * 16 + 16 * 16)      # attn_lexicon_kernel: + two node rows and the candidate-node plane
+
+
+def attn_lexicon_whole_context(D, T, W, x3=None):
+    """attn_beam_whole_context for the lexicon-constrained launch (csrc/rnn.hip beam_launch / beam_grouped with a trie): the same sum
+    with ATTN_LEXICON_LDS_EXTRA, 1152 bytes more.  There is no chunked form either: what does not fit is decoded stepwise
+    (Attention.lexicon_search)"""
+    x3 = DECODER_X3 if x3 is None else x3
+    lds = 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + ATTN_LEXICON_LDS_EXTRA
+    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and lds <= 160 * 1024
+
+
+class TrieHandle:
+    """a checked trie on a device (upload_trie): the four int32 tensors, the node count, the longest word, the size of the lexicon, and
+    the host arrays for CPU tensors"""
+
+    def __init__(self, trie, device):
+        self.trie = trie
+        import numpy as np
+        from .modules.decoding import check_trie
+        self.nodes, self.edges = check_trie(trie)
+        self.depth, self.words = int(trie.depth), int(trie.words)
+        pad = np.zeros(1, dtype=np.int32)           # a root alone has no edges: the kernel still gets two non-null arrays, never read
+        self.child_off, self.word_of = (torch.from_numpy(a).to(device) for a in (trie.child_off, trie.word_of))
+        self.child_tok, self.child_node = (torch.from_numpy(a if len(a) else pad).to(device) for a in (trie.child_tok, trie.child_node))
+
+
+def upload_trie(trie, device):
+    """a Trie of modules/decoding.py build_trie -> TrieHandle on `device`.  The arrays are checked on the host first (decoding.check_trie,
+    once per lexicon): the kernel trusts them, so a malformed trie is a ValueError here and never a launch"""
+    return TrieHandle(trie, device)
+
+
+def attn_lexicon_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width,
+                                trie, w_inv=None):
+    """lexicon-constrained beam search on the attention head for G experts of one geometry in one launch (per eight experts;
+    include/mrn_attn_lexicon.h): the operands of attn_beam_decode_grouped and the TrieHandle all experts share -> its six outputs and
+    word int32 [G,B,W] (modules/decoding.py).  The limits are the caller's to keep (attn_lexicon_whole_context, S <= 512, trie.depth <=
+    S - 1, 2 <= classes, hidden 256): outside them the call is an error"""
+    if trie is None:
+        raise ValueError("attn_lexicon_decode needs the handle of upload_trie, got None")
+    return _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, trie)
+
+
+def attn_lexicon_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, trie,
+                        w_inv=None):
+    """attn_lexicon_decode_grouped for one expert (G = 1) -> the seven outputs without the expert dimension"""
+    res = attn_lexicon_decode_grouped(Hb.unsqueeze(0), Hproj.unsqueeze(0), [etab], start, [w_h2h], [b_h2h], [w_score], [w_ih], [w_hh],
+                                      [b_hh], [w_gen], [b_gen], hidden, S, eos, width, trie, w_inv=None if w_inv is None else [w_inv])
     return tuple(r[0] for r in res)
 
 

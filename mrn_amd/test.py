@@ -28,13 +28,23 @@ the per-step arg-max and its probability.  The loss is still computed on the gre
 drops the last character" quirk and the returned strings are the code above, unchanged: the confidence is then the probability of
 the kept tokens of the best entry.
 
-opt.lexicon = a sequence of words (absent or None: as above, bit for bit; the attention head ignores it) decodes a CTC head to the
+opt.lexicon = a sequence of words (absent or None: as above, bit for bit; the attention head ignores it: opt.attn_lexicon below is its
+counterpart there) decodes a CTC head to the
 lexicon word of largest log p(word | image), the exact CTC forward score of every (sample, word) pair (modules/decoding.py): the words
 the converter can spell are encoded and uploaded once per call, then one mrn_ctc_lexicon_decode_f32 call per batch, or the float64
 host form for predictions that are not on the GPU and for lexicons or batches outside the kernel's limits (a word of more than 31
 characters).  The hand-over is the beam decoder's: the best word as a row of frames whose greedy collapse is that word, its probability
 as that row's first factor, and the scorer behind it unchanged.  opt.lexicon_top_n (default 1) is the number of entries the decoder
 ranks per sample; validation() scores the best one.  A lexicon together with ctc_decode = "beam" is an error: both replace best path.
+
+opt.attn_lexicon = a sequence of words (absent or None: as above, bit for bit; CTC heads ignore it) is opt.lexicon's counterpart on the
+attention head: the beam search of width opt.beam_width (whatever attn_decode says) is walked along a trie of the lexicon, so every
+entry is a lexicon word and its score log p(word, [EOS] | image) of the model, not renormalised (modules/decoding.py; with a width of
+at least the number of distinct words the best entry is the exact arg-max over the lexicon).  The words the converter can spell within
+batch_max_length characters are encoded, the trie built, checked and uploaded once per call; the evaluation forward is asked for the
+constrained beam pair (attn_beam=width, attn_lexicon=handle: one more launch per heads group, one trie for all experts) and the pair
+goes to the unchanged scorer as in beam mode: the confidence is the product of the kept tokens' probabilities, the loss is still the
+greedy logits'.  A sample none of whose words the routed expert can spell scores as an empty prediction with confidence 0.
 """
 import time
 
@@ -62,9 +72,10 @@ def edit_distance(a, b):
     return prev[-1]
 
 
-def _forward(model, image, opt, converter, val_choose, attn_beam=None):
+def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None):
     """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
-    attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits"""
+    attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits; attn_lexicon (a
+    trie handle beside it): the pair of the lexicon-constrained search"""
     if "CTC" in opt.Prediction:
         if val_choose == "FF":
             out = model(image, cross=False, is_train=False)
@@ -75,6 +86,8 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None):
     else:
         sos = torch.full((image.size(0),), converter.dict["[SOS]"], dtype=torch.long, device=image.device)
         kw = {} if attn_beam is None else {"attn_beam": attn_beam}
+        if attn_lexicon is not None:
+            kw["attn_lexicon"] = attn_lexicon
         if val_choose == "FF":
             out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
@@ -169,6 +182,20 @@ class _Lexicon:
         return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
 
 
+class _AttnLexicon:
+    """opt.attn_lexicon encoded and built into a trie once per validation() call; checked and uploaded when the first batch needs it"""
+
+    def __init__(self, converter, words, batch_max_length):
+        tokens, lengths, self.words = D.encode_attn_lexicon(converter, words, batch_max_length)
+        self.trie = D.build_trie(tokens, lengths)
+        self.handle = None
+
+    def on(self, device):
+        if self.handle is None:
+            self.handle = ops.upload_trie(self.trie, device)
+        return self.handle
+
+
 def validation(model, criterion, evaluation_loader, converter, opt, val_choose="val", tqdm_position=1):
     n_correct, norm_ED, length_of_data, infer_time = 0, 0.0, 0, 0.0
     loss_sum, loss_n = 0.0, 0
@@ -180,12 +207,17 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     ctc_decode, beam_width, beam_top_n = D.decode_options(opt)
     attn_decode, attn_width = D.attn_decode_options(opt)
     attn_beam = attn_width if attn and attn_decode == "beam" else None
+    attn_words, attn_lexicon_width = D.attn_lexicon_options(opt)
+    attn_lexicon = None
+    if attn and attn_words is not None:
+        attn_lexicon, attn_beam = _AttnLexicon(converter, attn_words, opt.batch_max_length), attn_lexicon_width
     lexicon_words, lexicon_n = D.lexicon_options(opt)
     if lexicon_words is not None and not attn and ctc_decode == "beam":
         raise ValueError("lexicon and ctc_decode='beam' both replace best-path decoding on a CTC head: set one of them")
     lexicon = _Lexicon(converter, lexicon_words, lexicon_n) if lexicon_words is not None and not attn else None
     if attn_beam is not None and converter.dict["[EOS]"] != D.ATTN_EOS:
-        raise ValueError(f"attn_decode='beam' ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
+        what = "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'"
+        raise ValueError(f"{what} ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
         length_of_data += batch_size
@@ -194,7 +226,8 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         if image.is_cuda:
             torch.cuda.synchronize()                 # the launches are asynchronous: infer_time is forward time, not host issue time
         start = time.time()
-        preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam)
+        preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam,
+                         attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device))
         if attn_beam is not None:
             preds, beam_pair = preds
         if image.is_cuda:
