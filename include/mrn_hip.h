@@ -738,9 +738,11 @@ int64_t mrn_grad_norm_workspace_floats(int64_t n);
    finite -- the update kernels below skip such a step (parameters and optimiser state untouched) -- a counter the caller
    zero-initialises once and keeps across steps */
 int mrn_grad_norm_clip_f32(const float* g, int64_t n, float max_norm, float* workspace, float* norm_coef, void* stream);
-/* g *= coef (in place), then torch.optim.Adam's update; step_size = lr/(1-beta1^t), bc2_sqrt = sqrt(1-beta2^t) */
+/* g *= coef (in place), then torch.optim.Adam's update; step_size = lr/(1-beta1^t), bc2_sqrt = sqrt(1-beta2^t).  The caller rounds
+   1 - beta1 and 1 - beta2 from double precision, as torch does: 1.f - 0.999f is 0.00099998713, a relative error of 1.3e-5 in every
+   second moment of the early steps */
 int mrn_adam_step_f32(float* p, float* g, float* m, float* v, int64_t n, const float* norm_coef, float step_size,
-                      float beta1, float beta2, float bc2_sqrt, float eps, void* stream);
+                      float one_minus_beta1, float beta2, float one_minus_beta2, float bc2_sqrt, float eps, void* stream);
 /* torch.optim.SGD (il_modules/base.py:74-79: momentum, weight decay; dampening 0, no Nesterov): g *= coef, buf = mu*buf + g + wd*p,
    p -= lr*buf.  buf zero-initialised by the caller (may be NULL when momentum == 0). */
 int mrn_sgd_step_f32(float* p, float* g, float* buf, int64_t n, const float* norm_coef, float lr, float momentum,

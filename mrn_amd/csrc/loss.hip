@@ -367,6 +367,10 @@ __global__ __launch_bounds__(256) void ctc_grad_long_kernel(const float* __restr
 // ---- knowledge distillation (LwF): -sum softmax(old/T) * log_softmax(new/T) / rows over the class slice [c0, c1) -------
 // reference il_modules/lwf.py:81-87,111-114.  One block per row.  loss_rows[row] = -sum_c p_old * logp_new.
 // When dnew != nullptr also writes d loss / d new = (softmax(new/T) - softmax(old/T)) / T * g (zeros outside the slice).
+// Probabilities are formed as exp(x/T - max) / sum and log-probabilities as (x/T - max) - log(sum), torch's order.  The shorter
+// exp(x/T - lse) with lse = max + log(sum) rounds lse to fp32 first, and an error in lse -- or in log(sum) alone: one ulp of a value
+// near 4 is 5e-7 -- shifts EVERY probability of the row by the same relative amount; it showed as 4e-7 of a one-row loss against
+// float64.  x/T is rounded once (__fmul_rn keeps the compiler from fusing it into the subtraction): every pass sees the same value.
 __global__ __launch_bounds__(256) void kd_rows_kernel(const float* __restrict__ xnew, long ldn, const float* __restrict__ xold,
                                                       long ldo, int c0, int c1, float invT, float* __restrict__ loss_rows,
                                                       const float* __restrict__ upstream, float inv_rows,
@@ -376,17 +380,18 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float* __restrict__ 
   const float* a = xnew + row * ldn;
   const float* b = xold + row * ldo;
   float ma = -INFINITY, mb = -INFINITY;
-  for (int c = c0 + threadIdx.x; c < c1; c += 256) { ma = fmaxf(ma, a[c] * invT); mb = fmaxf(mb, b[c] * invT); }
+  for (int c = c0 + threadIdx.x; c < c1; c += 256) { ma = fmaxf(ma, __fmul_rn(a[c], invT)); mb = fmaxf(mb, __fmul_rn(b[c], invT)); }
   ma = block_max<256>(ma, scratch);
   mb = block_max<256>(mb, scratch);
   float sa = 0.f, sb = 0.f;
-  for (int c = c0 + threadIdx.x; c < c1; c += 256) { sa += expf(a[c] * invT - ma); sb += expf(b[c] * invT - mb); }
+  for (int c = c0 + threadIdx.x; c < c1; c += 256) { sa += expf(__fmul_rn(a[c], invT) - ma); sb += expf(__fmul_rn(b[c], invT) - mb); }
   sa = block_sum<256>(sa, scratch);
   sb = block_sum<256>(sb, scratch);
-  const float lsa = ma + logf(sa), lsb = mb + logf(sb);
   if (loss_rows) {
+    const float la = logf(sa);
     float l = 0.f;
-    for (int c = c0 + threadIdx.x; c < c1; c += 256) l -= expf(b[c] * invT - lsb) * (a[c] * invT - lsa);
+    for (int c = c0 + threadIdx.x; c < c1; c += 256)
+      l -= expf(__fmul_rn(b[c], invT) - mb) / sb * ((__fmul_rn(a[c], invT) - ma) - la);
     l = block_sum<256>(l, scratch);
     if (threadIdx.x == 0) loss_rows[row] = l;
   }
@@ -394,16 +399,23 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float* __restrict__ 
     const float g = upstream[0] * inv_rows * invT;
     float* d = dnew + row * ldd;
     for (int c = threadIdx.x; c < C; c += 256)
-      d[c] = (c >= c0 && c < c1) ? (expf(a[c] * invT - lsa) - expf(b[c] * invT - lsb)) * g : 0.f;
+      d[c] = (c >= c0 && c < c1) ? (expf(__fmul_rn(a[c], invT) - ma) / sa - expf(__fmul_rn(b[c], invT) - mb) / sb) * g : 0.f;
   }
 }
 
-__global__ __launch_bounds__(256) void mean_finalize_kernel(const float* __restrict__ v, long n, float scale, float* __restrict__ out) {
-  __shared__ float scratch[4];
-  float s = 0.f;
-  for (long i = threadIdx.x; i < n; i += 256) s += v[i];
-  s = block_sum<256>(s, scratch);
-  if (threadIdx.x == 0) out[0] = s * scale;
+// out[0] = mean(v[0..n)), one block.  Summed in double and divided once: an fp32 sum of a thousand row losses times an fp32 1 / n was
+// four ulps off the float64 mean (2.5e-7); the one block makes double precision free here.
+__global__ __launch_bounds__(256) void mean_finalize_kernel(const float* __restrict__ v, long n, float* __restrict__ out) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) s += (double)v[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(part[0] / (double)n);
 }
 
 }  // namespace
@@ -414,8 +426,7 @@ MRN_EXPORT int mrn_kd_loss_fwd_f32(const float* xnew, int64_t ldn, const float* 
   if (rows == 0) return MRN_OK;
   hipLaunchKernelGGL(kd_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, xnew, (long)ldn, xold, (long)ldo, c0,
                      c1, 1.f / T, loss_rows, (const float*)nullptr, 0.f, (float*)nullptr, 0L, 0);
-  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)loss_rows, (long)rows,
-                     1.f / (float)rows, loss);
+  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)loss_rows, (long)rows, loss);
   MRN_LAUNCH_CHECK("kd_loss_fwd");
   return MRN_OK;
 }

@@ -2192,8 +2192,8 @@ def grad_norm_clip(gflat, max_norm, out=None):
 def adam_step(p, g, m, v, norm_coef, lr, step, betas=(0.9, 0.999), eps=1e-8):
     bc1 = 1.0 - betas[0] ** step
     bc2 = 1.0 - betas[1] ** step
-    call("mrn_adam_step_f32", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(norm_coef), float(lr / bc1), float(betas[0]),
-         float(betas[1]), float(bc2 ** 0.5), float(eps), _stream())
+    call("mrn_adam_step_f32", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(norm_coef), float(lr / bc1), float(1.0 - betas[0]),
+         float(betas[1]), float(1.0 - betas[1]), float(bc2 ** 0.5), float(eps), _stream())
 
 
 def sgd_step(p, g, buf, norm_coef, lr, momentum=0.0, weight_decay=0.0):

@@ -284,3 +284,156 @@ def rel_err(got, ref):
 
 
 F32_FLOOR = 4 * 2.0 ** -24        # two fp32 roundings of the result itself: the floor under every "8 x the fp32 baseline" bound
+
+
+def baseline_bound(ref64, base32, factor=8.0, extra=0.0):
+    """the bound within_baseline applies: max(factor * error of the fp32 baseline, 4 * 2^-24, extra), relative to max|reference|"""
+    return max(factor * rel_err(base32, ref64), F32_FLOOR, extra)
+
+
+def within_baseline(name, got, ref64, base32, factor=8.0, extra=0.0):
+    """kernel error <= max(factor * error of the fp32 CPU baseline, 4 * 2^-24), both relative to max|reference|; -> the ratio.
+    `extra`: a relative tolerance the caller DERIVED for a known property of the kernel's formula (never a measured one), OR-ed
+    into the bound"""
+    err, e32 = rel_err(got, ref64), rel_err(base32, ref64)
+    ratio = err / max(e32, F32_FLOOR / factor)
+    print(f"{name}: kernel {err:.2e}  fp32 baseline {e32:.2e}  ratio {ratio:.2f}" + (f"  derived extra {extra:.2e}" if extra else ""))
+    bound = max(factor * e32, F32_FLOOR, extra)
+    assert err <= bound, (f"{name}: kernel error {err:.3e} > max({factor:g} x {e32:.3e}, {F32_FLOOR:.2e}"
+                          + (f", {extra:.3e})" if extra else ")"))
+    return ratio
+
+
+# ---------------------------------------------------------------------------------------------------------
+# written-out yardsticks of the loss / distillation / EWC / optimiser kernels (tests/test_loss_optim_*.py).  Every one casts its
+# operands to `dtype` first: float64 is the reference, float32 the baseline a plain fp32 evaluation of the same formula reaches.
+# ---------------------------------------------------------------------------------------------------------
+def row_lse(x, dtype=torch.float64):
+    """log-sum-exp of every row of x [rows, C]"""
+    x = x.detach().to(dtype)
+    m = x.max(1, keepdim=True).values
+    return (m + torch.log(torch.exp(x - m).sum(1, keepdim=True))).squeeze(1)
+
+
+def _log_softmax(x):
+    m = x.max(1, keepdim=True).values
+    return (x - m) - torch.log(torch.exp(x - m).sum(1, keepdim=True))
+
+
+def ce_reference(logits, target, ignore_index=-100, upstream=1.0, dtype=torch.float64):
+    """CrossEntropyLoss(reduction='mean', ignore_index) on logits [rows, C], target [rows] int64 -> (loss, d(upstream * loss) / dlogits).
+    loss = sum over the rows with target != ignore_index of (lse - x[target]) / their number; no such row: the loss is NaN (0 / 0)
+    and the gradient exactly zero, as torch has it."""
+    x = logits.detach().to(dtype)
+    t = target.reshape(-1)
+    valid = t != ignore_index
+    n = int(valid.sum())
+    logp = _log_softmax(x)
+    tt = torch.where(valid, t, torch.zeros_like(t)).unsqueeze(1)
+    rows = -logp.gather(1, tt).squeeze(1) * valid.to(dtype)
+    loss = rows.sum() / torch.tensor(float(n), dtype=dtype)
+    if n == 0:
+        return loss, torch.zeros_like(x)
+    onehot = torch.zeros_like(x).scatter_(1, tt, 1.0)
+    d = (torch.exp(logp) - onehot) * valid.to(dtype).unsqueeze(1) * (upstream / n)
+    return loss, d
+
+
+def kd_reference(new, old, c0, c1, T, upstream=1.0, dtype=torch.float64):
+    """_KD_loss of LwF / WA on the class slice [c0, c1) of new / old [rows, C]:
+    loss = -sum(softmax(old / T) * log_softmax(new / T)) / rows -> (loss, d(upstream * loss) / dnew over the full width C: zero outside
+    the slice, (softmax(new / T) - softmax(old / T)) / T * upstream / rows inside)"""
+    new, old = new.detach().to(dtype), old.detach().to(dtype)
+    rows = new.shape[0]
+    la, lb = _log_softmax(new[:, c0:c1] / T), _log_softmax(old[:, c0:c1] / T)
+    pb = torch.exp(lb)
+    loss = -(pb * la).sum() / rows
+    d = torch.zeros_like(new)
+    d[:, c0:c1] = (torch.exp(la) - pb) / T * (upstream / rows)
+    return loss, d
+
+
+def weight_align_reference(w, n_old, dtype=torch.float64):
+    """Model.weight_align on w [rows, C]: gamma = mean ||old rows|| / mean ||new rows||, the rows from n_old on scaled by it
+    -> (gamma, w aligned)"""
+    w = w.detach().to(dtype)
+    norms = torch.sqrt((w * w).sum(1))
+    gamma = norms[:n_old].mean() / norms[n_old:].mean()
+    out = w.clone()
+    out[n_old:] *= gamma
+    return gamma, out
+
+
+def clip_reference(g, max_norm):
+    """clip_grad_norm_(g, max_norm) -> (norm, coefficient, g * coefficient): coefficient = min(1, max_norm / (norm + 1e-6));
+    max_norm None: no clipping, g is returned as it is"""
+    if max_norm is None:
+        return None, None, g
+    norm = torch.sqrt((g * g).sum())
+    coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    return norm, coef, g * coef
+
+
+def adam_reference(p, grads, max_norm, lr, betas=(0.9, 0.999), eps=1e-8, dtype=torch.float64):
+    """len(grads) steps of clip_grad_norm_(max_norm) + torch.optim.Adam (no weight decay, no amsgrad) from zero moments
+    -> dict p, g (the last gradient after clipping), m, v, norms, coefs"""
+    p = p.detach().to(dtype).clone()
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    norms, coefs = [], []
+    for step, g in enumerate(grads, 1):
+        norm, coef, g = clip_reference(g.detach().to(dtype), max_norm)
+        norms.append(norm)
+        coefs.append(coef)
+        m = m + (g - m) * (1 - betas[0])
+        v = v * betas[1] + (1 - betas[1]) * g * g
+        denom = torch.sqrt(v) / (1 - betas[1] ** step) ** 0.5 + eps
+        p = p - lr / (1 - betas[0] ** step) * (m / denom)
+    return dict(p=p, g=g, m=m, v=v, norms=norms, coefs=coefs)
+
+
+def sgd_reference(p, grads, max_norm, lr, momentum=0.0, weight_decay=0.0, dtype=torch.float64):
+    """... + torch.optim.SGD (dampening 0, no Nesterov): d = g + wd * p; buf = d at the first step, momentum * buf + d afterwards;
+    p -= lr * buf (momentum 0: p -= lr * d and buf stays zero) -> dict p, g, buf, norms, coefs"""
+    p = p.detach().to(dtype).clone()
+    buf = torch.zeros_like(p)
+    norms, coefs = [], []
+    for g in grads:
+        norm, coef, g = clip_reference(g.detach().to(dtype), max_norm)
+        norms.append(norm)
+        coefs.append(coef)
+        d = g + weight_decay * p
+        if momentum != 0:
+            buf = momentum * buf + d
+            d = buf
+        p = p - lr * d
+    return dict(p=p, g=g, buf=buf, norms=norms, coefs=coefs)
+
+
+def adadelta_reference(p, grads, max_norm, lr, rho=0.9, eps=1e-6, dtype=torch.float64):
+    """... + torch.optim.Adadelta (no weight decay) -> dict p, g, sq (square_avg), acc (acc_delta), norms, coefs"""
+    p = p.detach().to(dtype).clone()
+    sq, acc = torch.zeros_like(p), torch.zeros_like(p)
+    norms, coefs = [], []
+    for g in grads:
+        norm, coef, g = clip_reference(g.detach().to(dtype), max_norm)
+        norms.append(norm)
+        coefs.append(coef)
+        sq = sq * rho + (1 - rho) * g * g
+        delta = torch.sqrt(acc + eps) / torch.sqrt(sq + eps) * g
+        acc = acc * rho + (1 - rho) * delta * delta
+        p = p - lr * delta
+    return dict(p=p, g=g, sq=sq, acc=acc, norms=norms, coefs=coefs)
+
+
+def ewc_reference(grads, fisher_max, p, mean, coef, grad0, dtype=torch.float64):
+    """EWC (il_modules/ewc.py): fisher = min(sum_k grads[k]^2 / len(grads), fisher_max); penalty = sum fisher * (p - mean)^2 / 2;
+    grad = grad0 + coef * fisher * (p - mean) -> dict acc (the sum before finalising), fisher, penalty, grad"""
+    acc = torch.zeros_like(p, dtype=dtype)
+    for g in grads:
+        g = g.detach().to(dtype)
+        acc = acc + g * g
+    fisher = torch.clamp(acc * (1.0 / len(grads)), max=fisher_max)
+    d = p.detach().to(dtype) - mean.detach().to(dtype)
+    penalty = (fisher * d * d).sum() / 2
+    grad = grad0.detach().to(dtype) + coef * fisher * d
+    return dict(acc=acc, fisher=fisher, penalty=penalty, grad=grad)

@@ -18,7 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import F32_FLOOR, assert_close, bn_bwd_reference, pack_relu_mask, rel_err, unpack_relu_mask
+from tests.helpers import F32_FLOOR, assert_close, bn_bwd_reference, pack_relu_mask, rel_err, unpack_relu_mask, within_baseline
 
 pytestmark = pytest.mark.gpu
 
@@ -46,15 +46,6 @@ def cu(t):
 def bits(t):
     """the tensor's bit patterns: equality that tells -0.0 from +0.0 and holds for NaN"""
     return t.detach().contiguous().view(torch.int32)
-
-
-def within_baseline(name, got, ref64, base32, factor=8.0):
-    """kernel error <= max(factor * error of the fp32 CPU baseline, 4 * 2^-24), both relative to max|reference|; -> the ratio"""
-    err, e32 = rel_err(got, ref64), rel_err(base32, ref64)
-    ratio = err / max(e32, F32_FLOOR / factor)
-    print(f"{name}: kernel {err:.2e}  fp32 baseline {e32:.2e}  ratio {ratio:.2f}")
-    assert err <= max(factor * e32, F32_FLOOR), f"{name}: kernel error {err:.3e} > max({factor:g} x {e32:.3e}, {F32_FLOOR:.2e})"
-    return ratio
 
 
 # ---------------------------------------------------------------------------------------------------------
