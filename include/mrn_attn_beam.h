@@ -10,7 +10,7 @@ extern "C" {
 #endif
 
 /* Beam search on the attention head (extends the greedy loop of modules/prediction.py:70-86: W entries per sample instead of the one
- * arg-max), all S steps of `groups` experts of one geometry (B, T, D, S) in one launch per eight experts (csrc/rnn.hip attn_beam_kernel,
+ * arg-max), all S steps of `groups` experts of one geometry (B, T, D, S) in one launch per eight experts (csrc/attn_decode.hip attn_beam_kernel,
  * exact-fp32 form).  The algorithm is stated in mrn_amd/modules/decoding.py and restated in float64 by attn_beam_host there.  The
  * operands are those of mrn_attn_greedy_decode_grouped_f32: every pointer argument but start_token is a HOST array of `groups` device
  * pointers, num_class a host array of `groups` class counts.  eos = the end token, W = the beam width.  scratch[g]: scratch_floats

@@ -11,7 +11,7 @@ extern "C" {
 
 /* Beam search on the attention head walked along a trie of a lexicon (extends the greedy loop of modules/prediction.py:70-86: W
  * entries per sample, each one a prefix of a lexicon word, instead of the one arg-max), all S steps of `groups` experts of one geometry
- * (B, T, D, S) in one launch per eight experts (csrc/rnn.hip attn_lexicon_kernel, exact-fp32 form).  The algorithm is stated in
+ * (B, T, D, S) in one launch per eight experts (csrc/attn_decode.hip attn_lexicon_kernel, exact-fp32 form).  The algorithm is stated in
  * mrn_amd/modules/decoding.py and restated in float64 by attn_lexicon_host there.  The operands, eos, W, scratch and the six outputs
  * are those of mrn_attn_beam_decode_grouped_f32 (include/mrn_attn_beam.h).  The trie, one for all groups, is four DEVICE arrays of
  * int32: node 0 is the root, the children of node n are the edges child_off[n] ... child_off[n + 1] - 1 (child_off [nodes + 1]) with

@@ -2,19 +2,15 @@
 //
 // Reference: loss.backward() (il_modules/mrn.py:260-261) through modules/prediction.py:58-68,102-118 (26 steps of
 // additive attention + LSTMCell) and modules/transformation.py:33-44,204-216.  Same workgroup geometry as the
-// forward (rnn.hip): 16 samples per workgroup, 16 waves, wave w owns hidden units [16w, 16w+16); the transposed
-// recurrent weights stream fragment-major from L2.
-#include "common.hpp"
+// forward (attn_decode.hip): 16 samples per workgroup, 16 waves, wave w owns hidden units [16w, 16w+16); the transposed
+// recurrent weights stream fragment-major from L2.  The tile constants HID, BT, NW, NTH, HLD, mfma4 and fast_tanh are the forward's
+// (recurrent.hpp).
+#include "recurrent.hpp"
 #include <stdlib.h>
 
 namespace {
 
-constexpr int HID = 256, BT = 16, NW = 16, NTH = NW * 64;
-constexpr int HLD = HID + 4, GLD = 4 * HID + 4;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+constexpr int GLD = 4 * HID + 4;
 
 // acc[g] += A(16 x K in LDS) . Wg^T with fragment-major weights; G weight sets share the A fragment reads
 template <int G>
@@ -79,11 +75,6 @@ struct AttnBwdParams {
   const float* w_inv;     // x3 form: device float[3] = 1 / prescale of W_h2h^T, W_ih_ctx^T, W_hh^T (then fp16 hi / lo fragment-major streams)
   const float* gscale;    // x3 form: device float[2] = {s, 1/s}: the gate / hp gradients are split as s * value
 };
-
-__device__ __forceinline__ float fast_tanh(float x) {
-  const float e = __expf(2.f * x);
-  return 1.f - 2.f / (e + 1.f);
-}
 
 // X3: the three transposed products (dgates . W_ih_ctx, dgates . W_hh, dhp . W_h2h) as split-fp16 x3 -- the gate / hp gradients live in
 // LDS as fp16 hi / lo planes of gscale * value.  On the exact-fp32 pipe they are 30 us of a step (576 MFMAs of 32 cycles per wave).
@@ -504,7 +495,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dhproj_kernel(const float* __res
 
 // samples per workgroup of the decoder backward: the smallest of {2, 4, 8, 16} that keeps the grid within one workgroup per CU (B = 256,
 // D = 256 / 1536, us per launch: 1150 / 3120 at 1, 1195 / 3360 at 2, 1440 / 4040 at 4, 1900 / 5420 at 8, 2840 / 8280 at 16; not 1 for the
-// reason given at the forward's rule, rnn.hip: attn_launch)
+// reason given at the forward's rule, attn_decode.hip: attn_launch)
 static int attn_bwd_vb(int B) {
   static const int forced = getenv("MRN_ATTN_BWD_VB") ? atoi(getenv("MRN_ATTN_BWD_VB")) : 0;     // (A/B switch, read once)
   if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) return forced;

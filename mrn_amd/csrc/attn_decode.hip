@@ -1,643 +1,12 @@
-// Recurrent kernels: bidirectional LSTM layer and the attention decoder (teacher-forced and greedy).
+// Attention decoders: teacher-forced, greedy, beam and lexicon-constrained beam, one persistent kernel each around one shared
+// attention-cell step; their launch rules and entry points.
 //
-// Reference: modules/sequence_modeling.py:7-21 (nn.LSTM bidirectional, gate order i,f,g,o) and
-// modules/prediction.py:38-118 (Attention / AttentionCell, 26 decode steps).
-//
-// Samples are independent along the time recurrence, so one workgroup owns a 16-sample batch tile for the
-// whole sequence: hidden state lives in LDS, cell state in registers, and only the recurrent weights stream
-// from L2 each step.  Products run on v_mfma_f32_16x16x4_f32 (exact fp32): M = 16 samples, N = gate columns,
-// K = hidden.  Wave w owns hidden units [64w, 64w+64) for all four gates, so the LSTM pointwise update is
-// lane-local (the i,f,g,o pre-activations of a unit land in the same lane and register index).
-// The k index is permuted (lane group g takes k = 16q+4g+r) so every operand read is one 16-byte access.
-#include "common.hpp"
+// Reference: modules/prediction.py:38-118 (Attention / AttentionCell, 26 decode steps).  The workgroup geometry and the MFMA
+// helpers are recurrent.hpp's, shared with the BiLSTM layer (lstm.hip) and the backward (attn_bwd.hip).
+#include "recurrent.hpp"
 #include <stdlib.h>
 
 namespace {
-
-constexpr int HID = 256;       // hidden size (reference configs: hidden_size=256)
-constexpr int BT = 16;         // samples per workgroup
-constexpr int HLD = HID + 4;   // padded LDS row
-constexpr int NW = 16;         // waves per workgroup: wave w owns hidden units [16w, 16w+16) of every gate
-constexpr int NTH = NW * 64;   // 1024 threads -- many waves in flight hide the L2 latency of the weight stream
-// (the five constants above are the attention decoder's, which runs hidden = 256 only.)
-
-// The LSTM layer kernels are templates over the hidden size HS in {128, 256, 512}.  A 16-unit tile of every gate belongs to one wave:
-//   HS = 128   8 waves (512 threads), one unit tile each
-//   HS = 256  16 waves (1024 threads), one unit tile each
-//   HS = 512  16 waves, wave w walks unit tiles w and w + 16 one after the other inside a step (NP = 2 passes: the four gate accumulators
-//             are reused, cell state and bias are held per pass).  Both passes read h of the step from LDS buffer `cur` and write the new h
-//             to buffer `cur ^ 1`, so no pass ever sees a half-updated h; one barrier per step as at the other sizes.
-template <int HS>
-struct LstmGeom {
-  static_assert(HS == 128 || HS == 256 || HS == 512, "LSTM layer kernels: hidden size 128, 256 or 512");
-  static constexpr int NW = HS >= 256 ? 16 : HS / 16;   // waves per workgroup
-  static constexpr int NP = HS / (16 * NW);             // unit tiles (passes) per wave and step
-  static constexpr int NTH = NW * 64;
-  static constexpr int HLD = HS + 4;                    // padded fp32 LDS row
-  static constexpr int LDH = HS + 8;                    // padded fp16 LDS row (halves)
-};
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// acc[g] += A(16 x K from LDS rows of stride lda) . W_g^T   for K a multiple of 16.
-// W is FRAGMENT-MAJOR: Wp[((wave*NG + g)*Q + q)*64 + lane] is the float4 the lane feeds to the four MFMAs of k-step q,
-//   = W[g*HID + 16*wave + (lane&15)][16q + 4*(lane>>4) .. +3]
-// so every wave-level load is one contiguous 1 KiB line instead of 16 rows x 64 B (pack_fragment_major on the host).
-// Weight fragments of step q+1 are fetched before the MFMAs of step q issue; consecutive MFMAs target different
-// accumulators (the 16x16x4 f32 MFMA has a 40-cycle dependent latency vs 32-cycle issue).
-template <int NG>
-__device__ __forceinline__ void mma_rows(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
-                                         const float* __restrict__ Wp, int K, int wave, int lane) {
-  const int n = lane & 15, g4 = (lane >> 4) * 4;
-  const float* ap = a_lds + n * lda + g4;
-  const int Q = K / 16;
-  const f32x4* wp = reinterpret_cast<const f32x4*>(Wp) + (long)wave * NG * Q * 64 + lane;
-  f32x4 wv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) wv[g] = wp[(long)g * Q * 64];
-#pragma unroll 1   // keep the one-step-ahead register pipeline; full unrolling hoists every load and spills
-  for (int q = 0; q < Q; ++q) {
-    f32x4 wn[NG];
-    const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wn[g] = wp[((long)g * Q + qn) * 64];
-    const f32x4 av = *reinterpret_cast<const f32x4*>(ap + q * 16);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int g = 0; g < NG; ++g) acc[g] = mfma4(av[r], wv[g][r], acc[g]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wv[g] = wn[g];
-  }
-}
-
-// mma_rows over the k-steps of the columns [k0, k0 + kn) of a K-wide fragment-major W, with A holding just those kn columns (from its
-// column 0): the wide-context decoder keeps one chunk of the context in LDS at a time.  Chunk after chunk on the same accumulators,
-// the MFMAs run in the order of one mma_rows over all of K.
-template <int NG>
-__device__ __forceinline__ void mma_rows_k(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
-                                           const float* __restrict__ Wp, int K, int k0, int kn, int wave, int lane) {
-  const int n = lane & 15, g4 = (lane >> 4) * 4;
-  const float* ap = a_lds + n * lda + g4;
-  const int Q = K / 16, nq = kn / 16;
-  const f32x4* wp = reinterpret_cast<const f32x4*>(Wp) + (long)wave * NG * Q * 64 + (long)(k0 / 16) * 64 + lane;
-  f32x4 wv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) wv[g] = wp[(long)g * Q * 64];
-#pragma unroll 1
-  for (int q = 0; q < nq; ++q) {
-    f32x4 wn[NG];
-    const int qn = (q + 1 < nq) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wn[g] = wp[((long)g * Q + qn) * 64];
-    const f32x4 av = *reinterpret_cast<const f32x4*>(ap + q * 16);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int g = 0; g < NG; ++g) acc[g] = mfma4(av[r], wv[g][r], acc[g]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wv[g] = wn[g];
-  }
-}
-
-// act[g][r] receives the post-activation gates (i, f, g, o) for the backward pass
-__device__ __forceinline__ void lstm_pointwise(const f32x4 (&acc)[4], const float (&xg)[4][4], const float (&bh)[4],
-                                               float (&c)[4], float (&h)[4], float (&act)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float gi = acc[0][r] + xg[0][r] + bh[0];
-    const float gf = acc[1][r] + xg[1][r] + bh[1];
-    const float gg = acc[2][r] + xg[2][r] + bh[2];
-    const float go = acc[3][r] + xg[3][r] + bh[3];
-    const float ig = sigmoidf_acc(gi), fg = sigmoidf_acc(gf), og = sigmoidf_acc(go), cg = tanhf(gg);
-    const float cn = fg * c[r] + ig * cg;
-    c[r] = cn;
-    h[r] = og * tanhf(cn);
-    act[0][r] = ig; act[1][r] = fg; act[2][r] = cg; act[3][r] = og;
-  }
-}
-
-// (the form whose accumulators already hold the input projection)
-__device__ __forceinline__ void lstm_pointwise0(const f32x4 (&acc)[4], const float (&bh)[4], float (&c)[4], float (&h)[4], float (&act)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float gi = acc[0][r] + bh[0];
-    const float gf = acc[1][r] + bh[1];
-    const float gg = acc[2][r] + bh[2];
-    const float go = acc[3][r] + bh[3];
-    const float ig = sigmoidf_acc(gi), fg = sigmoidf_acc(gf), og = sigmoidf_acc(go), cg = tanhf(gg);
-    const float cn = fg * c[r] + ig * cg;
-    c[r] = cn;
-    h[r] = og * tanhf(cn);
-    act[0][r] = ig; act[1][r] = fg; act[2][r] = cg; act[3][r] = og;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Bidirectional LSTM layer.  xproj[b][t][dir*4H + gate*H + j] holds W_ih x + b_ih.
-// grid = (ceil(B/16), ndir); out[b][t][dir*H + j].
-// ---------------------------------------------------------------------------------------------
-// Up to MAX_GROUPS independent layers (the frozen experts of the router phase) share one launch: grid.x = groups * tiles.
-constexpr int MAX_GROUPS = 8;
-struct LstmParams {
-  const float* xproj; const float* w_hh; const float* b_hh; float* out;
-  float* gates_out;   // optional [B][T][ndir][4H]
-  float* c_out;       // optional [B][T][ndir][H]
-};
-struct LstmGroup {
-  LstmParams g[MAX_GROUPS];
-  int tiles, B, T, ndir, nsets, pinned;
-};
-
-template <int HS>
-__global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_kernel(const LstmGroup grp) {
-  constexpr int HID = HS, NW = LstmGeom<HS>::NW, NP = LstmGeom<HS>::NP, NTH = LstmGeom<HS>::NTH, HLD = LstmGeom<HS>::HLD;
-  // two h buffers of [BT][HLD] floats: static up to 256, dynamic at 512 (66 048 bytes, past the 64 KiB of a static allocation)
-  extern __shared__ __attribute__((aligned(16))) float lstm_f32_dyn[];
-  __shared__ __attribute__((aligned(16))) float h_static[HS <= 256 ? 2 * BT * HLD : 4];
-  float* const h_lds0 = HS <= 256 ? h_static : lstm_f32_dyn;
-  // set = (group, direction) owns one W_hh stream (4 * HS * HS floats: 1 MiB at 256); all tiles of a set run on ONE XCD (block b lands on
-  // XCD b % 8) so the stream stays resident in that XCD's 4 MiB L2 instead of every XCD cycling through every set's weights
-  // (only while a set's tiles fit the 32 CUs of an XCD; larger batches keep the plain block order)
-  const int set = grp.pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / grp.tiles) : (int)blockIdx.x / grp.tiles;
-  if (set >= grp.nsets) return;
-  const int gi = set / grp.ndir;
-  const float* __restrict__ xproj = grp.g[gi].xproj;
-  const float* __restrict__ w_hh = grp.g[gi].w_hh;
-  const float* __restrict__ b_hh = grp.g[gi].b_hh;
-  float* __restrict__ out = grp.g[gi].out;
-  float* __restrict__ gates_out = grp.g[gi].gates_out;
-  float* __restrict__ c_out = grp.g[gi].c_out;
-  const int B = grp.B, T = grp.T, ndir = grp.ndir;
-  const int dir = set - gi * grp.ndir;
-  const int b0 = (grp.pinned ? (int)((blockIdx.x / 8) % grp.tiles) : (int)blockIdx.x % grp.tiles) * BT;
-  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
-  const float* W = w_hh + (long)dir * 4 * HID * HID;
-  const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j0 = wave * 16 + col;              // this lane's hidden unit of pass 0 (pass p: + 16 * NW * p)
-
-  for (int i = t_; i < BT * HLD; i += NTH) h_lds0[i] = 0.f;
-  float c[NP][4], bh[NP][4];
-#pragma unroll
-  for (int p = 0; p < NP; ++p)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      c[p][g] = 0.f;
-      bh[p][g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j0 + 16 * NW * p] : 0.f;
-    }
-  __syncthreads();
-
-  // Two passes: the sample index goes through an empty asm inside the step, so the row addresses of the five arrays are formed per step
-  // (a few VALU ops) instead of being hoisted as 64-bit pointers per row, array and pass -- hoisted, they put the kernel 13 registers over
-  // the 128 of a 1024-thread workgroup.  One pass (128, 256): the plain index, the kernel as it was.
-  auto row_of = [](int b) -> int {
-    if constexpr (NP > 1) asm volatile("" : "+v"(b));
-    return b;
-  };
-  for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
-    const int cur = step & 1;
-    const float* h_cur = h_lds0 + cur * (BT * HLD);
-    float* h_new = h_lds0 + (cur ^ 1) * (BT * HLD);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int JP = 16 * NW * p;                // pass p's units sit JP floats behind pass 0's in every row: a constant on pass 0's addresses
-      // input projections of this step: issued first, they land while the recurrent product runs
-      float xg[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = b0 + rbase + r;
-        const float* xp = xproj + ((long)row_of(b < B ? b : 0) * T + t) * (ndir * 4 * HID) + dir * 4 * HID + j0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) xg[g][r] = xp[g * HID + JP];
-      }
-      f32x4 acc[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-      mma_rows<4>(acc, h_cur, HLD, W, HID, wave + NW * p, lane);
-      float h[4], act[4][4];
-      lstm_pointwise(acc, xg, bh[p], c[p], h, act);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rbase + r, b = b0 + row;
-        if (b < B) {
-          const int bs = row_of(b);
-          (out + ((long)bs * T + t) * (ndir * HID) + dir * HID + j0)[JP] = h[r];
-          if (gates_out) {
-            const long base = ((long)bs * T + t) * ndir + dir;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) (gates_out + base * 4 * HID + j0)[g * HID + JP] = act[g][r];
-            (c_out + base * HID + j0)[JP] = c[p][r];
-          }
-        }
-        (h_new + row * HLD + j0)[JP] = b < B ? h[r] : 0.f;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Inference variant of the LSTM layer for the FROZEN experts of the router phase: the recurrent product runs as
-// split-fp16 x3 on v_mfma_f32_16x16x32_f16 (h = hi + lo written to LDS as two fp16 planes by the pointwise stage, W_hh
-// pre-split with a power-of-two prescale into a fragment-major fp16 stream of the same byte size), 96 MFMAs of 16 cycles
-// per wave and step instead of 256 MFMAs of 32 cycles on the exact-fp32 matrix pipe.  Same launch geometry, grouping and
-// XCD pinning as lstm_layer_kernel; no training saves.
-// ---------------------------------------------------------------------------------------------
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr int LDH = HID + 8;   // fp16 LDS row (halves): 528 B, 16 rows hit 16 distinct 16-byte bank groups
-
-// acc[g] += A(16 x K, fp16 hi / lo planes in LDS) . W_g^T with W FRAGMENT-MAJOR fp16:
-//   Wp[(((wave*NG + g)*Q + q)*64 + lane)*2 + {0: hi, 1: lo}] = 8 halves W[g*HID + 16*wave + (lane&15)][32q + 8*(lane>>4) .. +7]
-template <int NG>
-__device__ __forceinline__ void mma_rows_h(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
-                                           const unsigned char* __restrict__ Wp, int K, int wave, int lane, int ld = LDH) {
-  const int n = lane & 15, kg = lane >> 4;
-  const int Q = K / 32;
-  const f16v8* wp = reinterpret_cast<const f16v8*>(Wp) + ((long)wave * NG * Q * 64 + lane) * 2;
-  const _Float16* ah = a_hi + n * ld + kg * 8;
-  const _Float16* al = a_lo + n * ld + kg * 8;
-  f16v8 wh[NG], wl[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    wh[g] = wp[(long)g * Q * 128];
-    wl[g] = wp[(long)g * Q * 128 + 1];
-  }
-#pragma unroll 1
-  for (int q = 0; q < Q; ++q) {
-    f16v8 nh[NG], nl[NG];
-    const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      nh[g] = wp[((long)g * Q + qn) * 128];
-      nl[g] = wp[((long)g * Q + qn) * 128 + 1];
-    }
-    const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + q * 32), xl = *reinterpret_cast<const f16v8*>(al + q * 32);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      wh[g] = nh[g];
-      wl[g] = nl[g];
-    }
-  }
-}
-
-// mma_rows_h with the weight stream behind a buffer resource: scalar (wave, gate, k-step) offsets + one 32-bit lane offset, no 64-bit
-// fragment pointers in the vector file (the pointer form put the decoder kernel 60 registers over its 128)
-template <int NG>
-__device__ __forceinline__ void mma_rows_hb(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
-                                            const __amdgpu_buffer_rsrc_t rw, int K, int wave, int lane, int ld = LDH) {
-  const int n = lane & 15, kg = lane >> 4;
-  const int Q = K / 32;
-  const int wwave = __builtin_amdgcn_readfirstlane(wave) * NG * Q * 2048;
-  const int wlane = lane * 32;
-  auto wfrag = [&](int g, int q, int plane) -> f16v8 {
-    return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + ((g * Q + q) * 128 + plane) * 16, 0));
-  };
-  const _Float16* ah = a_hi + n * ld + kg * 8;
-  const _Float16* al = a_lo + n * ld + kg * 8;
-  f16v8 wh[NG], wl[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    wh[g] = wfrag(g, 0, 0);
-    wl[g] = wfrag(g, 0, 1);
-  }
-#pragma unroll 1
-  for (int q = 0; q < Q; ++q) {
-    f16v8 nh[NG], nl[NG];
-    const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      nh[g] = wfrag(g, qn, 0);
-      nl[g] = wfrag(g, qn, 1);
-    }
-    const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + q * 32), xl = *reinterpret_cast<const f16v8*>(al + q * 32);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      wh[g] = nh[g];
-      wl[g] = nl[g];
-    }
-  }
-}
-
-// mma_rows_hb over the k-steps of the columns [k0, k0 + kn) of a K-wide stream, A holding just those kn columns (see mma_rows_k)
-template <int NG>
-__device__ __forceinline__ void mma_rows_hb_k(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
-                                              const __amdgpu_buffer_rsrc_t rw, int K, int k0, int kn, int wave, int lane, int ld) {
-  const int n = lane & 15, kg = lane >> 4;
-  const int Q = K / 32, q0 = k0 / 32, nq = kn / 32;
-  const int wwave = __builtin_amdgcn_readfirstlane(wave) * NG * Q * 2048;
-  const int wlane = lane * 32;
-  auto wfrag = [&](int g, int q, int plane) -> f16v8 {
-    return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + ((g * Q + q0 + q) * 128 + plane) * 16, 0));
-  };
-  const _Float16* ah = a_hi + n * ld + kg * 8;
-  const _Float16* al = a_lo + n * ld + kg * 8;
-  f16v8 wh[NG], wl[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    wh[g] = wfrag(g, 0, 0);
-    wl[g] = wfrag(g, 0, 1);
-  }
-#pragma unroll 1
-  for (int q = 0; q < nq; ++q) {
-    f16v8 nh[NG], nl[NG];
-    const int qn = (q + 1 < nq) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      nh[g] = wfrag(g, qn, 0);
-      nl[g] = wfrag(g, qn, 1);
-    }
-    const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + q * 32), xl = *reinterpret_cast<const f16v8*>(al + q * 32);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      wh[g] = nh[g];
-      wl[g] = nl[g];
-    }
-  }
-}
-
-__device__ __forceinline__ void store_h_split(_Float16* hi, _Float16* lo, int idx, float v) {
-  _Float16 h, l;
-  split_f16(v, h, l);
-  hi[idx] = h;
-  lo[idx] = l;
-}
-
-struct LstmX3Params {
-  const float* xproj; const unsigned char* w_hh; const float* w_inv; const float* b_hh; float* out;
-  float* gates_out;   // optional training saves, as in LstmParams: [B][T][ndir][4H] post-activation gates
-  float* c_out;       //                                          [B][T][ndir][H] cell state
-};
-struct LstmX3Group {
-  LstmX3Params g[MAX_GROUPS];
-  int tiles, B, T, ndir, nsets, pinned;
-};
-
-// (group, tile) of workgroup blockIdx.x among groups x tiles pairs (the sets of the LSTM layers, the experts of the attention decoders).
-// pinned == 0: group-major; 1: all tiles of a group on XCD (group % 8) (workgroup b runs on XCD b % 8; groups past the last come out
-// >= `groups`: the workgroup returns); 2: the pairs in group-major order cut into eight equal runs, one per XCD
-__device__ __forceinline__ void group_tile(int groups, int tiles, int pinned, int& group, int& tile) {
-  if (pinned == 2) {
-    const int per = groups * tiles / 8;
-    const int pair = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    group = pair / tiles;
-    tile = pair - group * tiles;
-  } else {
-    group = pinned ? (int)(blockIdx.x % 8) + 8 * (int)((blockIdx.x / 8) / tiles) : (int)blockIdx.x / tiles;
-    tile = pinned ? (int)((blockIdx.x / 8) % tiles) : (int)blockIdx.x % tiles;
-  }
-}
-
-// RB: 16-sample row blocks per workgroup.  A workgroup streams the whole W_hh of its (expert, direction) set through one CU every step
-// (1 MiB; 64 B / clk / CU from L2 = 7.8 us), with little MFMA work behind each fragment (96 MFMAs of 16 cycles per wave).  RB = 2 -- the same
-// stream for twice the samples, half as many workgroups per L2 -- was built and measured SLOWER (round 6, tools/bench_lstm.py, B = 256,
-// T = 65: G = 1 17.1 us / step against 11.8, G = 3 21.3 / 14.8, G = 6 22.9 / 15.3): with registers for the next hi fragments only, the
-// second row block's MFMAs wait on the lo fragments instead of hiding them.  RB = 1 is the product form; MRN_LSTM_RB=2 selects the other
-// for an A/B (bit-identical results).
-// The input projection is the accumulators' INITIAL value, scaled by the weights' power-of-two prescale (exact): no registers of its own.
-// Every global access is a buffer instruction (resource + scalar offset + a 32-bit lane offset).  Both changes are round 6's: the form
-// with 64-bit row and fragment pointers in vector registers ran at the 128-register cap; this one takes 100 and is 12-24 % faster
-// (G = 1 13.3 -> 11.8 us / step, G = 3 17.9 -> 14.8, G = 6 20.3 -> 15.3).
-template <int HS, int RB>
-__global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_x3_kernel(const LstmX3Group grp) {
-  constexpr int HID = HS, NW = LstmGeom<HS>::NW, NP = LstmGeom<HS>::NP, NTH = LstmGeom<HS>::NTH, LDH = LstmGeom<HS>::LDH;
-  constexpr int BTX = BT * RB;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lstm_lds[];
-  _Float16* const h_hi = reinterpret_cast<_Float16*>(lstm_lds);        // [2][BTX * LDH]
-  _Float16* const h_lo = h_hi + 2 * BTX * LDH;                         // [2][BTX * LDH]
-  // pinned == 1: all tiles of a (expert, direction) set run on XCD (set % 8), whose L2 then holds that set's W_hh stream (4 * HS * HS * 4 bytes: 1 MiB at 256).
-  // pinned == 2: the (set, tile) pairs in set-major order are cut into eight equal runs, one per XCD (workgroup b runs on XCD b % 8): every
-  // L2 serves the same number of workgroups and at most two or three sets' weights.  The step time follows the number of workgroups
-  // streaming through one L2 (13.1 us at 4, 17.4 at 16, 21.9 at 32): 12 sets = 24 per XCD instead of 32 / 16, 6 sets = 12 instead of 16 / 0.
-  int set, tile;
-  group_tile(grp.nsets, grp.tiles, grp.pinned, set, tile);
-  if (set >= grp.nsets) return;
-  const int gi = set / grp.ndir;
-  const float* __restrict__ xproj = grp.g[gi].xproj;
-  const float* __restrict__ b_hh = grp.g[gi].b_hh;
-  float* __restrict__ out = grp.g[gi].out;
-  float* __restrict__ gates_out = grp.g[gi].gates_out;
-  float* __restrict__ c_out = grp.g[gi].c_out;
-  const int B = grp.B, T = grp.T, ndir = grp.ndir;
-  const int dir = set - gi * grp.ndir;
-  const int b0 = tile * BTX;
-  const int t_ = threadIdx.x, lane = t_ & 63, wave = t_ >> 6;
-  const unsigned char* W = grp.g[gi].w_hh + (long)dir * 4 * HID * HID * 4;     // hi + lo fp16 = 4 bytes per weight
-  const float inv = grp.g[gi].w_inv[dir];
-  const float pre = 1.f / inv;                                                 // the prescale itself (a power of two: exact)
-  const int col = lane & 15, rbase = (lane >> 4) * 4;
-  const int j = wave * 16 + col;                 // this lane's hidden unit of pass 0 (pass p: + 16 * NW * p)
-
-  for (int i = t_; i < BTX * LDH; i += NTH) {
-    h_hi[i] = (_Float16)0.f;
-    h_lo[i] = (_Float16)0.f;
-  }
-  float c[NP][RB][4], bh[NP][4];
-  // per-lane BYTE offsets of this lane's rows in xproj / the gate saves ([B][T][ndir][4H]); the (t, direction) part of an address is
-  // wave-uniform and goes into the scalar base, and the [B][T][ndir][H] arrays' offsets follow from the same registers -- eight
-  // loop-invariant registers instead of a 64-bit pointer per row and array (which the compiler hoisted and, at RB = 2, spilled).
-  // The launcher keeps B * T * ndir * 4H * 4 bytes below 2^32 (larger batches go in several launches)
-  unsigned xoff[RB][4];
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int b = b0 + rb * BT + rbase + r;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) c[p][rb][r] = 0.f;
-      xoff[rb][r] = ((unsigned)(b < B ? b : 0) * (unsigned)(T * ndir * 4 * HID) + (unsigned)j) * 4u;
-    }
-#pragma unroll
-  for (int p = 0; p < NP; ++p)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) bh[p][g] = b_hh ? b_hh[dir * 4 * HID + g * HID + j + 16 * NW * p] : 0.f;
-  __syncthreads();
-
-  // fragment-major weight stream of this wave: [g][q][lane][hi 8 | lo 8 halves] (mma_rows_h's layout)
-  constexpr int Q = HID / 32;
-  // every global access is a buffer instruction -- resource + scalar offset + one 32-bit lane offset: no address lives in the vector file
-  // (as 64-bit pointers per gate / row the compiler hoisted them out of the step loop and, at RB = 2, spilled them)
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 4 * HID * HID * 4, 0x00020000);
-  const int wwave = __builtin_amdgcn_readfirstlane(wave) * (4 * Q * 64 * 32);
-  const int wlane = lane * 32;
-  constexpr int WPASS = NW * (4 * Q * 64 * 32);        // bytes between the unit tiles of two passes of a wave
-  constexpr int UPASS = 16 * NW * 4;                  // bytes between their hidden units in a row of floats
-  const unsigned xbytes = (unsigned)B * (unsigned)(T * ndir * 4 * HID) * 4u;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xproj, 0, xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, xbytes / 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gates_out, 0, gates_out ? xbytes : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)c_out, 0, gates_out ? xbytes / 4 : 0, 0x00020000);
-  const int n = lane & 15, kg = lane >> 4;
-
-  for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
-    const int cur = step & 1;
-    const int tq = (t * ndir + dir) * HID * 4;                                     // (wave-uniform) byte offset in a [..][T][ndir][H] row
-    _Float16* const nhi = h_hi + (cur ^ 1) * BTX * LDH;
-    _Float16* const nlo = h_lo + (cur ^ 1) * BTX * LDH;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      // pass p: unit tile wave + NW * p -- its weight fragments, its columns of every row (a scalar offset on top of pass 0's)
-      auto wfrag = [&](int g, int q, int plane) -> f16v8 {
-        return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + p * WPASS + ((g * Q + q) * 128 + plane) * 16, 0));
-      };
-      f32x4 acc[RB][4];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            acc[rb][g][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)xoff[rb][r], 4 * tq + g * HID * 4 + p * UPASS, 0)) * pre;
-        }
-      {
-        const _Float16* ah = h_hi + cur * BTX * LDH + n * LDH + kg * 8;
-        const _Float16* al = h_lo + cur * BTX * LDH + n * LDH + kg * 8;
-        // RB = 1: the hi and lo fragments of k-step q + 1 are fetched before the MFMAs of step q issue.  RB = 2 has registers for the next hi
-        // fragments only: the lo fragments of step q are fetched at its top and used by its LAST product group
-        constexpr bool PF_LO = RB == 1;
-        f16v8 wh[4], wl[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          wh[g] = wfrag(g, 0, 0);
-          if (PF_LO) wl[g] = wfrag(g, 0, 1);
-        }
-#pragma unroll 1
-        for (int q = 0; q < Q; ++q) {
-          f16v8 nh[4], nl[4];
-          const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            if (!PF_LO) wl[g] = wfrag(g, q, 1);
-            nh[g] = wfrag(g, qn, 0);
-            if (PF_LO) nl[g] = wfrag(g, qn, 1);
-          }
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb) {
-            const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + rb * BT * LDH + q * 32), xl = *reinterpret_cast<const f16v8*>(al + rb * BT * LDH + q * 32);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[rb][g], 0, 0, 0);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[rb][g], 0, 0, 0);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) acc[rb][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[rb][g], 0, 0, 0);
-          }
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            wh[g] = nh[g];
-            if (PF_LO) wl[g] = nl[g];
-          }
-        }
-      }
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[rb][g] *= inv;        // undo the power-of-two weight prescale (exact): x-projection + W_hh . h
-        float h[4], act[4][4];
-        lstm_pointwise0(acc[rb], bh[p], c[p][rb], h, act);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = rb * BT + rbase + r, b = b0 + row;
-          if (b < B) {
-            const int ooff = (int)(((xoff[rb][r] - 4u * (unsigned)j) >> 2) + 4u * (unsigned)j);       // the same row of a [B][T][ndir][H] array
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h[r]), ro, ooff, tq + p * UPASS, 0);
-            if (gates_out) {
-#pragma unroll
-              for (int g = 0; g < 4; ++g) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, act[g][r]), rg, (int)xoff[rb][r], 4 * tq + g * HID * 4 + p * UPASS, 0);
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[p][rb][r]), rc, ooff, tq + p * UPASS, 0);
-            }
-          }
-          store_h_split(nhi, nlo, row * LDH + j + 16 * NW * p, b < B ? h[r] : 0.f);
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// one launch of a filled group
-template <int HS, int RB>
-static int lstm_x3_launch_rb(LstmX3Group& grp, int n, bool may_pin, hipStream_t stream) {
-  constexpr size_t lds = (size_t)4 * BT * RB * LstmGeom<HS>::LDH * sizeof(_Float16);
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)lstm_layer_x3_kernel<HS, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    once = true;
-  }
-  grp.tiles = ceil_div(grp.B, BT * RB);
-  grp.nsets = n * grp.ndir;
-  grp.pinned = 0;
-  int blocks = grp.nsets * grp.tiles;
-  if (may_pin) {
-    grp.pinned = grp.nsets > 2 && grp.tiles * ceil_div(grp.nsets, 8) <= 32;
-    if (grp.pinned) blocks = 8 * ceil_div(grp.nsets, 8) * grp.tiles;
-    static const bool balance = !(getenv("MRN_LSTM_BALANCE") && atoi(getenv("MRN_LSTM_BALANCE")) == 0);     // (A/B switch, read once)
-    if (balance && grp.nsets > 2 && (grp.nsets * grp.tiles) % 8 == 0 && grp.nsets * grp.tiles <= 256) {
-      grp.pinned = 2;
-      blocks = grp.nsets * grp.tiles;
-    }
-  }
-  hipLaunchKernelGGL((lstm_layer_x3_kernel<HS, RB>), dim3(blocks), dim3(LstmGeom<HS>::NTH), lds, stream, grp);
-  return 0;
-}
-template <int HS>
-static int lstm_x3_launch_hs(LstmX3Group& all, int n, bool may_pin, hipStream_t stream) {
-  constexpr int HID = HS;
-  static const int forced = getenv("MRN_LSTM_RB") ? atoi(getenv("MRN_LSTM_RB")) : 0;
-  // the kernel's row offsets are 32-bit byte offsets into [B][T][ndir][4H] floats: batches beyond that go in chunks of whole tiles
-  // (a row is 4 * HS floats per direction and step, so at 512 the chunk boundary falls at half the batch of 256)
-  const long row_bytes = (long)all.T * all.ndir * 4 * HID * 4;
-  const long fit = 0xffffffffL / row_bytes / (2 * BT) * (2 * BT);
-  MRN_CHECK_ARG(fit >= 2 * BT, "lstm x3 layer: T=%d is beyond the kernel's 32-bit row offsets", all.T);
-  for (long s0 = 0; s0 < all.B; s0 += fit) {
-    LstmX3Group grp = all;
-    grp.B = (int)(all.B - s0 < fit ? all.B - s0 : fit);
-    for (int i = 0; i < n; ++i) {
-      LstmX3Params& q = grp.g[i];
-      q.xproj += s0 * (row_bytes / 4);
-      q.out += s0 * (row_bytes / 16);
-      if (q.gates_out) q.gates_out += s0 * (row_bytes / 4);
-      if (q.c_out) q.c_out += s0 * (row_bytes / 16);
-    }
-    int rc;
-    if constexpr (HS <= 256) rc = forced == 2 ? lstm_x3_launch_rb<HS, 2>(grp, n, may_pin, stream) : lstm_x3_launch_rb<HS, 1>(grp, n, may_pin, stream);
-    else rc = lstm_x3_launch_rb<HS, 1>(grp, n, may_pin, stream);     // (RB = 2 with two passes spills at the 128-register cap: not built)
-    if (rc) return rc;
-  }
-  return 0;
-}
-static int lstm_x3_launch(LstmX3Group& all, int n, bool may_pin, int hidden, hipStream_t stream) {
-  switch (hidden) {
-    case 128: return lstm_x3_launch_hs<128>(all, n, may_pin, stream);
-    case 256: return lstm_x3_launch_hs<256>(all, n, may_pin, stream);
-    default: return lstm_x3_launch_hs<512>(all, n, may_pin, stream);
-  }
-}
-
-// (A weight-stationary variant -- W_hh slices in the LDS of 16 workgroups per (expert, direction), h exchanged through L2 every step --
-// was built, bit-identical and measured slower in round 2: G = 3 22.3 us / step against 17.1 streaming, G = 6 23.9 against 22.4; the
-// hand-over of h at agent scope costs more than streaming W_hh.  Removed in round 4; DESIGN.md section 7 keeps the measurements.)
 
 // ---------------------------------------------------------------------------------------------
 // Attention decoder, all S steps in one launch (reference recomputes i2h(H) every step and issues ~10
@@ -665,12 +34,6 @@ struct AttnDecParams {
   int B, T, D, S;
   long eproj_stride_b, eproj_stride_s, hid_stride_b, hid_stride_s;
 };
-
-__device__ __forceinline__ float fast_tanh(float x) {
-  // tanh(x) = 1 - 2/(exp(2x)+1); saturates correctly through inf / 0
-  const float e = __expf(2.f * x);
-  return 1.f - 2.f / (e + 1.f);
-}
 
 struct AttnDecGroup {
   AttnDecParams g[MAX_GROUPS];
@@ -1501,117 +864,9 @@ __global__ __launch_bounds__(NTH) void attn_lexicon_kernel(const BeamGroup grp, 
 
 }  // namespace
 
-static int lstm_launch(LstmGroup& grp, int groups, int hidden, hipStream_t st) {
-  grp.nsets = groups * grp.ndir;
-  grp.pinned = grp.nsets > 2 && grp.tiles * ceil_div(grp.nsets, 8) <= 32;   // (a single layer already fits every L2)
-  const int blocks = grp.pinned ? 8 * ceil_div(grp.nsets, 8) * grp.tiles : grp.nsets * grp.tiles;
-  switch (hidden) {
-    case 128: hipLaunchKernelGGL(lstm_layer_kernel<128>, dim3(blocks), dim3(LstmGeom<128>::NTH), 0, st, grp); break;
-    case 256: hipLaunchKernelGGL(lstm_layer_kernel<256>, dim3(blocks), dim3(LstmGeom<256>::NTH), 0, st, grp); break;
-    default: {
-      constexpr size_t lds = sizeof(float) * 2 * BT * LstmGeom<512>::HLD;
-      static bool once = false;
-      if (!once) {
-        (void)hipFuncSetAttribute((const void*)lstm_layer_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        once = true;
-      }
-      hipLaunchKernelGGL(lstm_layer_kernel<512>, dim3(blocks), dim3(LstmGeom<512>::NTH), lds, st, grp);
-    }
-  }
-  MRN_LAUNCH_CHECK("lstm_layer");
-  return MRN_OK;
-}
-
-static inline bool lstm_hidden_ok(int hidden) { return hidden == 128 || hidden == 256 || hidden == 512; }
-
-MRN_EXPORT int mrn_lstm_layer_fwd_f32(const float* xproj, const float* w_hh, const float* b_hh, float* out,
-                                      float* gates_out, float* c_out, int B, int T, int hidden, int ndir, void* stream) {
-  MRN_CHECK_ARG(xproj && w_hh && out, "mrn_lstm_layer_fwd_f32: null operand");
-  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_f32: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
-  MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_f32: ndir=%d", ndir);
-  MRN_CHECK_ARG((gates_out == nullptr) == (c_out == nullptr), "mrn_lstm_layer_fwd_f32: gates_out / c_out must come together");
-  if (B == 0 || T == 0) return MRN_OK;
-  LstmGroup grp;
-  memset(&grp, 0, sizeof(grp));
-  grp.g[0] = LstmParams{xproj, w_hh, b_hh, out, gates_out, c_out};
-  grp.tiles = ceil_div(B, BT); grp.B = B; grp.T = T; grp.ndir = ndir;
-  return lstm_launch(grp, 1, hidden, (hipStream_t)stream);
-}
-
-// `groups` independent layers of identical geometry in one launch.  xproj / w_hh / b_hh / out are HOST arrays of
-// `groups` device pointers (b_hh may be NULL or hold NULL entries).
-MRN_EXPORT int mrn_lstm_layer_fwd_grouped_f32(const void* const* xproj, const void* const* w_hh, const void* const* b_hh,
-                                              const void* const* out, int groups, int B, int T, int hidden, int ndir,
-                                              void* stream) {
-  MRN_CHECK_ARG(xproj && w_hh && out && groups >= 1, "mrn_lstm_layer_fwd_grouped_f32: null operand");
-  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_grouped_f32: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
-  MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_grouped_f32: ndir=%d", ndir);
-  if (B == 0 || T == 0) return MRN_OK;
-  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-    LstmGroup grp;
-    memset(&grp, 0, sizeof(grp));
-    for (int i = 0; i < n; ++i) {
-      MRN_CHECK_ARG(xproj[g0 + i] && w_hh[g0 + i] && out[g0 + i], "mrn_lstm_layer_fwd_grouped_f32: null operand in group %d", g0 + i);
-      grp.g[i] = LstmParams{(const float*)xproj[g0 + i], (const float*)w_hh[g0 + i], b_hh ? (const float*)b_hh[g0 + i] : nullptr,
-                            (float*)out[g0 + i], nullptr, nullptr};
-    }
-    grp.tiles = ceil_div(B, BT); grp.B = B; grp.T = T; grp.ndir = ndir;
-    const int rc = lstm_launch(grp, n, hidden, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return MRN_OK;
-}
-
-// Inference-only LSTM layers of `groups` frozen experts with the recurrent product on the f16 MFMA (split-fp16 x3).
-// w_hh: HOST array of device pointers to the fragment-major fp16 streams ([ndir][H/16][4][H/32][64][hi 8 | lo 8 halves],
-// ops.pack_fragment_major_h), w_inv: HOST array of device float[ndir] = 1 / prescale of each direction's weights.
-MRN_EXPORT int mrn_lstm_layer_fwd_x3_grouped(const void* const* xproj, const void* const* w_hh, const void* const* w_inv,
-                                             const void* const* b_hh, const void* const* out, int groups, int B, int T,
-                                             int hidden, int ndir, void* stream) {
-  MRN_CHECK_ARG(xproj && w_hh && w_inv && out && groups >= 1, "mrn_lstm_layer_fwd_x3_grouped: null operand");
-  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_x3_grouped: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
-  MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_x3_grouped: ndir=%d", ndir);
-  if (B == 0 || T == 0) return MRN_OK;
-  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-    LstmX3Group grp;
-    memset(&grp, 0, sizeof(grp));
-    for (int i = 0; i < n; ++i) {
-      MRN_CHECK_ARG(xproj[g0 + i] && w_hh[g0 + i] && w_inv[g0 + i] && out[g0 + i], "mrn_lstm_layer_fwd_x3_grouped: null operand in group %d", g0 + i);
-      grp.g[i] = LstmX3Params{(const float*)xproj[g0 + i], (const unsigned char*)w_hh[g0 + i], (const float*)w_inv[g0 + i],
-                              b_hh ? (const float*)b_hh[g0 + i] : nullptr, (float*)out[g0 + i]};
-    }
-    grp.B = B; grp.T = T; grp.ndir = ndir;
-    const int rc = lstm_x3_launch(grp, n, true, hidden, (hipStream_t)stream);
-    if (rc) return rc;
-    MRN_LAUNCH_CHECK("lstm_layer_x3");
-  }
-  return MRN_OK;
-}
-
-// One layer being TRAINED with the recurrent product as split-fp16 x3 (the arithmetic of the trained convolutions, fp16x3s): the
-// forward of mrn_lstm_layer_fwd_x3_grouped for one network, plus the saves mrn_lstm_layer_bwd_f32 reads (gates [B][T][ndir][4H]
-// post-activation, cseq [B][T][ndir][H]).  Half the time per step of the exact-fp32 kernel (96 MFMAs of 16 cycles instead of 256 of 32).
-MRN_EXPORT int mrn_lstm_layer_fwd_x3_save(const float* xproj, const void* w_hh, const float* w_inv, const float* b_hh, float* out,
-                                          float* gates_out, float* c_out, int B, int T, int hidden, int ndir, void* stream) {
-  MRN_CHECK_ARG(xproj && w_hh && w_inv && out && gates_out && c_out, "mrn_lstm_layer_fwd_x3_save: null operand");
-  MRN_CHECK_ARG(lstm_hidden_ok(hidden), "mrn_lstm_layer_fwd_x3_save: hidden=%d unsupported (the LSTM layer kernels are built for 128, 256 and 512)", hidden);
-  MRN_CHECK_ARG(ndir == 1 || ndir == 2, "mrn_lstm_layer_fwd_x3_save: ndir=%d", ndir);
-  if (B == 0 || T == 0) return MRN_OK;
-  LstmX3Group grp;
-  memset(&grp, 0, sizeof(grp));
-  grp.g[0] = LstmX3Params{xproj, (const unsigned char*)w_hh, w_inv, b_hh, out, gates_out, c_out};
-  grp.B = B; grp.T = T; grp.ndir = ndir;
-  const int rc = lstm_x3_launch(grp, 1, false, hidden, (hipStream_t)stream);
-  if (rc) return rc;
-  MRN_LAUNCH_CHECK("lstm_layer_x3_save");
-  return MRN_OK;
-}
-
 // ---- launch rules of the three attention decoder kernels ------------------------------------------------------
-// LDS bytes of AttnTile's map for dc context columns and T frames plus the launching kernel's own arrays.  ops.attn_decoder_whole_context,
-// ops.attn_greedy_whole_context and ops.attn_beam_whole_context restate the sum
+// LDS bytes of AttnTile's map for dc context columns and T frames plus the launching kernel's own arrays.  ops._attn_tile_lds restates
+// the sum for the four ops.attn_*_whole_context rules
 static size_t attn_tile_lds(bool x3, int dc, int T, size_t extra) {
   return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra;
 }
@@ -1789,23 +1044,70 @@ static int greedy_launch(GreedyGroup& grp, int groups, int D, int T, hipStream_t
   return MRN_OK;
 }
 
-static void greedy_fill(GreedyParams& gp, const float* Hb, const float* Hproj, const float* etab, const int64_t* start,
-                        const float* w_h2h, const float* b_h2h, const float* w_score, const float* w_ih_ctx, const float* w_hh,
-                        const float* w_inv, const float* b_hh, const float* w_gen, const float* b_gen, int num_class, float* logits,
-                        int64_t stride_b, int64_t stride_s, int64_t* tokens_out, int B, int T, int D, int S) {
-  memset(&gp, 0, sizeof(gp));
-  AttnDecParams& p = gp.a;
-  p.Hb = Hb; p.Hproj = Hproj; p.w_h2h = w_h2h; p.b_h2h = b_h2h; p.w_score = w_score;
-  p.w_ih = w_ih_ctx; p.w_hh = w_hh; p.w_inv = w_inv; p.b_hh = b_hh;
-  p.B = B; p.T = T; p.D = D; p.S = S;
-  gp.etab = etab; gp.start = start; gp.w_gen = w_gen; gp.b_gen = b_gen; gp.num_class = num_class;
-  gp.logits = logits; gp.logits_stride_b = stride_b; gp.logits_stride_s = stride_s; gp.tokens_out = tokens_out;
+// What the greedy, beam and lexicon entry points share, as it arrives: HOST arrays of `groups` device pointers (b_hh may be NULL or hold
+// NULL entries; w_inv is read in the x3 form only), a class count per group, the shared start token and geometry
+typedef const void* const* PtrArray;
+struct DecodeOperands {
+  PtrArray Hb, Hproj, etab;
+  const int64_t* start_token;
+  PtrArray w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen;
+  const int* num_class;
+  int B, T, D, S;
+};
+static bool decode_arrays_given(const DecodeOperands& o, bool x3) {
+  return o.Hb && o.Hproj && o.etab && o.start_token && o.w_h2h && o.b_h2h && o.w_score && o.w_ih_ctx && o.w_hh && (!x3 || o.w_inv) &&
+         o.w_gen && o.b_gen && o.num_class;
+}
+static bool decode_group_given(const DecodeOperands& o, bool x3, int g) {
+  return o.Hb[g] && o.Hproj[g] && o.etab[g] && o.w_h2h[g] && o.b_h2h[g] && o.w_score[g] && o.w_ih_ctx[g] && o.w_hh[g] &&
+         (!x3 || o.w_inv[g]) && o.w_gen[g] && o.b_gen[g];
 }
 
-#define MRN_GREEDY_CHECKS(who, dmul)                                                                                              \
-  MRN_CHECK_ARG(hidden == HID, who ": hidden=%d unsupported (library is built for %d)", hidden, HID);                             \
-  MRN_CHECK_ARG(D % dmul == 0 && D > 0, who ": D=%d must be a multiple of %d", D, dmul);                                          \
-  MRN_CHECK_ARG(B >= 0 && T > 0 && S >= 0, who ": bad geometry (B=%d T=%d S=%d)", B, T, S)
+// group g's operands; the outputs (zero here) are the caller's
+static void greedy_fill(GreedyParams& gp, const DecodeOperands& o, bool x3, int g) {
+  memset(&gp, 0, sizeof(gp));
+  AttnDecParams& p = gp.a;
+  p.Hb = (const float*)o.Hb[g]; p.Hproj = (const float*)o.Hproj[g];
+  p.w_h2h = (const float*)o.w_h2h[g]; p.b_h2h = (const float*)o.b_h2h[g]; p.w_score = (const float*)o.w_score[g];
+  p.w_ih = (const float*)o.w_ih_ctx[g]; p.w_hh = (const float*)o.w_hh[g];
+  p.w_inv = x3 ? (const float*)o.w_inv[g] : nullptr; p.b_hh = o.b_hh ? (const float*)o.b_hh[g] : nullptr;
+  p.B = o.B; p.T = o.T; p.D = o.D; p.S = o.S;
+  gp.etab = (const float*)o.etab[g]; gp.start = o.start_token;
+  gp.w_gen = (const float*)o.w_gen[g]; gp.b_gen = (const float*)o.b_gen[g]; gp.num_class = o.num_class[g];
+}
+
+// The four greedy entry points: `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch (several
+// beyond MAX_GROUPS).  logits and tokens_out are HOST arrays of `groups` device pointers, the two logits strides host arrays of `groups`
+// values; tokens_out may be NULL.  The single-expert entry points (`single`) pass arrays of one
+static int greedy_grouped(const char* who, bool x3, bool single, const DecodeOperands& o, PtrArray logits, const int64_t* logits_stride_b,
+                          const int64_t* logits_stride_s, PtrArray tokens_out, int groups, int hidden, void* stream) {
+  const int B = o.B, T = o.T, D = o.D, S = o.S;
+  auto given = [&](int g) { return decode_group_given(o, x3, g) && logits[g]; };
+  MRN_CHECK_ARG(decode_arrays_given(o, x3) && logits && logits_stride_b && logits_stride_s && groups >= 1 && (!single || given(0)),
+                "%s: null operand", who);
+  MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
+  MRN_CHECK_ARG(D % (x3 ? 32 : 16) == 0 && D > 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
+  MRN_CHECK_ARG(B >= 0 && T > 0 && S >= 0, "%s: bad geometry (B=%d T=%d S=%d)", who, B, T, S);
+  MRN_CHECK_ARG(!single || o.num_class[0] >= 1, "%s: num_class=%d", who, o.num_class[0]);
+  if (B == 0 || S == 0) return MRN_OK;
+  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
+    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
+    GreedyGroup grp;
+    memset(&grp, 0, sizeof(grp));
+    for (int i = 0; i < n; ++i) {
+      const int g = g0 + i;
+      MRN_CHECK_ARG(given(g), "%s: null operand in group %d", who, g);
+      MRN_CHECK_ARG(o.num_class[g] >= 1, "%s: num_class=%d in group %d", who, o.num_class[g], g);
+      GreedyParams& gp = grp.g[i];
+      greedy_fill(gp, o, x3, g);
+      gp.logits = (float*)logits[g]; gp.logits_stride_b = logits_stride_b[g]; gp.logits_stride_s = logits_stride_s[g];
+      gp.tokens_out = tokens_out ? (int64_t*)tokens_out[g] : nullptr;
+    }
+    const int rc = greedy_launch(grp, n, D, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return MRN_OK;
+}
 
 // Greedy decoding of one expert: S steps, argmax fed back inside the launch (reference modules/prediction.py:70-86).
 MRN_EXPORT int mrn_attn_greedy_decode_f32(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
@@ -1813,16 +1115,9 @@ MRN_EXPORT int mrn_attn_greedy_decode_f32(const float* Hb, const float* Hproj, c
                                           const float* w_hh, const float* b_hh, const float* w_gen, const float* b_gen, int num_class,
                                           float* logits, int64_t logits_stride_b, int64_t logits_stride_s, int64_t* tokens_out, int B,
                                           int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_gen && b_gen && logits,
-                "mrn_attn_greedy_decode_f32: null operand");
-  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_f32", 16);
-  MRN_CHECK_ARG(num_class >= 1, "mrn_attn_greedy_decode_f32: num_class=%d", num_class);
-  if (B == 0 || S == 0) return MRN_OK;
-  GreedyGroup grp;
-  memset(&grp, 0, sizeof(grp));
-  greedy_fill(grp.g[0], Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class,
-              logits, logits_stride_b, logits_stride_s, tokens_out, B, T, D, S);
-  return greedy_launch(grp, 1, D, T, (hipStream_t)stream);
+  const void* const a[] = {Hb, Hproj, etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, logits, tokens_out};
+  const DecodeOperands o{a, a + 1, a + 2, start_token, a + 3, a + 4, a + 5, a + 6, a + 7, nullptr, a + 8, a + 9, a + 10, &num_class, B, T, D, S};
+  return greedy_grouped("mrn_attn_greedy_decode_f32", false, true, o, a + 11, &logits_stride_b, &logits_stride_s, a + 12, 1, hidden, stream);
 }
 
 MRN_EXPORT int mrn_attn_greedy_decode_x3(const float* Hb, const float* Hproj, const float* etab, const int64_t* start_token,
@@ -1830,46 +1125,9 @@ MRN_EXPORT int mrn_attn_greedy_decode_x3(const float* Hb, const float* Hproj, co
                                          const void* w_hh, const float* w_inv, const float* b_hh, const void* w_gen, const float* b_gen,
                                          int num_class, float* logits, int64_t logits_stride_b, int64_t logits_stride_s,
                                          int64_t* tokens_out, int B, int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && w_gen && b_gen && logits,
-                "mrn_attn_greedy_decode_x3: null operand");
-  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_x3", 32);
-  MRN_CHECK_ARG(num_class >= 1, "mrn_attn_greedy_decode_x3: num_class=%d", num_class);
-  if (B == 0 || S == 0) return MRN_OK;
-  GreedyGroup grp;
-  memset(&grp, 0, sizeof(grp));
-  greedy_fill(grp.g[0], Hb, Hproj, etab, start_token, (const float*)w_h2h, b_h2h, w_score, (const float*)w_ih_ctx, (const float*)w_hh,
-              w_inv, b_hh, (const float*)w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, B, T, D, S);
-  return greedy_launch(grp, 1, D, T, (hipStream_t)stream);
-}
-
-// `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch (several beyond MAX_GROUPS).  Every
-// pointer argument is a HOST array of `groups` device pointers, num_class and the two logits strides host arrays of `groups` values; the start token is shared; tokens_out may be NULL.  x3 == false: w_inv is ignored.
-static int greedy_grouped(const char* who, bool x3, const void* const* Hb, const void* const* Hproj, const void* const* etab,
-                          const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h, const void* const* w_score,
-                          const void* const* w_ih_ctx, const void* const* w_hh, const void* const* w_inv, const void* const* b_hh,
-                          const void* const* w_gen, const void* const* b_gen, const int* num_class, const void* const* logits,
-                          const int64_t* logits_stride_b, const int64_t* logits_stride_s, const void* const* tokens_out, int groups, int B, int T,
-                          int D, int S, void* stream) {
-  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-    GreedyGroup grp;
-    memset(&grp, 0, sizeof(grp));
-    for (int i = 0; i < n; ++i) {
-      const int g = g0 + i;
-      MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&
-                        w_gen[g] && b_gen[g] && logits[g],
-                    "%s: null operand in group %d", who, g);
-      MRN_CHECK_ARG(num_class[g] >= 1, "%s: num_class=%d in group %d", who, num_class[g], g);
-      greedy_fill(grp.g[i], (const float*)Hb[g], (const float*)Hproj[g], (const float*)etab[g], start_token, (const float*)w_h2h[g],
-                  (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g], (const float*)w_hh[g],
-                  x3 ? (const float*)w_inv[g] : nullptr, b_hh ? (const float*)b_hh[g] : nullptr, (const float*)w_gen[g],
-                  (const float*)b_gen[g], num_class[g], (float*)logits[g], logits_stride_b[g], logits_stride_s[g],
-                  tokens_out ? (int64_t*)tokens_out[g] : nullptr, B, T, D, S);
-    }
-    const int rc = greedy_launch(grp, n, D, T, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return MRN_OK;
+  const void* const a[] = {Hb, Hproj, etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, logits, tokens_out};
+  const DecodeOperands o{a, a + 1, a + 2, start_token, a + 3, a + 4, a + 5, a + 6, a + 7, a + 8, a + 9, a + 10, a + 11, &num_class, B, T, D, S};
+  return greedy_grouped("mrn_attn_greedy_decode_x3", true, true, o, a + 12, &logits_stride_b, &logits_stride_s, a + 13, 1, hidden, stream);
 }
 
 MRN_EXPORT int mrn_attn_greedy_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
@@ -1879,13 +1137,9 @@ MRN_EXPORT int mrn_attn_greedy_decode_grouped_f32(const void* const* Hb, const v
                                                   const int* num_class, const void* const* logits, const int64_t* logits_stride_b,
                                                   const int64_t* logits_stride_s, const void* const* tokens_out, int groups, int B, int T,
                                                   int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_gen && b_gen && num_class &&
-                    logits && logits_stride_b && logits_stride_s && groups >= 1, "mrn_attn_greedy_decode_grouped_f32: null operand");
-  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_grouped_f32", 16);
-  if (B == 0 || S == 0) return MRN_OK;
-  return greedy_grouped("mrn_attn_greedy_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
-                        nullptr, b_hh, w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, groups, B, T, D, S,
-                        stream);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return greedy_grouped("mrn_attn_greedy_decode_grouped_f32", false, false, o, logits, logits_stride_b, logits_stride_s, tokens_out, groups,
+                        hidden, stream);
 }
 
 MRN_EXPORT int mrn_attn_greedy_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
@@ -1895,13 +1149,9 @@ MRN_EXPORT int mrn_attn_greedy_decode_x3_grouped(const void* const* Hb, const vo
                                                  const void* const* b_gen, const int* num_class, const void* const* logits,
                                                  const int64_t* logits_stride_b, const int64_t* logits_stride_s, const void* const* tokens_out,
                                                  int groups, int B, int T, int D, int S, int hidden, void* stream) {
-  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && w_inv && w_gen && b_gen &&
-                    num_class && logits && logits_stride_b && logits_stride_s && groups >= 1, "mrn_attn_greedy_decode_x3_grouped: null operand");
-  MRN_GREEDY_CHECKS("mrn_attn_greedy_decode_x3_grouped", 32);
-  if (B == 0 || S == 0) return MRN_OK;
-  return greedy_grouped("mrn_attn_greedy_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
-                        w_inv, b_hh, w_gen, b_gen, num_class, logits, logits_stride_b, logits_stride_s, tokens_out, groups, B, T, D, S,
-                        stream);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return greedy_grouped("mrn_attn_greedy_decode_x3_grouped", true, false, o, logits, logits_stride_b, logits_stride_s, tokens_out, groups,
+                        hidden, stream);
 }
 
 MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, const float* table, float* out, int B,
@@ -1941,26 +1191,29 @@ static int beam_launch(BeamGroup& grp, const LexTrie* lex, int groups, int D, in
   return MRN_OK;
 }
 
+// the lexicon entry points' trie, as it arrives: four device arrays shared by the groups, a HOST array `word` of `groups` device pointers
+struct LexOperands {
+  const int32_t *child_off, *child_tok, *child_node, *word_of;
+  int nodes, depth;
+  PtrArray word;
+};
+
 // `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch per MAX_GROUPS experts.  Every limit is
-// checked for every group before the first launch
-static int beam_grouped(const char* who, bool x3, const void* const* Hb, const void* const* Hproj, const void* const* etab,
-                        const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h, const void* const* w_score,
-                        const void* const* w_ih_ctx, const void* const* w_hh, const void* const* w_inv, const void* const* b_hh,
-                        const void* const* w_gen, const void* const* b_gen, const int* num_class, int eos, int W,
-                        const void* const* scratch, int64_t scratch_floats, const void* const* tokens, const void* const* length,
-                        const void* const* score, const void* const* logp, const void* const* path, const void* const* prob,
-                        int groups, int B, int T, int D, int S, int hidden, void* stream, bool lexicon = false,
-                        const void* child_off = nullptr, const void* child_tok = nullptr, const void* child_node = nullptr,
-                        const void* word_of = nullptr, int nodes = 0, int depth = 0, const void* const* word = nullptr) {
-  MRN_CHECK_ARG(Hb && Hproj && etab && start_token && w_h2h && b_h2h && w_score && w_ih_ctx && w_hh && (!x3 || w_inv) && w_gen && b_gen &&
-                    num_class && scratch && tokens && length && score && logp && path && prob && groups >= 1, "%s: null operand", who);
+// checked for every group before the first launch.  trie: null, or the lexicon of the two lexicon entry points
+static int beam_grouped(const char* who, bool x3, const DecodeOperands& o, int eos, int W, PtrArray scratch, int64_t scratch_floats,
+                        PtrArray tokens, PtrArray length, PtrArray score, PtrArray logp, PtrArray path, PtrArray prob, int groups,
+                        int hidden, void* stream, const LexOperands* trie = nullptr) {
+  const int B = o.B, T = o.T, D = o.D, S = o.S;
+  MRN_CHECK_ARG(decode_arrays_given(o, x3) && scratch && tokens && length && score && logp && path && prob && groups >= 1,
+                "%s: null operand", who);
   MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
   MRN_CHECK_ARG(W >= 1 && W <= BT, "%s: beam width W=%d outside 1 ... %d", who, W, BT);
   MRN_CHECK_ARG(S >= 1 && S <= 512, "%s: S=%d steps outside 1 ... 512", who, S);
   MRN_CHECK_ARG(D > 0 && D % (x3 ? 32 : 16) == 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
   MRN_CHECK_ARG(B >= 0 && T > 0, "%s: bad geometry (B=%d T=%d)", who, B, T);
   MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
-  if (lexicon) {
+  if (trie) {
+    const auto [child_off, child_tok, child_node, word_of, nodes, depth, word] = *trie;
     MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA + LEX_LDS_MORE) <= 160 * 1024,
                   "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
     MRN_CHECK_ARG(child_off && child_tok && child_node && word_of && word, "%s: null trie operand", who);
@@ -1970,12 +1223,12 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
   }
   const long tiles = ceil_div(B, BT / W);
   for (int g = 0; g < groups; ++g) {
-    MRN_CHECK_ARG(Hb[g] && Hproj[g] && etab[g] && w_h2h[g] && b_h2h[g] && w_score[g] && w_ih_ctx[g] && w_hh[g] && (!x3 || w_inv[g]) &&
-                      w_gen[g] && b_gen[g] && (B == 0 || (scratch[g] && tokens[g] && length[g] && score[g] && logp[g] && path[g] && prob[g])),
+    MRN_CHECK_ARG(decode_group_given(o, x3, g) &&
+                      (B == 0 || (scratch[g] && tokens[g] && length[g] && score[g] && logp[g] && path[g] && prob[g])),
                   "%s: null operand in group %d", who, g);
-    MRN_CHECK_ARG(num_class[g] >= 2, "%s: num_class=%d in group %d (at least 2)", who, num_class[g], g);
-    MRN_CHECK_ARG(eos >= 0 && eos < num_class[g], "%s: eos=%d outside the %d classes of group %d", who, eos, num_class[g], g);
-    const long need = tiles * BT * ((long)ceil_div(num_class[g], 16) * 16 + 3L * S);
+    MRN_CHECK_ARG(o.num_class[g] >= 2, "%s: num_class=%d in group %d (at least 2)", who, o.num_class[g], g);
+    MRN_CHECK_ARG(eos >= 0 && eos < o.num_class[g], "%s: eos=%d outside the %d classes of group %d", who, eos, o.num_class[g], g);
+    const long need = tiles * BT * ((long)ceil_div(o.num_class[g], 16) * 16 + 3L * S);
     MRN_CHECK_ARG(scratch_floats >= need, "%s: scratch of %ld floats, group %d needs %ld", who, (long)scratch_floats, g, need);
   }
   if (B == 0) return MRN_OK;
@@ -1988,10 +1241,7 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
     for (int i = 0; i < n; ++i) {
       const int g = g0 + i;
       BeamParams& bp = grp.g[i];
-      greedy_fill(bp.g, (const float*)Hb[g], (const float*)Hproj[g], (const float*)etab[g], start_token, (const float*)w_h2h[g],
-                  (const float*)b_h2h[g], (const float*)w_score[g], (const float*)w_ih_ctx[g], (const float*)w_hh[g],
-                  x3 ? (const float*)w_inv[g] : nullptr, b_hh ? (const float*)b_hh[g] : nullptr, (const float*)w_gen[g],
-                  (const float*)b_gen[g], num_class[g], nullptr, 0, 0, nullptr, B, T, D, S);
+      greedy_fill(bp.g, o, x3, g);
       bp.scratch = (float*)scratch[g];
       bp.tokens = (int32_t*)tokens[g];
       bp.length = (int32_t*)length[g];
@@ -2001,11 +1251,11 @@ static int beam_grouped(const char* who, bool x3, const void* const* Hb, const v
       bp.prob = (float*)prob[g];
     }
     LexTrie lex;
-    if (lexicon) {
-      lex = LexTrie{(const int32_t*)child_off, (const int32_t*)child_tok, (const int32_t*)child_node, (const int32_t*)word_of, {}, nodes};
-      for (int i = 0; i < n; ++i) lex.word[i] = (int32_t*)word[g0 + i];
+    if (trie) {
+      lex = LexTrie{trie->child_off, trie->child_tok, trie->child_node, trie->word_of, {}, trie->nodes};
+      for (int i = 0; i < n; ++i) lex.word[i] = (int32_t*)trie->word[g0 + i];
     }
-    const int rc = beam_launch(grp, lexicon ? &lex : nullptr, n, D, T, (hipStream_t)stream);
+    const int rc = beam_launch(grp, trie ? &lex : nullptr, n, D, T, (hipStream_t)stream);
     if (rc) return rc;
   }
   return MRN_OK;
@@ -2019,9 +1269,9 @@ MRN_EXPORT int mrn_attn_beam_decode_grouped_f32(const void* const* Hb, const voi
                                                 const void* const* tokens, const void* const* length, const void* const* score,
                                                 const void* const* logp, const void* const* path, const void* const* prob, int groups,
                                                 int B, int T, int D, int S, int hidden, void* stream) {
-  return beam_grouped("mrn_attn_beam_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
-                      nullptr, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
-                      groups, B, T, D, S, hidden, stream);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return beam_grouped("mrn_attn_beam_decode_grouped_f32", false, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, hidden, stream);
 }
 
 MRN_EXPORT int mrn_attn_beam_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
@@ -2033,9 +1283,9 @@ MRN_EXPORT int mrn_attn_beam_decode_x3_grouped(const void* const* Hb, const void
                                                const void* const* length, const void* const* score, const void* const* logp,
                                                const void* const* path, const void* const* prob, int groups, int B, int T, int D, int S,
                                                int hidden, void* stream) {
-  return beam_grouped("mrn_attn_beam_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv,
-                      b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob, groups, B,
-                      T, D, S, hidden, stream);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return beam_grouped("mrn_attn_beam_decode_x3_grouped", true, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, hidden, stream);
 }
 
 // ---- lexicon-constrained beam search on the attention head: attn_lexicon_kernel (include/mrn_attn_lexicon.h) ----
@@ -2050,9 +1300,10 @@ MRN_EXPORT int mrn_attn_lexicon_decode_grouped_f32(const void* const* Hb, const 
                                                    const void* const* logp, const void* const* path, const void* const* prob,
                                                    const void* const* word, int groups, int B, int T, int D, int S, int hidden,
                                                    void* stream) {
-  return beam_grouped("mrn_attn_lexicon_decode_grouped_f32", false, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
-                      nullptr, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
-                      groups, B, T, D, S, hidden, stream, true, child_off, child_tok, child_node, word_of, nodes, depth, word);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  const LexOperands trie{child_off, child_tok, child_node, word_of, nodes, depth, word};
+  return beam_grouped("mrn_attn_lexicon_decode_grouped_f32", false, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path,
+                      prob, groups, hidden, stream, &trie);
 }
 
 MRN_EXPORT int mrn_attn_lexicon_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
@@ -2066,7 +1317,8 @@ MRN_EXPORT int mrn_attn_lexicon_decode_x3_grouped(const void* const* Hb, const v
                                                   const void* const* score, const void* const* logp, const void* const* path,
                                                   const void* const* prob, const void* const* word, int groups, int B, int T, int D, int S,
                                                   int hidden, void* stream) {
-  return beam_grouped("mrn_attn_lexicon_decode_x3_grouped", true, Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh,
-                      w_inv, b_hh, w_gen, b_gen, num_class, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob, groups,
-                      B, T, D, S, hidden, stream, true, child_off, child_tok, child_node, word_of, nodes, depth, word);
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  const LexOperands trie{child_off, child_tok, child_node, word_of, nodes, depth, word};
+  return beam_grouped("mrn_attn_lexicon_decode_x3_grouped", true, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, hidden, stream, &trie);
 }

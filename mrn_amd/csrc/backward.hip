@@ -3,7 +3,7 @@
 // backward fused with the ReLU mask, max-pool backward, LSTM backward-through-time.
 // Convolution data / weight gradients themselves are implicit GEMMs on the forward kernels (gemm.hip):
 //   dgrad = conv(dy, flipped-transposed weight), wgrad = mrn_conv2d_wgrad_f32.
-#include "common.hpp"
+#include "recurrent.hpp"
 
 namespace {
 
@@ -223,10 +223,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_disjoint_kernel(const float* 
 }
 
 // ---- LSTM backward through time ------------------------------------------------------------------------
-// Templates over the hidden size HS in {128, 256, 512} with the forward kernels' geometry (rnn.hip, LstmGeom): 8 waves at 128, 16 at 256,
+// Templates over the hidden size HS in {128, 256, 512} with the forward kernels' geometry (lstm.hip; recurrent.hpp: LstmGeom, BT, mfma4): 8 waves at 128, 16 at 256,
 // and at 512 16 waves that each own the hidden units of two 16-unit tiles (w and w + 16, NP = 2 passes).  A step first writes the gate
 // gradients of ALL of a wave's units to LDS, then -- behind the barrier -- forms dh_rec of all of them: no pass reads a half-written row.
-constexpr int BT = 16;
 template <int HS>
 struct LstmBwdGeom {
   static_assert(HS == 128 || HS == 256 || HS == 512, "LSTM backward kernels: hidden size 128, 256 or 512");
@@ -236,10 +235,6 @@ struct LstmBwdGeom {
   static constexpr int GLD = 4 * HS + 4;      // fp32 LDS row
   static constexpr int GLDH = 4 * HS + 8;     // fp16 LDS row (halves)
 };
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // gates [B][T][ndir][4H] (post-activation i,f,g,o), cseq [B][T][ndir][H], dout [B][T][ndir*H]
 // w_hhT: fragment-major W_hh^T (rows = hidden unit j, K = 4H gate index), one gate group

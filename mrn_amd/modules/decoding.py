@@ -22,7 +22,7 @@ neighbours, blanks behind (the greedy collapse gives the prefix back) and prob [
 is exp(score): multiplying by 1.0 is exact).
 
 The attention head (reference modules/prediction.py:70-86 feeds the arg-max back: one hypothesis) is decoded by beam search with
-opt.attn_decode = "beam"; the width is opt.beam_width.  mrn_attn_beam_decode_* (mrn_amd/csrc/rnn.hip attn_beam_kernel) runs it in
+opt.attn_decode = "beam"; the width is opt.beam_width.  mrn_attn_beam_decode_* (mrn_amd/csrc/attn_decode.hip attn_beam_kernel) runs it in
 float32, all steps of all experts in one launch, attn_beam_host below in float64.  Per sample: width W, S = batch_max_length + 1 steps,
 start token sos, end token eos.  An entry is (tokens, score, finished, h, c).  Start: one live entry (no tokens, score 0, h = c = 0, fed
 sos); the other W - 1 slots are dead (score -inf).  Per step:
@@ -450,7 +450,7 @@ def ctc_lexicon_host(logits, lex_tokens, lex_len, n, cand=None):
 
 # ---- lexicon-constrained decoding on the attention head ------------------------------------------------------------------------------
 # With opt.attn_lexicon (a sequence of words) an attention head is decoded by the beam search above walked along a trie of the lexicon:
-# mrn_attn_lexicon_decode_* (mrn_amd/csrc/rnn.hip attn_lexicon_kernel) runs it in float32, all steps of all experts in one launch,
+# mrn_attn_lexicon_decode_* (mrn_amd/csrc/attn_decode.hip attn_lexicon_kernel) runs it in float32, all steps of all experts in one launch,
 # attn_lexicon_host below in float64.  (Scoring every (sample, word) pair, as the CTC lexicon decoder does, would give every pair a
 # recurrent roll-out of its own.)  The trie: node 0 is the root, nodes are numbered breadth-first with a node's children in ascending
 # class order, so the numbering does not depend on the order of the words and a child's index is above its parent's; the children of

@@ -1337,9 +1337,19 @@ def lstm_layer_x3_save(xproj, w_hh_h, w_inv, b_hh, hidden, ndir):
     return out, gates, cseq
 
 
-def _ptr_array(ptrs):
+def _ptrs(ts):
+    """host array of the device addresses of a list of tensors (or of a tensor's slices along its first dimension)"""
     import ctypes
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _x3_call(stem, grouped, w_inv, head, tail):
+    """one call site for an f32 / x3 pair of attention entry points: mrn_<stem>_f32 (grouped: mrn_<stem>_grouped_f32) without w_inv; with
+    it mrn_<stem>_x3 (mrn_<stem>_x3_grouped) and w_inv -- a tensor, grouped: a list of them -- where every x3 prototype has it, between
+    head (ending with w_hh) and tail (starting with b_hh)"""
+    if w_inv is None:
+        return call(f"mrn_{stem}_grouped_f32" if grouped else f"mrn_{stem}_f32", *head, *tail)
+    return call(f"mrn_{stem}_x3_grouped" if grouped else f"mrn_{stem}_x3", *head, _ptrs(w_inv) if grouped else _p(w_inv), *tail)
 
 
 def pack_fragment_major_h(w, hidden=256):
@@ -1361,10 +1371,7 @@ def lstm_layer_x3_grouped(xproj, w_hh_h, w_inv, b_hh, hidden, ndir):
     G, B, T, _ = xproj.shape
     assert xproj.is_contiguous() and w_hh_h.is_contiguous() and w_inv.is_contiguous() and b_hh.is_contiguous()
     out = torch.empty(G, B, T, ndir * hidden, device=xproj.device, dtype=torch.float32)
-    call("mrn_lstm_layer_fwd_x3_grouped", _ptr_array([xproj[g].data_ptr() for g in range(G)]),
-         _ptr_array([w_hh_h[g].data_ptr() for g in range(G)]), _ptr_array([w_inv[g].data_ptr() for g in range(G)]),
-         _ptr_array([b_hh[g].data_ptr() for g in range(G)]), _ptr_array([out[g].data_ptr() for g in range(G)]), G, B, T,
-         hidden, ndir, _stream())
+    call("mrn_lstm_layer_fwd_x3_grouped", _ptrs(xproj), _ptrs(w_hh_h), _ptrs(w_inv), _ptrs(b_hh), _ptrs(out), G, B, T, hidden, ndir, _stream())
     return out
 
 
@@ -1379,9 +1386,7 @@ def lstm_layer_grouped(xproj, w_hh, b_hh, hidden, ndir):
     G, B, T, _ = xproj.shape
     assert xproj.is_contiguous() and w_hh.is_contiguous() and b_hh.is_contiguous()
     out = torch.empty(G, B, T, ndir * hidden, device=xproj.device, dtype=torch.float32)
-    call("mrn_lstm_layer_fwd_grouped_f32", _ptr_array([xproj[g].data_ptr() for g in range(G)]),
-         _ptr_array([w_hh[g].data_ptr() for g in range(G)]), _ptr_array([b_hh[g].data_ptr() for g in range(G)]),
-         _ptr_array([out[g].data_ptr() for g in range(G)]), G, B, T, hidden, ndir, _stream())
+    call("mrn_lstm_layer_fwd_grouped_f32", _ptrs(xproj), _ptrs(w_hh), _ptrs(b_hh), _ptrs(out), G, B, T, hidden, ndir, _stream())
     return out
 
 
@@ -1392,41 +1397,38 @@ def attn_decoder_grouped(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_
     S = eproj.shape[2]
     assert Hb.is_contiguous() and Hproj.is_contiguous() and eproj.is_contiguous()
     hid = torch.empty(G, B, S, hidden, device=Hb.device, dtype=torch.float32)
-
-    def arr(ts):
-        return _ptr_array([t.data_ptr() for t in ts])
-    if w_inv is not None:          # x3 form: the weight lists hold pack_fragment_major_h streams, w_inv a list of device float[3]
-        call("mrn_attn_decoder_fwd_x3_grouped", arr(Hb), arr(Hproj), arr(eproj), eproj.stride(1), eproj.stride(2), arr(w_h2h),
-             arr(b_h2h), arr(w_score), arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(hid), hid.stride(1), hid.stride(2), G, B, T, D, S,
-             hidden, _stream())
-        return hid
-    call("mrn_attn_decoder_fwd_grouped_f32", arr(Hb), arr(Hproj), arr(eproj), eproj.stride(1), eproj.stride(2), arr(w_h2h),
-         arr(b_h2h), arr(w_score), arr(w_ih), arr(w_hh), arr(b_hh), arr(hid), hid.stride(1), hid.stride(2), G, B, T, D, S,
-         hidden, _stream())
+    # x3 form: the weight lists hold pack_fragment_major_h streams, w_inv a list of device float[3]
+    _x3_call("attn_decoder_fwd", True, w_inv,
+             (_ptrs(Hb), _ptrs(Hproj), _ptrs(eproj), eproj.stride(1), eproj.stride(2), _ptrs(w_h2h), _ptrs(b_h2h), _ptrs(w_score), _ptrs(w_ih),
+              _ptrs(w_hh)), (_ptrs(b_hh), _ptrs(hid), hid.stride(1), hid.stride(2), G, B, T, D, S, hidden, _stream()))
     return hid
 
 
 DECODER_X3 = os.environ.get("MRN_DECODER_X3", "1") == "1"     # attention decoder: the three recurrent products as split-fp16 x3
 
 
+def _attn_tile_lds(D, T, x3, extra=0):
+    """LDS bytes of an attention decoder launch with D context columns in the tile and T frames: attn_tile_lds of csrc/attn_decode.hip,
+    restated for callers and tests (x3 None: the DECODER_X3 default; extra: the launching kernel's own arrays)"""
+    x3 = DECODER_X3 if x3 is None else x3
+    return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + extra
+
+
 def attn_decoder_whole_context(D, T, x3=None):
     """does the decoder forward hold a 16-sample tile's whole [16, D] context in LDS (its single-launch form) for T frames, or does it
-    take the chunked WIDE form -- the rule of csrc/rnn.hip attn_launch (attn_tile_lds), restated for callers and tests: 4 * (2 * 16 * 260 + 16 * (D + 4)
-    + 16 * T + 256) bytes (+ 1024 in the x3 form) within 160 KiB.  DERNet's D = 256 * G fits up to G = 7 at every supported width
-    (T <= 129), as at T = 65."""
-    x3 = DECODER_X3 if x3 is None else x3
-    return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) <= 160 * 1024
+    take the chunked WIDE form -- the rule of csrc/attn_decode.hip attn_launch: 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) bytes
+    (+ 1024 in the x3 form) within 160 KiB.  DERNet's D = 256 * G fits up to G = 7 at every supported width (T <= 129), as at T = 65."""
+    return _attn_tile_lds(D, T, x3) <= 160 * 1024
 
 
 GREEDY_LDS_EXTRA = 4 * (16 + 2 * 16 * 16)      # attn_greedy_kernel: 16 tokens + 16 x 16 (value, index) argmax pairs
 
 
 def attn_greedy_whole_context(D, T, x3=None):
-    """attn_decoder_whole_context for the greedy decoder (csrc/rnn.hip greedy_launch): the same tile plus GREEDY_LDS_EXTRA bytes within
-    160 KiB.  At DERNet's widths (D = 256 * G) the crossing is where the teacher-forced decoder's is, between G = 7 and G = 8 for every
-    T <= 129; in between the extra 2112 bytes can tip a tile over (D = 1856 at T = 129 in the x3 form)."""
-    x3 = DECODER_X3 if x3 is None else x3
-    return 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + GREEDY_LDS_EXTRA <= 160 * 1024
+    """attn_decoder_whole_context for the greedy decoder (csrc/attn_decode.hip greedy_launch): the same tile plus GREEDY_LDS_EXTRA bytes
+    within 160 KiB.  At DERNet's widths (D = 256 * G) the crossing is where the teacher-forced decoder's is, between G = 7 and G = 8 for
+    every T <= 129; in between the extra 2112 bytes can tip a tile over (D = 1856 at T = 129 in the x3 form)."""
+    return _attn_tile_lds(D, T, x3, GREEDY_LDS_EXTRA) <= 160 * 1024
 
 
 def greedy_decode_mode():
@@ -1472,13 +1474,17 @@ def attn_greedy_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh
     tokens = torch.empty(B, S, device=Hb.device, dtype=torch.int64) if want_tokens else None
     if w_inv is not None:
         assert w_inv.numel() == 4 and w_inv.is_contiguous()
-        call("mrn_attn_greedy_decode_x3", _p(Hb), _p(Hproj), _p(etab), _p(start), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh),
-             _p(w_inv), _p(b_hh), _p(w_gen), _p(b_gen), C, _p(out), out.stride(0), out.stride(1), _p(tokens), B, T, D, S, hidden, _stream())
     else:
         _chk(w_h2h, w_ih, w_hh, w_gen)
-        call("mrn_attn_greedy_decode_f32", _p(Hb), _p(Hproj), _p(etab), _p(start), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh),
-             _p(b_hh), _p(w_gen), _p(b_gen), C, _p(out), out.stride(0), out.stride(1), _p(tokens), B, T, D, S, hidden, _stream())
+    _x3_call("attn_greedy_decode", False, w_inv,
+             (_p(Hb), _p(Hproj), _p(etab), _p(start), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh)),
+             (_p(b_hh), _p(w_gen), _p(b_gen), C, _p(out), out.stride(0), out.stride(1), _p(tokens), B, T, D, S, hidden, _stream()))
     return (out, tokens) if want_tokens else out
+
+
+def _decode_operands(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh):
+    """the leading arguments of the grouped greedy / beam / lexicon entry points, up to where the x3 forms take w_inv"""
+    return (_ptrs(Hb), _ptrs(Hproj), _ptrs(etab), _p(start), _ptrs(w_h2h), _ptrs(b_h2h), _ptrs(w_score), _ptrs(w_ih), _ptrs(w_hh))
 
 
 def attn_greedy_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, out,
@@ -1496,20 +1502,11 @@ def attn_greedy_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_
         assert etab[g].shape == (classes[g], 4 * hidden) and etab[g].is_contiguous() and w_gen[g].is_contiguous()
         assert w_gen[g].shape[0] == (classes[g] + 15) // 16 and b_gen[g].is_contiguous()
     tokens = torch.empty(G, B, S, device=Hb.device, dtype=torch.int64) if want_tokens else None
-
-    def arr(ts):
-        return _ptr_array([t.data_ptr() for t in ts])
     ncls = (ctypes.c_int * G)(*classes)
     sb, ss = (ctypes.c_int64 * G)(*[o.stride(0) for o in out]), (ctypes.c_int64 * G)(*[o.stride(1) for o in out])
-    tok = arr(tokens) if want_tokens else None
-    if w_inv is not None:
-        call("mrn_attn_greedy_decode_x3_grouped", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
-             arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(w_gen), arr(b_gen), ncls, arr(out), sb, ss, tok,
-             G, B, T, D, S, hidden, _stream())
-    else:
-        call("mrn_attn_greedy_decode_grouped_f32", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
-             arr(w_ih), arr(w_hh), arr(b_hh), arr(w_gen), arr(b_gen), ncls, arr(out), sb, ss, tok,
-             G, B, T, D, S, hidden, _stream())
+    _x3_call("attn_greedy_decode", True, w_inv, _decode_operands(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh),
+             (_ptrs(b_hh), _ptrs(w_gen), _ptrs(b_gen), ncls, _ptrs(out), sb, ss, _ptrs(tokens) if want_tokens else None,
+              G, B, T, D, S, hidden, _stream()))
     return (out, tokens) if want_tokens else out
 
 
@@ -1517,13 +1514,12 @@ ATTN_BEAM_LDS_EXTRA = 4 * (8 * 16 + 3 * 16 * 16)      # attn_beam_kernel: eight 
 
 
 def attn_beam_whole_context(D, T, W, x3=None):
-    """does the fused beam decoder (csrc/rnn.hip beam_launch / beam_grouped) take D context columns, T frames and beam width W: the
+    """does the fused beam decoder (csrc/attn_decode.hip beam_launch / beam_grouped) take D context columns, T frames and beam width W: the
     whole-context tile of attn_greedy_whole_context with ATTN_BEAM_LDS_EXTRA bytes in place of the arg-max pairs within 160 KiB (the 16
     rows are 16 // W samples x W entries, so the tile does not grow with W), 1 <= W <= 16, D a multiple of 16 (32 in the x3 form).  There
     is no chunked form: what does not fit is decoded stepwise (Attention.beam_search)"""
     x3 = DECODER_X3 if x3 is None else x3
-    lds = 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + ATTN_BEAM_LDS_EXTRA
-    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and lds <= 160 * 1024
+    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and _attn_tile_lds(D, T, x3, ATTN_BEAM_LDS_EXTRA) <= 160 * 1024
 
 
 def attn_beam_mode():
@@ -1567,30 +1563,18 @@ def _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh
     tiles = -(-B // (16 // W)) if 1 <= W <= 16 else 0
     per = tiles * 16 * ((max(classes) + 15) // 16 * 16 + 3 * Sd)
     scratch = torch.empty(G, max(per, 1), device=dev, dtype=torch.float32)
-
-    def arr(ts):
-        return _ptr_array([t.data_ptr() for t in ts])
-    outs = (arr(scratch), per, arr(tokens), arr(length), arr(score), arr(logp), arr(path), arr(prob))
-    ncls = (ctypes.c_int * G)(*classes)
+    outs = (tokens, length, score, logp, path, prob)
+    lex, word = (), ()
     if trie is not None:
         if not isinstance(trie, TrieHandle) or trie.child_off.device != dev:
             raise ValueError("attn_lexicon_decode needs the handle of upload_trie on the device of the features")
-        word = torch.empty(G, B, Wd, device=dev, dtype=torch.int32)
         lex = (_p(trie.child_off), _p(trie.child_tok), _p(trie.child_node), _p(trie.word_of), trie.nodes, trie.depth)
-        operands = (arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score), arr(w_ih), arr(w_hh))
-        tail = (arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *lex, *outs, arr(word), G, B, T, D, S, hidden, _stream())
-        if w_inv is not None:
-            call("mrn_attn_lexicon_decode_x3_grouped", *operands, arr(w_inv), *tail)
-        else:
-            call("mrn_attn_lexicon_decode_grouped_f32", *operands, *tail)
-        return tokens, length, score, logp, path, prob, word
-    if w_inv is not None:
-        call("mrn_attn_beam_decode_x3_grouped", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
-             arr(w_ih), arr(w_hh), arr(w_inv), arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *outs, G, B, T, D, S, hidden, _stream())
-    else:
-        call("mrn_attn_beam_decode_grouped_f32", arr(Hb), arr(Hproj), arr(etab), _p(start), arr(w_h2h), arr(b_h2h), arr(w_score),
-             arr(w_ih), arr(w_hh), arr(b_hh), arr(w_gen), arr(b_gen), ncls, int(eos), W, *outs, G, B, T, D, S, hidden, _stream())
-    return tokens, length, score, logp, path, prob
+        word = (torch.empty(G, B, Wd, device=dev, dtype=torch.int32),)
+    _x3_call("attn_beam_decode" if trie is None else "attn_lexicon_decode", True, w_inv,
+             _decode_operands(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh),
+             (_ptrs(b_hh), _ptrs(w_gen), _ptrs(b_gen), (ctypes.c_int * G)(*classes), int(eos), W, *lex, _ptrs(scratch), per,
+              *map(_ptrs, outs + word), G, B, T, D, S, hidden, _stream()))
+    return outs + word
 
 
 def attn_beam_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv=None):
@@ -1605,12 +1589,11 @@ ATTN_LEXICON_LDS_EXTRA = ATTN_BEAM_LDS_EXTRA + 4 * (2 * 16 + 16 * 16)      # att
 
 
 def attn_lexicon_whole_context(D, T, W, x3=None):
-    """attn_beam_whole_context for the lexicon-constrained launch (csrc/rnn.hip beam_launch / beam_grouped with a trie): the same sum
+    """attn_beam_whole_context for the lexicon-constrained launch (csrc/attn_decode.hip beam_launch / beam_grouped with a trie): the same sum
     with ATTN_LEXICON_LDS_EXTRA, 1152 bytes more.  There is no chunked form either: what does not fit is decoded stepwise
     (Attention.lexicon_search)"""
     x3 = DECODER_X3 if x3 is None else x3
-    lds = 4 * (2 * 16 * 260 + 16 * (D + 4) + 16 * T + 256) + (1024 if x3 else 0) + ATTN_LEXICON_LDS_EXTRA
-    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and lds <= 160 * 1024
+    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and _attn_tile_lds(D, T, x3, ATTN_LEXICON_LDS_EXTRA) <= 160 * 1024
 
 
 class TrieHandle:
@@ -1704,15 +1687,19 @@ def attn_decoder(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, hidd
         hid = torch.empty(B, S, hidden, device=Hb.device, dtype=torch.float32)
     alpha = torch.empty(B, S, T, device=Hb.device, dtype=torch.float32) if want_alpha else None
     assert eproj.stride(2) == 1 and hid.stride(2) == 1 and w_ih.is_contiguous() and w_hh.is_contiguous()
-    if w_inv is not None:          # x3 form (pack_decoder_x3)
-        call("mrn_attn_decoder_fwd_x3", _p(Hb), _p(Hproj), _p(eproj), eproj.stride(0), eproj.stride(1), _p(w_h2h),
-             _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh), _p(w_inv), _p(b_hh), _p(hid), hid.stride(0), hid.stride(1),
-             _p(h_state), _p(c_state), _p(alpha), None, None, None, None, B, T, D, S, hidden, _stream())
-        return (hid, alpha) if want_alpha else hid
-    call("mrn_attn_decoder_fwd_f32", _p(Hb), _p(Hproj), _p(eproj), eproj.stride(0), eproj.stride(1), _p(w_h2h),
-         _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh), _p(b_hh), _p(hid), hid.stride(0), hid.stride(1),
-         _p(h_state), _p(c_state), _p(alpha), None, None, None, None, B, T, D, S, hidden, _stream())
+    _attn_decoder_fwd(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, hidden, hid, h_state, c_state,
+                      (alpha, None, None, None, None), w_inv)
     return (hid, alpha) if want_alpha else hid
+
+
+def _attn_decoder_fwd(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, hidden, hid, h_state, c_state, saves, w_inv):
+    """the single-expert teacher-forced launch of attn_decoder and attn_decoder_train; saves: (alpha, gates, cseq, ctx, hp), each or None;
+    w_inv: the x3 form (pack_decoder_x3)"""
+    B, T, D = Hb.shape
+    _x3_call("attn_decoder_fwd", False, w_inv,
+             (_p(Hb), _p(Hproj), _p(eproj), eproj.stride(0), eproj.stride(1), _p(w_h2h), _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh)),
+             (_p(b_hh), _p(hid), hid.stride(0), hid.stride(1), _p(h_state), _p(c_state), *map(_p, saves), B, T, D, eproj.shape[1], hidden,
+              _stream()))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -2539,15 +2526,9 @@ def attn_decoder_train(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh
     cseq = torch.empty(B, S, hidden, device=dev, dtype=torch.float32)
     ctx = torch.empty(B, S, D, device=dev, dtype=torch.float32)
     hp = torch.empty(B, S, hidden, device=dev, dtype=torch.float32)
-    if w_inv is not None:
-        call("mrn_attn_decoder_fwd_x3", _p(Hb), _p(Hproj), _p(eproj), eproj.stride(0), eproj.stride(1), _p(w_h2h),
-             _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh), _p(w_inv), _p(b_hh), _p(hid), hid.stride(0), hid.stride(1), None, None,
-             _p(alpha), _p(gates), _p(cseq), _p(ctx), _p(hp), B, T, D, S, hidden, _stream())
-        return hid, (alpha, gates, cseq, ctx, hp)
-    call("mrn_attn_decoder_fwd_f32", _p(Hb), _p(Hproj), _p(eproj), eproj.stride(0), eproj.stride(1), _p(w_h2h),
-         _p(b_h2h), _p(w_score), _p(w_ih), _p(w_hh), _p(b_hh), _p(hid), hid.stride(0), hid.stride(1), None, None,
-         _p(alpha), _p(gates), _p(cseq), _p(ctx), _p(hp), B, T, D, S, hidden, _stream())
-    return hid, (alpha, gates, cseq, ctx, hp)
+    saves = (alpha, gates, cseq, ctx, hp)
+    _attn_decoder_fwd(Hb, Hproj, eproj, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, hidden, hid, None, None, saves, w_inv)
+    return hid, saves
 
 
 def attn_decoder_bwd(Hb, Hproj, saves, dhid, w_score, w_h2hT, w_ih_ctxT, w_hhT, hidden, w_inv=None):

@@ -1,4 +1,4 @@
-"""Outputs of the attention head's three decoder kernels (csrc/rnn.hip attn_decoder_kernel, attn_greedy_kernel, attn_beam_kernel) on
+"""Outputs of the attention head's three decoder kernels (csrc/attn_decode.hip attn_decoder_kernel, attn_greedy_kernel, attn_beam_kernel) on
 the smallest shapes that reach every branch of the step they share, for tests/test_decode_attn_step_gpu.py, which demands them back bit for bit.
 
     python tests/golden/make_golden_attn_step.py

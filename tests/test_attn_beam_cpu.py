@@ -200,10 +200,10 @@ def test_entry_points_are_declared_bound_exported_and_cited():
 
 
 def test_rule_matches_the_launch_helper():
-    """ops.attn_beam_whole_context restates the beam launch's LDS sum in csrc/rnn.hip (the tile of attn_tile_lds, the three decoder
+    """ops.attn_beam_whole_context restates the beam launch's LDS sum in csrc/attn_decode.hip (the tile of attn_tile_lds, the three decoder
     kernels' one definition, at dc = D plus BEAM_LDS_EXTRA) and the limits beam_grouped checks before any launch"""
     from mrn_amd import ops
-    src = open(os.path.join(ROOT, "mrn_amd", "csrc", "rnn.hip")).read()
+    src = open(os.path.join(ROOT, "mrn_amd", "csrc", "attn_decode.hip")).read()
     flat = re.sub(r"\s+", " ", src[src.index("static size_t attn_tile_lds("):src.index("static dim3 attn_grid(")])
     assert "(bool x3, int dc, int T, size_t extra)" in flat
     assert "sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra" in flat

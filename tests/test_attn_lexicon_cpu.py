@@ -347,10 +347,10 @@ def test_entry_points_are_declared_bound_exported_and_cited():
 
 
 def test_rule_matches_the_launch_helper():
-    """ops.attn_lexicon_whole_context restates the lexicon launch's LDS sum in csrc/rnn.hip (the beam's plus LEX_LDS_MORE), and the two
+    """ops.attn_lexicon_whole_context restates the lexicon launch's LDS sum in csrc/attn_decode.hip (the beam's plus LEX_LDS_MORE), and the two
     kernels share one body"""
     from mrn_amd import ops
-    src = open(os.path.join(ROOT, "mrn_amd", "csrc", "rnn.hip")).read()
+    src = open(os.path.join(ROOT, "mrn_amd", "csrc", "attn_decode.hip")).read()
     consts = dict(re.findall(r"(?m)^constexpr int (\w+) = ([^;]+);", src))
     assert re.sub(r"\s+", " ", consts["LEX_LDS_MORE"]).strip() == "4 * (2 * BT + BT * BT)"
     assert ops.ATTN_LEXICON_LDS_EXTRA == ops.ATTN_BEAM_LDS_EXTRA + 4 * (2 * 16 + 16 * 16) == 3584 + 1152

@@ -1,4 +1,4 @@
-"""Beam-search decoding on the attention head in one launch (mrn_attn_beam_decode_*, csrc/rnn.hip attn_beam_kernel) against the float64
+"""Beam-search decoding on the attention head in one launch (mrn_attn_beam_decode_*, csrc/attn_decode.hip attn_beam_kernel) against the float64
 reference mrn_amd/modules/decoding.py::attn_beam_host.
 
 Bands: logits are held to 1e-4 of the oracle, a chosen token's log-probability (logit - lse) therefore to 2e-4 and a score of n tokens

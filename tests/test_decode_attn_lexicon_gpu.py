@@ -1,4 +1,4 @@
-"""Lexicon-constrained beam search on the attention head in one launch (mrn_attn_lexicon_decode_*, csrc/rnn.hip attn_lexicon_kernel)
+"""Lexicon-constrained beam search on the attention head in one launch (mrn_attn_lexicon_decode_*, csrc/attn_decode.hip attn_lexicon_kernel)
 against the float64 reference mrn_amd/modules/decoding.py::attn_lexicon_host.
 
 Bands and the notion of a decisive sample are those of tests/test_decode_attn_beam_gpu.py: a chosen token's log-probability is held to

@@ -1,4 +1,4 @@
-"""The attention head's three decoder kernels (csrc/rnn.hip attn_decoder_kernel, attn_greedy_kernel, attn_beam_kernel) share one step;
+"""The attention head's three decoder kernels (csrc/attn_decode.hip attn_decoder_kernel, attn_greedy_kernel, attn_beam_kernel) share one step;
 tests/golden/attn_step.npz holds their outputs from before they did (tests/golden/make_golden_attn_step.py states the cases), and every
 stored array must come back bit for bit: torch.equal, no tolerance.  A difference means a regrouped expression or a moved contraction.
 

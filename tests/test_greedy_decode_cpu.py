@@ -15,7 +15,8 @@ GREEDY = ("mrn_attn_greedy_decode_f32", "mrn_attn_greedy_decode_x3", "mrn_attn_g
 
 
 def _source():
-    return open(os.path.join(ROOT, "mrn_amd", "csrc", "rnn.hip")).read()
+    """the decoders' translation unit: the shared header, then csrc/attn_decode.hip"""
+    return "".join(open(os.path.join(ROOT, "mrn_amd", "csrc", f)).read() for f in ("recurrent.hpp", "attn_decode.hip"))
 
 
 def test_whole_context_rule_over_widths_and_task_counts():
@@ -39,7 +40,7 @@ def test_whole_context_rule_over_widths_and_task_counts():
 
 
 def test_rule_matches_the_launch_helper():
-    """the terms of greedy_launch's budget in csrc/rnn.hip (the tile of attn_tile_lds, the three decoder kernels' one definition, plus
+    """the terms of greedy_launch's budget in csrc/attn_decode.hip (the tile of attn_tile_lds, the three decoder kernels' one definition, plus
     GREEDY_LDS_EXTRA) are the ones ops.attn_greedy_whole_context restates"""
     src = _source()
     tile = re.sub(r"\s+", " ", src[src.index("static size_t attn_tile_lds("):src.index("static dim3 attn_grid(")])

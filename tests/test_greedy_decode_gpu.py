@@ -1,4 +1,4 @@
-"""Greedy decoding on the attention head in one launch (mrn_attn_greedy_decode*, csrc/rnn.hip attn_greedy_kernel) against the CPU oracle's
+"""Greedy decoding on the attention head in one launch (mrn_attn_greedy_decode*, csrc/attn_decode.hip attn_greedy_kernel) against the CPU oracle's
 step loop (reference modules/prediction.py:70-86), and the fused launch against itself across its forms.
 
 Greedy feedback turns a flipped near-tie into a different sequence, so every oracle comparison first asserts that the ORACLE's smallest

@@ -489,3 +489,17 @@ def test_reduced_mode_winograd_eligibility():
     finally:
         ops.X3_PRODUCTS, ops.WINO_DENSE = saved
 
+
+
+def test_recurrent_helpers_are_defined_once():
+    """the MFMA wrapper and the fast tanh that the recurrent forward and backward units must agree on are each defined exactly once in
+    csrc/, in recurrent.hpp, which those units include"""
+    import re
+    csrc = os.path.join(ROOT, "mrn_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".cpp", ".h")))
+    for helper, ret in (("mfma4", "f32x4"), ("fast_tanh", "float")):
+        defs = [f for f in files for _ in re.finditer(r"\b%s\s+%s\(" % (ret, helper), open(os.path.join(csrc, f)).read())]
+        assert defs == ["recurrent.hpp"], (helper, defs)
+    for unit in ("lstm.hip", "attn_decode.hip", "attn_bwd.hip", "backward.hip"):
+        assert '#include "recurrent.hpp"' in open(os.path.join(csrc, unit)).read(), unit
+    assert not os.path.exists(os.path.join(csrc, "rnn.hip"))

@@ -566,7 +566,7 @@ def test_lstm_recurrence_on_f16_mfma(ops):
 
 def test_lstm_x3_batch_beyond_the_32bit_row_offsets(ops):
     """the x3 layer kernel addresses its rows with 32-bit byte offsets into [B][T][ndir][4H]; the launcher cuts a batch whose array is
-    beyond 4 GiB into chunks of whole tiles (rnn.hip: lstm_x3_launch).  T = 2048: 224 samples fit, B = 256 goes as 224 + 32 -- the same
+    beyond 4 GiB into chunks of whole tiles (lstm.hip: lstm_x3_launch).  T = 2048: 224 samples fit, B = 256 goes as 224 + 32 -- the same
     bits as the two parts launched separately"""
     G, B, T, Hd = 1, 256, 2048, 256
     gen = torch.Generator(device="cuda").manual_seed(77)
@@ -1736,7 +1736,7 @@ def test_transposed_split_with_column_sums(ops, rows, padded, C, S, mag):
 
 
 def test_lstm_grouped_tail_sets_spread_over_all_xcds(ops):
-    """the (expert, direction, tile) workgroups of a grouped layer are dealt to the eight XCDs in equal set-major runs (rnn.hip: pinned == 2;
+    """the (expert, direction, tile) workgroups of a grouped layer are dealt to the eight XCDs in equal set-major runs (lstm.hip: pinned == 2;
     twelve sets of 16 tiles = 24 per XCD) -- every (set, tile) is computed exactly once: the grouped launch equals the per-expert launches
     bit for bit, also with a ragged last tile (B = 250), ten sets, and eighteen sets of four tiles"""
     Hd, T = 256, 7

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a what-if variant of libmrn_hip.so: one source (default conv_x3.hip) recompiled with -D<flag>, every other object reused.
-# usage: bash tools/build_probe.sh MRN_PROBE_NO_MFMA [rnn.hip]  ->  tools/probe/libmrn_MRN_PROBE_NO_MFMA.so  (select it with MRN_LIB_PATH)
+# usage: bash tools/build_probe.sh MRN_PROBE_NO_MFMA [lstm.hip]  ->  tools/probe/libmrn_MRN_PROBE_NO_MFMA.so  (select it with MRN_LIB_PATH)
 set -e
 flag=$1
 src=${2:-conv_x3.hip}
