@@ -63,7 +63,8 @@ int mrn_pow2_finalize_f32(float target, float* scale, void* workspace, void* str
 
 /* Grouped split-fp16 x3 convolution on 256-wide tiles (the router phase runs the G frozen experts' backbones in
  * lock-step: il_modules/mrn.py:323-337 calls every expert on the same batch; modules/model.py:399-401).
- * Operands are in the "HL32" layout: one 128-byte line [hi fp16 x 32 | lo fp16 x 32] per (pixel, 32-channel block) for
+ * Operands are in the "HL32" layout (csrc/hl32.hpp; producers in csrc/hl32_pack.hip, the weight gradients' transposed operand passes in
+ * csrc/wgrad_operands.hip): one 128-byte line [hi fp16 x 32 | lo fp16 x 32] per (pixel, 32-channel block) for
  * the activation (mrn_split_hl32_f32, or the fused BatchNorm-apply pass mrn_bn_apply_hl32_f32) and per
  * (Cout row, 32-channel block, tap) for the weight (mrn_pack_weight_hl32; reduction order = channel block outer, tap
  * inner).  x_hl: [G][B][H][W][Cin/32][128 B] with group stride x_group_stride_bytes (0 = all groups read the same

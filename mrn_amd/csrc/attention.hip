@@ -13,7 +13,7 @@
 // The contraction over d is order-free, so MFMA step t of the first product takes d = 16*(lane>>5) + t: every lane reads
 // 16 contiguous floats of its K (and Q) row.  Softmax runs in base 2 (log2 e folded into the q scale and the mask).
 // The additive mask must be symmetric (SVTR's local window mask is): mask[key][query] is read row-wise.
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {
 
@@ -22,7 +22,6 @@ constexpr int AW = 4;           // waves per workgroup: 128 query tokens
 constexpr int KS = 36;          // LDS row stride of the K tile in floats (16-byte aligned rows, conflict-free b128 reads)
 constexpr int VS = 40;          // LDS row stride of the V tile: rows key and key + 4 land on disjoint bank halves
 constexpr float LOG2E = 1.4426950408889634f;
-typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
 
 struct AttnParams {
   const float* qkv;    // [B][N][3*C]: q | k | v, each (head, d) innermost
@@ -182,19 +181,7 @@ __global__ __launch_bounds__(AW * 64) void svtr_attention_kernel(const AttnParam
       const f32x4 v = {o[e] * inv, o[e + 1] * inv, o[e + 2] * inv, o[e + 3] * inv};
       const int d0 = 8 * (e >> 2) + 4 * half;
       if (p.out) *reinterpret_cast<f32x4*>(p.out + row * p.C + h * HD + d0) = v;
-      if (p.out_hl) {
-        f16v4 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          _Float16 hh, ll;
-          split_f16_sat(v[j] * hs, hh, ll);
-          hi[j] = hh;
-          lo[j] = ll;
-        }
-        unsigned char* line = p.out_hl + (row * p.heads + h) * 128 + d0 * 2;
-        *reinterpret_cast<f16v4*>(line) = hi;
-        *reinterpret_cast<f16v4*>(line + 64) = lo;
-      }
+      if (p.out_hl) split_hl4<true>([&](int j) { return v[j] * hs; }).store(p.out_hl + (row * p.heads + h) * 128 + d0 * 2);
     }
   }
 }
@@ -207,7 +194,6 @@ __global__ __launch_bounds__(AW * 64) void svtr_attention_kernel(const AttnParam
 // e -> slot 16h + e), so P^T goes from the first product's accumulator into the second product's B operand by a register
 // pack.  The probabilities carry a 2^12 bias (exp2(s - m + 12), cancelled by the final 1 / l) to keep small ones out of
 // fp16's subnormal range.
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
 constexpr int XS = 144;         // LDS line stride in bytes (128-byte line + 16: conflict-free 16-byte fragment reads)
 constexpr float PBIAS = 12.f;
 constexpr float OPSCALE = 64.f;  // q, k, v are split as 64 * x: the lo halves of O(1) operands stay out of fp16's subnormal range
@@ -396,19 +382,7 @@ __global__ __launch_bounds__(AW * 64) void svtr_attention_x3_kernel(const AttnPa
       const f32x4 v = {o[e] * inv, o[e + 1] * inv, o[e + 2] * inv, o[e + 3] * inv};
       const int d0 = 8 * (e >> 2) + 4 * half;
       if (p.out) *reinterpret_cast<f32x4*>(p.out + row * p.C + h * HD + d0) = v;
-      if (p.out_hl) {
-        f16v4 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          _Float16 hh, ll;
-          split_f16(v[j], hh, ll);
-          hi[j] = hh;
-          lo[j] = ll;
-        }
-        unsigned char* line = p.out_hl + (row * p.heads + h) * 128 + d0 * 2;
-        *reinterpret_cast<f16v4*>(line) = hi;
-        *reinterpret_cast<f16v4*>(line + 64) = lo;
-      }
+      if (p.out_hl) split_hl4(v).store(p.out_hl + (row * p.heads + h) * 128 + d0 * 2);
     }
   }
 }

@@ -5,6 +5,7 @@
 // forward (attn_decode.hip): 16 samples per workgroup, 16 waves, wave w owns hidden units [16w, 16w+16); the transposed
 // recurrent weights stream fragment-major from L2.  The tile constants HID, BT, NW, NTH, HLD, mfma4 and fast_tanh are the forward's
 // (recurrent.hpp).
+#include "hl32.hpp"
 #include "recurrent.hpp"
 #include <stdlib.h>
 

@@ -3,6 +3,7 @@
 //
 // Reference: modules/prediction.py:38-118 (Attention / AttentionCell, 26 decode steps).  The workgroup geometry and the MFMA
 // helpers are recurrent.hpp's, shared with the BiLSTM layer (lstm.hip) and the backward (attn_bwd.hip).
+#include "hl32.hpp"
 #include "recurrent.hpp"
 #include <stdlib.h>
 
@@ -96,9 +97,9 @@ __device__ __forceinline__ AttnTile<X3> attn_tile(float* lds, const AttnDecParam
   v.c_hi = reinterpret_cast<_Float16*>(v.ctx_lds);
   v.c_lo = v.c_hi + BT * v.CLDH;
   v.inv_h2h = X3 ? p.w_inv[0] : 1.f, v.inv_ih = X3 ? p.w_inv[1] : 1.f, v.inv_hh = X3 ? p.w_inv[2] : 1.f;
-  v.r_h2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_h2h, 0, X3 ? HID * HID * 4 : 0, 0x00020000);
-  v.r_ih = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_ih, 0, X3 ? 4 * HID * p.D * 4 : 0, 0x00020000);
-  v.r_hh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hh, 0, X3 ? 4 * HID * HID * 4 : 0, 0x00020000);
+  v.r_h2h = make_rsrc(p.w_h2h, X3 ? HID * HID * 4 : 0);
+  v.r_ih = make_rsrc(p.w_ih, X3 ? 4 * HID * p.D * 4 : 0);
+  v.r_hh = make_rsrc(p.w_hh, X3 ? 4 * HID * HID * 4 : 0);
   v.b0 = tile * ns;
   v.Bend = min(p.B, v.b0 + ns);
   v.nrows = ns * per;
@@ -427,7 +428,7 @@ __global__ __launch_bounds__(NTH) void attn_greedy_kernel(const GreedyGroup grp)
   const AttnDecParams& p = gp.a;
   const int C = gp.num_class;
   const float inv_gen = X3 ? p.w_inv[3] : 1.f;     // the generator stream (x3: fp16 hi / lo behind a buffer resource) and its inverse prescale
-  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_gen = make_rsrc(gp.w_gen, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0);
   const AttnTile<X3> v = attn_tile<X3>(lds, p, WIDE ? CTX_CHUNK : p.D, tile_, grp.vb, 1);
   int* tok_lds = reinterpret_cast<int*>(v.sw_lds + HID);     // behind the shared map: [BT] tokens, [NW][BT] best values, [NW][BT] best indices
   float* red_v = reinterpret_cast<float*>(tok_lds + BT);
@@ -588,7 +589,7 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
   const int W = grp.W, eos = grp.eos;
   const int CP = (C + 15) / 16 * 16;         // scratch row stride
   const float inv_gen = X3 ? p.w_inv[3] : 1.f;     // the generator stream (x3: fp16 hi / lo behind a buffer resource) and its inverse prescale
-  const __amdgpu_buffer_rsrc_t r_gen = __builtin_amdgcn_make_buffer_rsrc((void*)gp.w_gen, 0, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_gen = make_rsrc(gp.w_gen, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0);
   const AttnTile<X3> v = attn_tile<X3>(lds, p, p.D, tile_, BT / W, W);       // 16 / W samples x W entries
   int* tok_lds = reinterpret_cast<int*>(v.sw_lds + HID);     // behind the shared map: the beam state of BEAM_LDS_EXTRA
   float* score_lds = reinterpret_cast<float*>(tok_lds + BT);

@@ -3,6 +3,7 @@
 // backward fused with the ReLU mask, max-pool backward, LSTM backward-through-time.
 // Convolution data / weight gradients themselves are implicit GEMMs on the forward kernels (gemm.hip):
 //   dgrad = conv(dy, flipped-transposed weight), wgrad = mrn_conv2d_wgrad_f32.
+#include "hl32.hpp"
 #include "recurrent.hpp"
 
 namespace {

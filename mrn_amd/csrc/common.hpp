@@ -52,24 +52,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
-// x = hi + lo as two fp16 (22 significand bits).  The operand is pinned in a register first: under -ffp-contract=fast the
-// compiler may otherwise fold the multiply / fma that PRODUCED x into the conversion (v_fma_mixlo_f16: one rounding from the
-// exact product) for one use of hi and convert the fp32-rounded value (two roundings) for another -- the two differ by one
-// fp16 ulp when the fp32 value sits on an fp16 tie, and the pair then misses x by 2^-11 (seen on 2 of 65536 elements).
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-  asm volatile("" : "+v"(x));
-  hi = (_Float16)x;
-  lo = (_Float16)(x - (float)hi);
-}
-
-// the same for range-scaled GRADIENT operands (BPTT gate gradients, scaled by a power of two from max|dout|): saturate at the
-// fp16 range instead of hi = inf, lo = -inf (NaN products) when back-propagation through time grows them past the headroom --
-// the exact-fp32 kernels give large finite gradients there, which the global-norm clip then handles
-__device__ __forceinline__ void split_f16_sat(float x, _Float16& hi, _Float16& lo) {
-  x = fminf(fmaxf(x, -65504.f), 65504.f);
-  split_f16(x, hi, lo);
-}
-
 // torch.relu / max_pool2d propagate NaN; v_max_f32 (fmaxf) returns the OTHER operand.  The pooled epilogues and the separate pooling
 // pass must agree on non-finite data too (a NaN in a frozen expert's raw convolution output must reach the features).
 __device__ __forceinline__ float relu_nan(float v, float floor_ = 0.f) { return v != v ? v : fmaxf(v, floor_); }

@@ -20,14 +20,10 @@
 //     then runs on the pooled map and produces bit for bit what apply -> ReLU -> max-pool produced.
 // One wave per SIMD (4 waves, up to 512 registers); LDS: 2 x 43 KiB (Cin 32, 8-row tiles) or 2 x 51 KiB (Cin 64, 4-row tiles) + 32 KiB
 // of per-lane statistics accumulators (one deterministic row of partial sums per workgroup for the whole launch).
-#include "common.hpp"
+#include "hl32.hpp"
 #include <stdlib.h>
 
 namespace {
-
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct ConvPatchParams {
   const unsigned char* x;      // HL32 [Gx][B][H][W][Cin/32][128 B]
@@ -58,15 +54,6 @@ struct Cfg {
   static constexpr int LDS = NST * STAGE + STATS;
   static constexpr int NS = CB * 9 * 2;          // (channel block, tap, 16-channel half) steps of a tile
 };
-
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-#ifdef MRN_PPROBE_NO_MFMA
-  f32x16 r = c;                 // (what-if probes MRN_PPROBE_*: never in the product build; tools/build_probe.sh)
-  r[0] += __builtin_bit_cast(float, a[0] ^ b[0]);
-  return r;
-#endif
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16v8*>(&a), *reinterpret_cast<const f16v8*>(&b), c, 0, 0, 0);
-}
 
 #ifdef MRN_PPROBE_TIMING
 // timing probe (never in the product build): per-wave shader-clock totals of a tile's phases, summed over all waves
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(256) void conv_patch_x3_kernel(const ConvPatchParam
   // ---- DMA geometry: instruction j = wave + 4 i moves lines 8 j .. 8 j + 7; lane -> line L = 8 j + (lane >> 3), physical chunk
   // lane & 7 (LDS is written lane-linearly: the swizzle is applied to the SOURCE chunk).  Recomputed per piece (a dozen VALU
   // operations) rather than held in 2 x NJ registers next to the stationary weights.
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (long)g * p.x_gstride), 0, p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x + (long)g * p.x_gstride, p.x_bytes);
   const int tiles_img = p.tiles_x * p.tiles_y;
   struct TileAt { int b, y0, x0, base; };        // sample, top-left output pixel, byte offset of the patch's top-left pixel (y0 - 1, x0 - 1)
   auto locate = [&](int tile) {
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(256) void conv_patch_x3_kernel(const ConvPatchParam
     const int rel = ((prow * p.W + pcol) * CB + cb) * 128 + (((lane & 7) ^ ((pcol >> 1) & 7)) << 4);
     const int okm = -(int)ok;                                       // (mask arithmetic, not a select: the compiler turned the select into an exec-masked BLOCK)
     const int voff = ((a.base + rel) & okm) | ((int)0x80000000 & ~okm);      // beyond the descriptor: zeros
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr_t)(lds + stage * STAGE + (wave + 4 * i) * 1024), 16, voff, 0, 0, 0);
+    dma16(xr, lds + stage * STAGE + (wave + 4 * i) * 1024, voff, 0);
   };
 
   constexpr int RP = 2, NPASS = 4 / RP;          // a wave's four rows in passes of two: two accumulators (= one pooled row) per pass
@@ -213,7 +200,7 @@ __global__ __launch_bounds__(256) void conv_patch_x3_kernel(const ConvPatchParam
   auto sign_of = [&](int e) { return LEAN ? ((negmask >> e) & 1u ? -1.f : 1.f) : sgn[LEAN ? 0 : e]; };
   const int Ho = p.H >> 1, Wo = p.W >> 1;
   const long y_elems = (long)p.B * (POOL ? Ho * (long)Wo : p.H * (long)p.W) * Cout;      // one expert's output (< 2^30 elements: checked by the launcher)
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (long)g * y_elems), 0, (int)(y_elems * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + (long)g * y_elems, (int)(y_elems * 4));
   const float relu_floor = p.act == 1 ? 0.f : -INFINITY;
   auto store16 = [&](const f32x4 v, int elem_off, bool ok) {      // (a lane without an output stores beyond the descriptor: dropped, no branch)
     const int okm = -(int)ok;

@@ -22,38 +22,23 @@
 // The price is registers: 4 x 4 output accumulators + 4 component accumulators = 320 per lane, so a workgroup is four waves, ONE per SIMD
 // (the 512-register pattern), with the MFMA stream skewed across the step barrier (the last input row's products of step s issue after
 // the barrier, covering the DMA issue and the first fragment reads of step s + 1).  LDS: 2 stages x (6 x 64 + 3 x 64) lines = 144 KiB.
-#include "common.hpp"
+#include "hl32.hpp"
 #include "conv_wino.hpp"
 #include <stdlib.h>
 
 namespace {
 
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int NPOS = 64, NCH = 64;                       // positions / output channels per workgroup
 constexpr int LDS_BYTES = 144 * 1024;                   // activation ring + weight ring (sized per row-block class in wino_rows_tile)
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t r, unsigned char* l, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-#ifdef MRN_WPROBE_NO_MFMA
-  f32x16 r = c;                 // (what-if probes MRN_WPROBE_*: never in the product build)
-  r[0] += __builtin_bit_cast(float, a[0] ^ b[0]);
-  return r;
-#endif
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16v8*>(&a), *reinterpret_cast<const f16v8*>(&b), c, 0, 0, 0);
-}
 
 // DENSE = 2: the plain 16-bit operands are bfloat16 (the literal "bf16" of BASELINE config 2: a comparison instantiation of the reduced mode)
 __device__ __forceinline__ f32x16 mma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16v8*>(&a), *reinterpret_cast<const bf16v8*>(&b), c, 0, 0, 0);
 }
 
-// A^T of F(4,3) with the inverse row scales of the packed weight transform (conv_x3.hip: WinoAT<4>, pack_weight_wino_hl32_kernel)
+// A^T of F(4,3) with the inverse row scales of the packed weight transform (conv_x3.hip: WinoAT<4>; hl32_pack.hip: pack_weight_wino_hl32_kernel)
 __constant__ float kWinoAT[6][4] = {{0.25f, 0.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f, -0.5f},
                                     {0.5f, 1.f, 2.f, 4.f}, {0.5f, -1.f, 2.f, -4.f}, {0.f, 0.f, 0.f, 1.f}};
 
@@ -115,8 +100,8 @@ __device__ __forceinline__ void wino_rows_tile(const WinoRowsParams& p, unsigned
     const int n = min(n0 + r, p.N - 1);                             // channels beyond N re-read the last one (never stored)
     brow[jj] = n * w_pitch + coff;
   }
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.v + (long)g * p.v_gstride), 0, p.v_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.u + (long)g * p.u_gstride), 0, (int)p.u_gstride, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.v + (long)g * p.v_gstride, p.v_bytes);
+  const __amdgpu_buffer_rsrc_t wr = make_rsrc(p.u + (long)g * p.u_gstride, (int)p.u_gstride);
   const int row_bytes = p.Wq * a_pitch;                             // one image row of one sample
   // The DMAs of a step are a list of NDMA items -- the six weight pieces first, then two per input-row slot -- and every row-op of the
   // main loop issues DMA_PER_OP of them: all four waves issuing a step's pieces at once right after the barrier queue up in front of

@@ -3,7 +3,7 @@
 // Arithmetic: every fp32 operand is x = hi + lo (two fp16, 22 significand bits); product = lo*hi + hi*lo + hi*hi on
 // v_mfma_f32_32x32x16_f16 with fp32 accumulation (same numerics as conv_bf16_dma_kernel<3,true> in gemm_bf16.hip).
 //
-// Operand layout "HL32" (written by the producer pass, mrn_split_hl32_f32 / mrn_pack_weight_hl32):
+// Operand layout "HL32" (hl32.hpp; written by the producer passes of hl32_pack.hip, mrn_split_hl32_f32 / mrn_pack_weight_hl32):
 //   activation [pixel][Cin/32][ hi[32] | lo[32] ] fp16  -- one 128-byte line per (pixel, 32-channel block)
 //   weight     [Cout][Cin/32][tap][ hi[32] | lo[32] ] fp16
 // so that one K-step of the GEMM (32 channels of one tap) is exactly one 128-byte line per tile row for BOTH
@@ -24,16 +24,11 @@
 // Groups: G independent convolutions of identical geometry (the frozen experts of MRN's router phase run their
 // backbones in lock-step): weights / bias / scales / outputs / statistics are [G]-strided, the input is either
 // [G]-strided or shared (x_gstride = 0).  Tiles never straddle a group.
-#include "common.hpp"
+#include "hl32.hpp"
 #include "conv_wino.hpp"
 #include <stdlib.h>
 
 namespace {
-
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 // K-window of one group of a windowed GEMM (mrn_gemm_x3_windows_hl32): byte offsets of the window's first line inside the two
 // operand matrices and its length in K-steps (128-byte lines); rows are `a_pitch` / `w_pitch` lines apart
@@ -77,23 +72,6 @@ struct ConvX3Params {
   int w_bytes;                // ... bytes of the whole weight-side matrix (x_bytes = the activation-side one)
   int wino_W;                 // Winograd F(R,3) along W (WINO = R instantiations): real output width; GEMM rows are groups of R pixels
 };
-
-// 16 bytes per lane, global (buffer descriptor + per-lane byte offset + wave-uniform offset) -> LDS (wave-uniform base + 16*lane)
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t r, unsigned char* l, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const unsigned char* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-#ifdef MRN_PROBE_NO_MFMA
-  f32x16 r = c;                 // (what-if probe, never in the product build: the staging floor without matrix work)
-  r[0] += __builtin_bit_cast(float, a[0] ^ b[0]);
-  return r;
-#endif
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16v8*>(&a), *reinterpret_cast<const f16v8*>(&b), c, 0, 0, 0);
-}
 
 // n / d for 0 <= n < 2^31 with host-computed (magic, shift): q = umulhi(n, magic) >> shift
 __device__ __forceinline__ int fast_div(int n, unsigned magic, int shift) {
@@ -142,7 +120,7 @@ constexpr size_t x3_lds_bytes() {
 // NPROD: 3 = split-fp16 x3 (lo*hi + hi*lo + hi*hi, 22-bit products: the parity mode); 1 = hi*hi only (plain fp16 products with fp32
 // accumulation -- the reduced-precision mode of BASELINE configs 2 and 5; the lo halves of the staged lines are not read)
 // Winograd F(R,3) output transforms A^T [R][R+2] with the power-of-two row scales of the packed weight transform folded in
-// (pack_weight_wino_hl32_kernel multiplies row m of G by wino_gscale(R, m); column m here carries the inverse)
+// (the weight transform of hl32_pack.hip, wino_g, multiplies row m of G by that scale; column m here carries the inverse)
 template <int R> struct WinoAT;
 template <> struct WinoAT<2> {
   static constexpr float at[2][4] = {{1.f, 1.f, 1.f, 0.f}, {0.f, 1.f, -1.f, -1.f}};
@@ -644,445 +622,6 @@ template __global__ void conv_x3_kernel<4, 4, 2, 2, true, 1>(const ConvX3Params)
 template __global__ void conv_x3_kernel<2, 4, 2, 1, false, 3, 4>(const ConvX3Params);     // Winograd F(4,3): 128 groups x 128 channels
 template __global__ void conv_x3_kernel<2, 4, 2, 1, false, 3, 2>(const ConvX3Params);     // Winograd F(2,3)
 
-// ---- producers of the HL32 layout -------------------------------------------------------------------------------
-__device__ __forceinline__ void split_h(float v, _Float16& h, _Float16& l) {
-  split_f16(v, h, l);
-}
-
-// fp32 [rows][C] -> HL32 [rows][C/32][hi 32 | lo 32]; one thread = 8 channels (32 B in, 2 x 16 B out)
-__global__ __launch_bounds__(256) void split_hl32_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long n8,
-                                                         const float* __restrict__ scale) {
-  const float sc = scale ? scale[0] : 1.f;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(x + i * 8) * sc, b = *reinterpret_cast<const f32x4*>(x + i * 8 + 4) * sc;
-    f16v8 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 hh, ll;
-      split_h(a[e], hh, ll);
-      h[e] = hh; l[e] = ll;
-      split_h(b[e], hh, ll);
-      h[4 + e] = hh; l[4 + e] = ll;
-    }
-    const long blk = i >> 2;            // 32-channel block index (4 threads per block)
-    unsigned char* o = out + blk * 128 + (i & 3) * 16;
-    *reinterpret_cast<f16v8*>(o) = h;
-    *reinterpret_cast<f16v8*>(o + 64) = l;
-  }
-}
-
-// Transposed split for weight-gradient GEMMs (dW = dy^T x reduces over ROWS): fp32 x[rows][C] -> `splits` HL32 matrices
-// out[s][c][rps/32][hi 32 | lo 32] with rps = rows / splits, element (c, r) = scale * x[s*rps + r][c].  One block moves a
-// 32-row x 32-column tile through LDS: coalesced 128-byte row reads, one 128-byte HL32 line per column written.
-__global__ __launch_bounds__(256) void split_hl32_t_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int C,
-                                                           long rows, long rps32, long tiles_c, long ntiles,
-                                                           const float* __restrict__ scale) {
-  __shared__ float tile[32][33];
-  const float sc = scale ? scale[0] : 1.f;
-  const int t = threadIdx.x;
-  for (long id = blockIdx.x; id < ntiles; id += gridDim.x) {
-    const long rb = id / tiles_c;                 // 32-row block (global)
-    const int c0 = (int)(id - rb * tiles_c) * 32;
-    {
-      const int r = t >> 3, c4 = (t & 7) * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c0 + c4 < C && rb * 32 + r < rows) v = *reinterpret_cast<const f32x4*>(x + (rb * 32 + r) * C + c0 + c4);
-      tile[r][c4 + 0] = v[0] * sc; tile[r][c4 + 1] = v[1] * sc; tile[r][c4 + 2] = v[2] * sc; tile[r][c4 + 3] = v[3] * sc;
-    }
-    __syncthreads();
-    {
-      const int c = t >> 3, seg = t & 7;          // column c, rows seg*4 .. +3
-      if (c0 + c < C) {
-        const long s_ = rb / rps32, rl = rb - s_ * rps32;
-        unsigned char* o = out + ((s_ * C + c0 + c) * rps32 + rl) * 128 + seg * 8;
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-        f16v4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 hh, ll;
-          split_h(tile[seg * 4 + e][c], hh, ll);
-          h[e] = hh; l[e] = ll;
-        }
-        *reinterpret_cast<f16v4*>(o) = h;
-        *reinterpret_cast<f16v4*>(o + 64) = l;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// The same transposed split WITH the column sums of x (the bias gradient of a Linear layer is the column sum of the very dy this pass
-// transposes for the weight gradient: two more passes over dy, 100 launches and 2.5 ms of an SVTR loop-A step's weight-gradient stream).
-// grid (column tiles, chunks): a block keeps ONE 32-column tile and walks the 32-row blocks of its chunk four at a time (four 16-byte
-// loads in flight per lane); its column sums (of the scaled values: the scale is a power of two, so 1/s * sum(s x) == sum(x) in the
-// same order) go to partial[chunk][C] (one chunk: straight into colsum); a column-sum pass over those <= 256 rows finishes.  [Measured:
-// the finish inside this kernel -- last block to arrive per column tile, __threadfence() + ticket -- made it 8-15 x slower, 39 -> 324 us
-// at 131072 x 256: every block's agent-scope release writes back an L2 that 2048 blocks keep dirtying with 134 MB of operand lines.]
-__global__ __launch_bounds__(256) void split_hl32_t_colsum_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int C,
-                                                                  long rows, long rps32, long rblocks, long rb_per_chunk,
-                                                                  const float* __restrict__ scale, float* __restrict__ partial,
-                                                                  float* __restrict__ colsum, int accumulate) {
-  __shared__ float tile[4][32][33];
-  const float sc = scale ? scale[0] : 1.f, inv = scale ? scale[1] : 1.f;
-  const int t = threadIdx.x;
-  const int c0 = blockIdx.x * 32, chunk = blockIdx.y, nchunks = gridDim.y;
-  const long rb0 = chunk * rb_per_chunk, rb1 = min(rblocks, rb0 + rb_per_chunk);
-  const int r = t >> 3, c4 = (t & 7) * 4;          // load role: row r of a row block, columns c4 .. +3
-  const int c = t >> 3, seg = t & 7;               // store role: column c, rows seg*4 .. +3
-  float acc = 0.f;
-  for (long rb = rb0; rb < rb1; rb += 4) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const long row = (rb + u) * 32 + r;
-      if (rb + u < rb1 && c0 + c4 < C && row < rows) v[u] = *reinterpret_cast<const f32x4*>(x + row * C + c0 + c4);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      tile[u][r][c4 + 0] = v[u][0] * sc; tile[u][r][c4 + 1] = v[u][1] * sc;
-      tile[u][r][c4 + 2] = v[u][2] * sc; tile[u][r][c4 + 3] = v[u][3] * sc;
-    }
-    __syncthreads();
-    if (c0 + c < C) {
-      typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (rb + u >= rb1) break;
-        const long s_ = (rb + u) / rps32, rl = (rb + u) - s_ * rps32;
-        unsigned char* o = out + ((s_ * C + c0 + c) * rps32 + rl) * 128 + seg * 8;
-        f16v4 h, l;
-        float a = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float f = tile[u][seg * 4 + e][c];
-          _Float16 hh, ll;
-          split_h(f, hh, ll);
-          h[e] = hh; l[e] = ll;
-          a += f;
-        }
-        acc += a;
-        *reinterpret_cast<f16v4*>(o) = h;
-        *reinterpret_cast<f16v4*>(o + 64) = l;
-      }
-    }
-    __syncthreads();
-  }
-  acc += __shfl_xor(acc, 1);
-  acc += __shfl_xor(acc, 2);
-  acc += __shfl_xor(acc, 4);
-  acc *= inv;
-  if (nchunks == 1) {
-    if (seg == 0 && c0 + c < C) colsum[c0 + c] = accumulate ? colsum[c0 + c] + acc : acc;
-    return;
-  }
-  if (seg == 0 && c0 + c < C) partial[(long)chunk * C + c0 + c] = acc;
-}
-
-struct Im2colT {
-  const float* x; unsigned char* out; const float* scale;
-  int B, H, W, C, Ho, Wo, kw, taps, sh, sw, ph, pw;
-  long P, rps32, tiles_c, ntiles;
-};
-
-// one block = (32 output pixels) x (32 channels) of ONE tap; the tap index runs fastest over the grid so the nine taps of a
-// pixel block re-read the same input lines from L2
-__global__ __launch_bounds__(256) void im2col_t_hl32_kernel(const Im2colT p) {
-  __shared__ float tile[32][33];
-  const float sc = p.scale ? p.scale[0] : 1.f;
-  const int t = threadIdx.x;
-  for (long id = blockIdx.x; id < p.ntiles; id += gridDim.x) {
-    const int tap = (int)(id % p.taps);
-    const long id2 = id / p.taps;
-    const long rb = id2 / p.tiles_c;                 // 32-pixel block (global over the padded pixel axis)
-    const int c0 = (int)(id2 - rb * p.tiles_c) * 32;
-    const int ky = tap / p.kw, kx = tap - ky * p.kw;
-    {
-      const int r = t >> 3, c4 = (t & 7) * 4;
-      const long pix = rb * 32 + r;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (pix < p.P && c0 + c4 < p.C) {
-        const int hw = p.Ho * p.Wo;
-        const int b = (int)(pix / hw);
-        const int rem = (int)(pix - (long)b * hw);
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        const int iy = oy * p.sh - p.ph + ky, ix = ox * p.sw - p.pw + kx;
-        if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W)
-          v = *reinterpret_cast<const f32x4*>(p.x + (((long)b * p.H + iy) * p.W + ix) * p.C + c0 + c4);
-      }
-      tile[r][c4 + 0] = v[0] * sc; tile[r][c4 + 1] = v[1] * sc; tile[r][c4 + 2] = v[2] * sc; tile[r][c4 + 3] = v[3] * sc;
-    }
-    __syncthreads();
-    {
-      const int c = t >> 3, seg = t & 7;
-      if (c0 + c < p.C) {
-        const long s_ = rb / p.rps32, rl = rb - s_ * p.rps32;
-        unsigned char* o = p.out + ((((s_ * p.taps + tap) * p.C) + c0 + c) * p.rps32 + rl) * 128 + seg * 8;
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-        f16v4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 hh, ll;
-          split_h(tile[seg * 4 + e][c], hh, ll);
-          h[e] = hh; l[e] = ll;
-        }
-        *reinterpret_cast<f16v4*>(o) = h;
-        *reinterpret_cast<f16v4*>(o + 64) = l;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Transposed split in IMAGE-ROW-MAJOR pixel order, optionally shifted along x: NHWC fp32 x[b][y][xx][c] -> out[c][k / 32][hi 32 | lo 32]
-// with k = (y * B + b) * W + xx and element (c, k) = scale * x[b][y][xx + shift][c] (0 outside the row; k >= P: 0).  The operand layout
-// of the convolution weight gradient without an im2col (mrn_gemm_x3_windows_hl32): in this order a kernel-row offset ky - 1 is
-// a whole number of lines (B * W pixels) and only the THREE horizontal shifts need their own copy.  One block = 32 pixels x 32 channels.
-__global__ __launch_bounds__(256) void transpose_oy_hl32_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int B,
-                                                                int H, int W, int C, int shift, long P, long lines, long tiles_c,
-                                                                long ntiles, const float* __restrict__ scale) {
-  __shared__ float tile[32][33];
-  const float sc = scale ? scale[0] : 1.f;
-  const int t = threadIdx.x;
-  for (long id = blockIdx.x; id < ntiles; id += gridDim.x) {
-    const long kb = id / tiles_c;                 // 32-pixel block along k
-    const int c0 = (int)(id - kb * tiles_c) * 32;
-    {
-      const int r = t >> 3, c4 = (t & 7) * 4;
-      const long k = kb * 32 + r;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (k < P && c0 + c4 < C) {
-        const long row = k / W;                   // = y * B + b
-        const int xx = (int)(k - row * W) + shift;
-        const int y = (int)(row / B), b = (int)(row - (long)y * B);
-        if ((unsigned)xx < (unsigned)W) v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + y) * W + xx) * C + c0 + c4);
-      }
-      tile[r][c4 + 0] = v[0] * sc; tile[r][c4 + 1] = v[1] * sc; tile[r][c4 + 2] = v[2] * sc; tile[r][c4 + 3] = v[3] * sc;
-    }
-    __syncthreads();
-    {
-      const int c = t >> 3, seg = t & 7;          // column c, pixels seg*4 .. +3
-      if (c0 + c < C) {
-        unsigned char* o = out + ((long)(c0 + c) * lines + kb) * 128 + seg * 8;
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-        f16v4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 hh, ll;
-          split_h(tile[seg * 4 + e][c], hh, ll);
-          h[e] = hh; l[e] = ll;
-        }
-        *reinterpret_cast<f16v4*>(o) = h;
-        *reinterpret_cast<f16v4*>(o + 64) = l;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// The three horizontal shifts (-1, 0, +1) of transpose_oy_hl32_kernel from ONE read of the activation: out[s][c][k / 32][...] for
-// s = 0, 1, 2 (copy stride `copy_bytes`).  A block stages pixels k0 - 1 .. k0 + 32 (34 rows) x 32 channels.
-__global__ __launch_bounds__(256) void transpose_oy3_hl32_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int B,
-                                                                 int H, int W, int C, long P, long lines, long tiles_c, long ntiles,
-                                                                 long copy_bytes, const float* __restrict__ scale) {
-  __shared__ float tile[34][33];
-  __shared__ int xpos[34];
-  const float sc = scale ? scale[0] : 1.f;
-  const int t = threadIdx.x;
-  for (long id = blockIdx.x; id < ntiles; id += gridDim.x) {
-    const long kb = id / tiles_c;
-    const int c0 = (int)(id - kb * tiles_c) * 32;
-    for (int i = t; i < 34 * 8; i += 256) {
-      const int r = i >> 3, c4 = (i & 7) * 4;
-      const long k = kb * 32 + r - 1;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      int xx = -1000;
-      if (k >= 0 && k < P) {
-        const long row = k / W;
-        xx = (int)(k - row * W);
-        const int y = (int)(row / B), b = (int)(row - (long)y * B);
-        if (c0 + c4 < C) v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + y) * W + xx) * C + c0 + c4);
-      }
-      if (c4 == 0) xpos[r] = xx;
-      tile[r][c4 + 0] = v[0] * sc; tile[r][c4 + 1] = v[1] * sc; tile[r][c4 + 2] = v[2] * sc; tile[r][c4 + 3] = v[3] * sc;
-    }
-    __syncthreads();
-    {
-      const int c = t >> 3, seg = t & 7;
-      if (c0 + c < C) {
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {              // shift = s - 1: destination pixel j takes source pixel j + shift of the SAME image row
-          f16v4 h, l;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int j = seg * 4 + e;             // destination row of the tile is j + 1, its source j + s
-            const int xd = xpos[j + 1];
-            const bool ok = xd >= 0 && (unsigned)(xd + s - 1) < (unsigned)W;
-            _Float16 hh, ll;
-            split_h(ok ? tile[j + s][c] : 0.f, hh, ll);
-            h[e] = hh; l[e] = ll;
-          }
-          unsigned char* o = out + s * copy_bytes + ((long)(c0 + c) * lines + kb) * 128 + seg * 8;
-          *reinterpret_cast<f16v4*>(o) = h;
-          *reinterpret_cast<f16v4*>(o + 64) = l;
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Transposed operands of the Winograd-domain weight gradient (mrn_conv_wgrad_wino...): NHWC fp32 t[b][y][xx][c] -> out[m][c][kq / 32][hi 32 | lo 32]
-// over GROUPS of 4 columns in image-row-major order kq = (y * B + b) * Wq + q (Wq = ceil(W / 4)), six components m per group:
-//   MODE 0 (the layer input x):       V_m  = sum_j B^T[m][j] * x[.., 4q - 1 + j]   (j = 0..5, zero outside the row)
-//   MODE 1 (the output gradient dy):  dY_m = sum_r A^T[r][m] * dy[.., 4q + r]      (r = 0..3, zero beyond W)
-// times scale[0].  With these, dU_m[ky] = sum over groups of dY_m (x) V_m (row-shifted by ky - 1) and dW[ky][kx] = sum_m G[m][kx] dU_m[ky]:
-// 18 K-windows of length P/4 instead of 9 of length P -- half the matrix work -- and ONE 1.5x copy of x^T instead of three shifted copies.
-// One block = 32 groups x 32 channels through LDS.
-template <int MODE>
-__global__ __launch_bounds__(256) void transpose_oy_wino_hl32_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int B, int H,
-                                                                     int W, int Wq, int C, long Pq, long lines, long tiles_c, long ntiles,
-                                                                     const float* __restrict__ scale) {
-  constexpr int NCOL = MODE == 0 ? 6 : 4;
-  __shared__ float tile[32 * NCOL][33];
-  const float sc = scale ? scale[0] : 1.f;
-  const int t = threadIdx.x;
-  for (long id = blockIdx.x; id < ntiles; id += gridDim.x) {
-    const long kb = id / tiles_c;
-    const int c0 = (int)(id - kb * tiles_c) * 32;
-    for (int i = t; i < 32 * NCOL * 8; i += 256) {
-      const int rr = i >> 3, c4 = (i & 7) * 4;          // rr = group-in-block * NCOL + column
-      const int gq = rr / NCOL, j = rr - gq * NCOL;
-      const long kq = kb * 32 + gq;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (kq < Pq && c0 + c4 < C) {
-        const long row = kq / Wq;                        // = y * B + b
-        const int q = (int)(kq - row * Wq);
-        const int xx = 4 * q + j - (MODE == 0 ? 1 : 0);
-        const int y = (int)(row / B), b = (int)(row - (long)y * B);
-        if ((unsigned)xx < (unsigned)W) v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + y) * W + xx) * C + c0 + c4);
-      }
-      tile[rr][c4 + 0] = v[0]; tile[rr][c4 + 1] = v[1]; tile[rr][c4 + 2] = v[2]; tile[rr][c4 + 3] = v[3];
-    }
-    __syncthreads();
-    {
-      const int c = t >> 3, seg = t & 7;                 // channel c, groups seg*4 .. +3 of the block
-      if (c0 + c < C) {
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-        f16v4 h[6], l[6];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int gq = seg * 4 + e;
-          float m_[6];
-          if constexpr (MODE == 0) {
-            const float d0 = tile[gq * 6 + 0][c], d1 = tile[gq * 6 + 1][c], d2 = tile[gq * 6 + 2][c], d3 = tile[gq * 6 + 3][c],
-                        d4 = tile[gq * 6 + 4][c], d5 = tile[gq * 6 + 5][c];
-            m_[0] = 4.f * d0 - 5.f * d2 + d4;
-            m_[1] = -4.f * (d1 + d2) + d3 + d4;
-            m_[2] = 4.f * (d1 - d2) - d3 + d4;
-            m_[3] = 2.f * (d3 - d1) - d2 + d4;
-            m_[4] = 2.f * (d1 - d3) - d2 + d4;
-            m_[5] = 4.f * d1 - 5.f * d3 + d5;
-          } else {
-            const float y0 = tile[gq * 4 + 0][c], y1 = tile[gq * 4 + 1][c], y2 = tile[gq * 4 + 2][c], y3 = tile[gq * 4 + 3][c];
-            m_[0] = y0;                                  // columns of A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
-            m_[1] = y0 + y1 + y2 + y3;
-            m_[2] = y0 - y1 + y2 - y3;
-            m_[3] = y0 + 2.f * y1 + 4.f * y2 + 8.f * y3;
-            m_[4] = y0 - 2.f * y1 + 4.f * y2 - 8.f * y3;
-            m_[5] = y3;
-          }
-#pragma unroll
-          for (int k = 0; k < 6; ++k) {
-            _Float16 hh, ll;
-            split_h(m_[k] * sc, hh, ll);
-            h[k][e] = hh; l[k][e] = ll;
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          unsigned char* o = out + (((long)k * C + c0 + c) * lines + kb) * 128 + seg * 8;
-          *reinterpret_cast<f16v4*>(o) = h[k];
-          *reinterpret_cast<f16v4*>(o + 64) = l[k];
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// dW [Cout][3][3][Cin] = sum over split-K chunks s and components m of G[m][kx] * part[s][m * 3 + ky][co][ci]  (G of F(4,3), unfolded);
-// one lane = 4 consecutive input channels (Cin % 4 == 0) of ONE kernel row (blockIdx.y = ky: the three rows are independent, and a
-// 512 x 512 layer has only 65536 channel quads -- one wave per SIMD without the split): 6 accumulators, two split-K slabs in flight
-// OIHW_ACC: dW is ADDED into the parameter's own [Cout][Cin][3][3] gradient (the flat-gradient slice)
-template <bool OIHW_ACC>
-__global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const float* __restrict__ part, float* __restrict__ dw, int S, long CC4, int Cin4) {
-  const float G[6][3] = {{0.25f, 0.f, 0.f}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
-                         {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
-  const f32x4* p4 = reinterpret_cast<const f32x4*>(part);
-  const int ky = blockIdx.y;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < CC4; i += (long)gridDim.x * 256) {      // i = (co * Cin + ci) / 4
-    const long co = i / Cin4;
-    const int c4 = (int)(i - co * Cin4);
-    f32x4 u[6], w[6];
-#pragma unroll
-    for (int m = 0; m < 6; ++m) u[m] = w[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int s_ = 0;
-    for (; s_ + 1 < S; s_ += 2) {
-#pragma unroll
-      for (int m = 0; m < 6; ++m) {
-        u[m] += p4[((long)s_ * 18 + m * 3 + ky) * CC4 + i];
-        w[m] += p4[((long)(s_ + 1) * 18 + m * 3 + ky) * CC4 + i];
-      }
-    }
-    if (s_ < S) {
-#pragma unroll
-      for (int m = 0; m < 6; ++m) u[m] += p4[((long)s_ * 18 + m * 3 + ky) * CC4 + i];
-    }
-#pragma unroll
-    for (int m = 0; m < 6; ++m) u[m] += w[m];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < 6; ++m) v += G[m][kx] * u[m];
-      if constexpr (OIHW_ACC) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dw[((co * Cin4 + c4) * 4 + j) * 9 + ky * 3 + kx] += v[j];
-      } else {
-        reinterpret_cast<f32x4*>(dw)[((co * 3 + ky) * 3 + kx) * Cin4 + c4] = v;
-      }
-    }
-  }
-}
-
-// w [Cout][taps][Cin] fp32 (x scale[0]) -> [Cout][Cin/32][taps][hi 32 | lo 32]; one thread = 8 channels
-__global__ __launch_bounds__(256) void pack_weight_hl32_kernel(const float* __restrict__ w, unsigned char* __restrict__ out,
-                                                               int Cout, int taps, int Cin, const float* __restrict__ scale) {
-  const float sc = scale ? scale[0] : 1.f;
-  const int Cb = Cin >> 5;
-  const long n8 = (long)Cout * taps * (Cin >> 3);
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-    const int c8 = (int)(i % (Cin >> 3));
-    const long r = i / (Cin >> 3);
-    const int tap = (int)(r % taps);
-    const long o_ = r / taps;
-    const float* src = w + (o_ * taps + tap) * Cin + c8 * 8;
-    f16v8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 hh, ll;
-      split_h(src[e] * sc, hh, ll);
-      h[e] = hh; l[e] = ll;
-    }
-    const int cb = c8 >> 2;
-    unsigned char* o = out + ((o_ * Cb + cb) * taps + tap) * 128 + (c8 & 3) * 16;
-    *reinterpret_cast<f16v8*>(o) = h;
-    *reinterpret_cast<f16v8*>(o + 64) = l;
-  }
-}
-
 // (magic, shift) with n / d == umulhi(n, magic) >> shift for every 0 <= n < 2^31
 void magic_div(unsigned d, unsigned& magic, int& shift) {
   if (d <= 1) {            // encoded as magic 0 (fast_div returns n)
@@ -1123,6 +662,32 @@ int launch_x3(const ConvX3Params& p0, hipStream_t st) {
   hipLaunchKernelGGL((conv_x3_kernel<WAVES_M, WAVES_N, WM, WN, HL_OUT, NPROD, WINO>), dim3((unsigned)tiles), dim3(WAVES_M * WAVES_N * 64), ldsz, st, p);
   MRN_LAUNCH_CHECK("conv2d_x3_hl32");
   return MRN_OK;
+}
+
+// The one map from (tile_m x tile_n, HL32 result, products) to the instantiation that runs it -- exactly the combinations instantiated
+// above.  256x256: 16 waves (64x64 wave tiles, four waves per SIMD) hide the per-K-step LDS / barrier stalls better than 8 waves with
+// 128x64 tiles: 464 vs 438 TFLOP/s on the dominant shape (w8: the 8-wave variant for A/B runs).  64x64 and 128x64 exist for the
+// fp32-result x3 form only (weight-gradient GEMMs of the narrow layers).
+template <bool HL_OUT, int NPROD>
+int launch_x3_tile(int tile_m, int tile_n, bool w8, const ConvX3Params& p, hipStream_t st) {
+  if constexpr (!HL_OUT && NPROD == 3) {
+    if (tile_m == 64 && tile_n == 64) return launch_x3<2, 2, 1, 1>(p, st);
+    if (tile_m == 128 && tile_n == 64) return launch_x3<4, 1, 1, 2>(p, st);
+    if (tile_m == 256 && tile_n == 256 && w8) return launch_x3<2, 4, 4, 2>(p, st);
+  }
+  if (tile_m == 256 && tile_n == 256) return launch_x3<4, 4, 2, 2, HL_OUT, NPROD>(p, st);
+  if (tile_m == 256 && tile_n == 128) return launch_x3<4, 2, 2, 2, HL_OUT, NPROD>(p, st);
+  if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2, HL_OUT, NPROD>(p, st);
+  if (tile_m == 128 && tile_n == 128) return launch_x3<4, 2, 1, 2, HL_OUT, NPROD>(p, st);
+  mrn_set_error("conv_x3: no %dx%d tile with%s the HL32 result and %d product(s)", tile_m, tile_n, HL_OUT ? "" : "out", NPROD);
+  return MRN_ERR_UNSUPPORTED;
+}
+
+// products == 1: the reduced-precision mode, one fp16 product per term (the lo halves stay unread); HL32 result: separate instantiations,
+// the store path of the plain kernels stays as it was
+int launch_x3_tile(int tile_m, int tile_n, bool hl_out, int products, bool w8, const ConvX3Params& p, hipStream_t st) {
+  if (products == 1) return hl_out ? launch_x3_tile<true, 1>(tile_m, tile_n, w8, p, st) : launch_x3_tile<false, 1>(tile_m, tile_n, w8, p, st);
+  return hl_out ? launch_x3_tile<true, 3>(tile_m, tile_n, w8, p, st) : launch_x3_tile<false, 3>(tile_m, tile_n, w8, p, st);
 }
 
 }  // namespace
@@ -1177,273 +742,7 @@ MRN_EXPORT int mrn_conv2d_x3_hl32(const void* x_hl, const void* w_hl, const void
   magic_div((unsigned)Wo, p.wo_magic, p.wo_shift);
   magic_div((unsigned)p.BWo, p.bw_magic, p.bw_shift);
   magic_div((unsigned)kw, p.kw_magic, p.kw_shift);
-  // 256x256: 16 waves (64x64 wave tiles, four waves per SIMD) hide the per-K-step LDS / barrier stalls better than 8 waves
-  // with 128x64 tiles: 464 vs 438 TFLOP/s on the dominant shape (MRN_X3_W8=1 selects the 8-wave variant for A/B runs)
-  if (products == 1) {   // reduced-precision mode: one fp16 product per term, the lo halves stay unread
-    hipStream_t st1 = (hipStream_t)stream;
-    if (y_hl32) {
-      if (tile_n == 256) return launch_x3<4, 4, 2, 2, true, 1>(p, st1);
-      if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2, true, 1>(p, st1);
-      if (tile_m == 256) return launch_x3<4, 2, 2, 2, true, 1>(p, st1);
-      return launch_x3<4, 2, 1, 2, true, 1>(p, st1);
-    }
-    if (tile_n == 256) return launch_x3<4, 4, 2, 2, false, 1>(p, st1);
-    if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2, false, 1>(p, st1);
-    if (tile_m == 256) return launch_x3<4, 2, 2, 2, false, 1>(p, st1);
-    return launch_x3<4, 2, 1, 2, false, 1>(p, st1);
-  }
-  if (y_hl32) {     // separate instantiations: the store path of the plain kernels stays as it was
-    if (tile_n == 256) return launch_x3<4, 4, 2, 2, true>(p, (hipStream_t)stream);
-    if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2, true>(p, (hipStream_t)stream);
-    if (tile_m == 256) return launch_x3<4, 2, 2, 2, true>(p, (hipStream_t)stream);
-    return launch_x3<4, 2, 1, 2, true>(p, (hipStream_t)stream);
-  }
-  if (tile_n == 256 && env_flags().w8) return launch_x3<2, 4, 4, 2>(p, (hipStream_t)stream);
-  if (tile_n == 256) return launch_x3<4, 4, 2, 2>(p, (hipStream_t)stream);
-  if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2>(p, (hipStream_t)stream);
-  if (tile_m == 256) return launch_x3<4, 2, 2, 2>(p, (hipStream_t)stream);
-  return launch_x3<4, 2, 1, 2>(p, (hipStream_t)stream);
-}
-
-// fp32 [rows][C] (C % 32 == 0) -> HL32 of scale[0] * x (scale: device float[2] from mrn_pow2_scale_f32, or NULL)
-MRN_EXPORT int mrn_split_hl32_f32(const float* x, void* out, int64_t rows, int C, const float* scale, void* stream) {
-  MRN_CHECK_ARG(x && out && C % 32 == 0, "mrn_split_hl32_f32: bad operands (C=%d)", C);
-  const long n8 = rows * (C / 8);
-  if (n8 == 0) return MRN_OK;
-  long grid = (n8 + 255) / 256;
-  if (grid > 16384) grid = 16384;
-  hipLaunchKernelGGL(split_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (unsigned char*)out, n8, scale);
-  MRN_LAUNCH_CHECK("split_hl32");
-  return MRN_OK;
-}
-
-// w [Cout][kh*kw][Cin] fp32 -> HL32 weight [Cout][Cin/32][kh*kw][128 B], multiplied by scale[0] (device) when given
-MRN_EXPORT int mrn_pack_weight_hl32(const float* w_ohwi, void* out, int Cout, int taps, int Cin, const float* scale,
-                                    void* stream) {
-  MRN_CHECK_ARG(w_ohwi && out && Cin % 32 == 0, "mrn_pack_weight_hl32: bad operands (Cin=%d)", Cin);
-  const long n8 = (long)Cout * taps * (Cin / 8);
-  if (n8 == 0) return MRN_OK;
-  long grid = (n8 + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(pack_weight_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w_ohwi,
-                     (unsigned char*)out, Cout, taps, Cin, scale);
-  MRN_LAUNCH_CHECK("pack_weight_hl32");
-  return MRN_OK;
-}
-
-// Every trained Linear weight's operands for the coming step in ONE call (3 stream operations): the per-weight sequence max|W| ->
-// power-of-two prescale -> HL32 pack [-> the same for W^T, the data gradient's operand] was 6 launches per layer, ~310 per SVTR loop-A
-// step, issued by the host while the forward pass waited (a host-bound step: 1287 dispatches in 27 ms of host time).
-// desc: n x 8 int64 on the device {W (fp32 [N][K]), out, scale (float[2]), N, K, transposed, first_tile, tiles_i}: the operand is
-// L = W (O = N, I = K) or L = W^T (O = K, I = N), out [O][I/32][128 B] = HL32 of s * L, s = 2^floor(log2(target / max|W|)) exactly as
-// mrn_pow2_scale_f32 + mrn_pack_weight_hl32 produce it.  amax: n zeroed-by-this-call words.  One block = one 32 x 32 tile of L.
-namespace {
-struct MultiPackDesc { const float* w; unsigned char* out; float* scale; long N, K, transposed, first_tile, tiles_i; };
-
-__device__ __forceinline__ int multi_pack_find(const MultiPackDesc* __restrict__ d, int n, long tile) {
-  int lo = 0, hi = n - 1;                       // last descriptor with first_tile <= tile
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (d[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void multi_pack_amax_kernel(const MultiPackDesc* __restrict__ desc, int n, unsigned* __restrict__ amax) {
-  __shared__ float scratch[4];
-  const int di = multi_pack_find(desc, n, blockIdx.x);
-  const MultiPackDesc d = desc[di];
-  const long tl = blockIdx.x - d.first_tile;
-  const long to = tl / d.tiles_i, ti = tl - to * d.tiles_i;
-  // the tile of L as a 32 x 32 region of the SOURCE matrix [N][K]: rows = o (plain) or i (transposed), columns the other index
-  const long r0 = (d.transposed ? ti : to) * 32, c0 = (d.transposed ? to : ti) * 32;
-  const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
-  float m = 0.f;
-  if (r0 + r < d.N && c0 + c4 < d.K) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(d.w + (r0 + r) * d.K + c0 + c4);
-    m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-  }
-  m = block_max<256>(m, scratch);
-  if (threadIdx.x == 0 && !(m <= 0.f)) atomicMax(amax + di, __float_as_uint(m));      // NaN / inf pass through
-}
-
-__global__ __launch_bounds__(256) void multi_pack_kernel(const MultiPackDesc* __restrict__ desc, int n, const unsigned* __restrict__ amax,
-                                                         float target) {
-  __shared__ float tile[32][33];
-  const int di = multi_pack_find(desc, n, blockIdx.x);
-  const MultiPackDesc d = desc[di];
-  const long tl = blockIdx.x - d.first_tile;
-  const long to = tl / d.tiles_i, ti = tl - to * d.tiles_i;
-  const float mm = __uint_as_float(amax[di]);
-  float sc = 1.f;
-  if (mm > 0.f && isfinite(mm)) sc = exp2f(floorf(log2f(target / mm)));
-  if (tl == 0 && threadIdx.x == 0) {
-    d.scale[0] = sc;
-    d.scale[1] = 1.f / sc;
-  }
-  const long O = d.transposed ? d.K : d.N, Cb = (d.transposed ? d.N : d.K) >> 5;
-  const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (!d.transposed) {
-    if (to * 32 + r < O) v = *reinterpret_cast<const f32x4*>(d.w + (to * 32 + r) * d.K + ti * 32 + c4);
-    tile[r][c4 + 0] = v[0] * sc; tile[r][c4 + 1] = v[1] * sc; tile[r][c4 + 2] = v[2] * sc; tile[r][c4 + 3] = v[3] * sc;
-  } else {        // source row = i, source columns = o: lands transposed
-    if (to * 32 + c4 < O) v = *reinterpret_cast<const f32x4*>(d.w + (ti * 32 + r) * d.K + to * 32 + c4);
-    tile[c4 + 0][r] = v[0] * sc; tile[c4 + 1][r] = v[1] * sc; tile[c4 + 2][r] = v[2] * sc; tile[c4 + 3][r] = v[3] * sc;
-  }
-  __syncthreads();
-  const int o = threadIdx.x >> 3, seg = threadIdx.x & 7;          // row o of the tile, elements seg*4 .. +3 of its 32-channel line
-  if (to * 32 + o < O) {
-    typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-    f16v4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 hh, ll;
-      split_h(tile[o][seg * 4 + e], hh, ll);
-      h[e] = hh; l[e] = ll;
-    }
-    unsigned char* dst = d.out + ((to * 32 + o) * Cb + ti) * 128 + seg * 8;
-    *reinterpret_cast<f16v4*>(dst) = h;
-    *reinterpret_cast<f16v4*>(dst + 64) = l;
-  }
-}
-}  // namespace
-
-MRN_EXPORT int mrn_multi_pack_linear_hl32(const void* desc, int n, int64_t tiles, void* amax, float target, void* stream) {
-  MRN_CHECK_ARG(desc && amax && n > 0 && tiles > 0 && tiles < (1L << 31) && target > 0.f, "mrn_multi_pack_linear_hl32: bad operands (n=%d)", n);
-  const hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(amax, 0, sizeof(unsigned) * (size_t)n, st);
-  MRN_CHECK_ARG(e == hipSuccess, "mrn_multi_pack_linear_hl32: memset failed (%s)", hipGetErrorString(e));
-  hipLaunchKernelGGL(multi_pack_amax_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (const MultiPackDesc*)desc, n, (unsigned*)amax);
-  hipLaunchKernelGGL(multi_pack_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (const MultiPackDesc*)desc, n, (const unsigned*)amax, target);
-  MRN_LAUNCH_CHECK("multi_pack_linear_hl32");
-  return MRN_OK;
-}
-
-// fp32 x[rows][C] (C % 4 == 0) -> `splits` transposed HL32 matrices [splits][C][rows_padded/splits/32][128 B] of scale[0] * x
-// (rows_padded % (32 * splits) == 0, rows beyond `rows` are zero): the operand layout of a weight-gradient GEMM that
-// reduces over rows, split-K = groups.
-MRN_EXPORT int mrn_split_hl32_t_f32(const float* x, void* out, int64_t rows, int64_t rows_padded, int C, int splits,
-                                    const float* scale, void* stream) {
-  MRN_CHECK_ARG(x && out && splits >= 1 && C % 4 == 0 && rows_padded >= rows && rows_padded % (32L * splits) == 0,
-                "mrn_split_hl32_t_f32: bad operands (rows=%ld padded=%ld C=%d splits=%d)", (long)rows, (long)rows_padded, C, splits);
-  if (rows_padded == 0 || C == 0) return MRN_OK;
-  const long tiles_c = (C + 31) / 32, ntiles = rows_padded / 32 * tiles_c;
-  long grid = ntiles > 65536 ? 65536 : ntiles;
-  hipLaunchKernelGGL(split_hl32_t_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (unsigned char*)out, C,
-                     (long)rows, (long)(rows_padded / splits / 32), tiles_c, ntiles, scale);
-  MRN_LAUNCH_CHECK("split_hl32_t");
-  return MRN_OK;
-}
-
-// mrn_split_hl32_t_f32 that also leaves colsum[c] (+)= sum over rows of x[r][c].  partial: mrn_split_hl32_t_colsum_chunks(rows_padded, C) * C
-// floats of scratch (unused with one chunk).
-extern "C" int mrn_colsum_f32(const float* in, int64_t ld, float* out, float* workspace, int64_t rows, int C, int accumulate, void* stream);
-
-MRN_EXPORT int64_t mrn_split_hl32_t_colsum_chunks(int64_t rows_padded, int C) {
-  const long rblocks = rows_padded / 32, tiles_c = (C + 31) / 32;
-  long want = 4096 / (tiles_c < 1 ? 1 : tiles_c);
-  want = want < 1 ? 1 : (want > 256 ? 256 : want);
-  long per = (rblocks + want - 1) / want;
-  per = (per + 3) / 4 * 4;                             // (four row blocks per iteration)
-  const long chunks = per > 0 ? (rblocks + per - 1) / per : 1;
-  return chunks < 1 ? 1 : chunks;
-}
-
-MRN_EXPORT int mrn_split_hl32_t_colsum_f32(const float* x, void* out, int64_t rows, int64_t rows_padded, int C, int splits,
-                                           const float* scale, float* colsum, int accumulate, float* partial, void* stream) {
-  MRN_CHECK_ARG(x && out && colsum && splits >= 1 && C % 4 == 0 && rows_padded >= rows && rows_padded % (32L * splits) == 0,
-                "mrn_split_hl32_t_colsum_f32: bad operands (rows=%ld padded=%ld C=%d splits=%d)", (long)rows, (long)rows_padded, C, splits);
-  if (rows_padded == 0 || C == 0) return MRN_OK;
-  const long rblocks = rows_padded / 32, tiles_c = (C + 31) / 32;
-  const long chunks = mrn_split_hl32_t_colsum_chunks(rows_padded, C);
-  const long per = (((rblocks + chunks - 1) / chunks) + 3) / 4 * 4;
-  MRN_CHECK_ARG(chunks == 1 || partial, "mrn_split_hl32_t_colsum_f32: %ld chunks need the scratch rows", chunks);
-  MRN_CHECK_ARG(per * chunks >= rblocks && chunks <= 512, "mrn_split_hl32_t_colsum_f32: bad chunking (%ld x %ld < %ld)", per, chunks, rblocks);
-  hipLaunchKernelGGL(split_hl32_t_colsum_kernel, dim3((unsigned)tiles_c, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, x,
-                     (unsigned char*)out, C, (long)rows, (long)(rows_padded / splits / 32), rblocks, per, scale, partial, colsum, accumulate);
-  MRN_LAUNCH_CHECK("split_hl32_t_colsum");
-  if (chunks > 1) return mrn_colsum_f32(partial, C, colsum, nullptr, chunks, C, accumulate, stream);     // (<= 512 rows: one pass)
-  return MRN_OK;
-}
-
-// Transposed im2col for the convolution weight gradient dW[co][tap][ci] = sum_p dy[p][co] * x[pixel(p, tap)][ci]:
-//   out[s][tap][ci][rps/32][hi 32 | lo 32], element (tap, ci, p) = scale * x[b][oy*sh + ky - ph][ox*sw + kx - pw][ci]
-// (zero outside the image / beyond P = B*Ho*Wo), p = s*rps + r the output pixel.  x NHWC [B][H][W][C], C % 4 == 0.
-MRN_EXPORT int mrn_im2col_t_hl32_f32(const float* x, void* out, int B, int H, int W, int C, int kh, int kw, int sh, int sw,
-                                     int ph, int pw, int64_t rows_padded, int splits, const float* scale, void* stream) {
-  MRN_CHECK_ARG(x && out && splits >= 1 && C % 4 == 0 && rows_padded % (32L * splits) == 0, "mrn_im2col_t_hl32_f32: bad operands");
-  const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
-  MRN_CHECK_ARG(Ho > 0 && Wo > 0 && rows_padded >= (long)B * Ho * Wo, "mrn_im2col_t_hl32_f32: bad geometry");
-  if (rows_padded == 0 || C == 0) return MRN_OK;
-  Im2colT p;
-  p.x = x; p.out = (unsigned char*)out; p.scale = scale;
-  p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.kw = kw; p.taps = kh * kw;
-  p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw;
-  p.P = (long)B * Ho * Wo; p.rps32 = rows_padded / splits / 32; p.tiles_c = (C + 31) / 32;
-  p.ntiles = rows_padded / 32 * p.tiles_c * p.taps;
-  long grid = p.ntiles > 262144 ? 262144 : p.ntiles;
-  hipLaunchKernelGGL(im2col_t_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
-  MRN_LAUNCH_CHECK("im2col_t_hl32");
-  return MRN_OK;
-}
-
-// x NHWC [B][H][W][C] fp32 -> transposed HL32 matrix [C][lines][128 B] (lines = ceil(B*H*W / 32)) in image-row-major pixel order
-// k = (y*B + b)*W + xx, shifted by shift_x pixels along x with zero fill: see transpose_oy_hl32_kernel
-MRN_EXPORT int mrn_transpose_oy_hl32_f32(const float* x, void* out, int B, int H, int W, int C, int shift_x, const float* scale,
-                                         void* stream) {
-  MRN_CHECK_ARG(x && out && C % 4 == 0 && B > 0 && H > 0 && W > 0, "mrn_transpose_oy_hl32_f32: bad operands");
-  const long P = (long)B * H * W, lines = (P + 31) / 32, tiles_c = (C + 31) / 32, ntiles = lines * tiles_c;
-  long grid = ntiles > 65536 ? 65536 : ntiles;
-  hipLaunchKernelGGL(transpose_oy_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (unsigned char*)out, B, H, W,
-                     C, shift_x, P, lines, tiles_c, ntiles, scale);
-  MRN_LAUNCH_CHECK("transpose_oy_hl32");
-  return MRN_OK;
-}
-
-// the three copies shift_x = -1, 0, +1 of mrn_transpose_oy_hl32_f32 in one pass: out [3][C][lines][128 B]
-MRN_EXPORT int mrn_transpose_oy3_hl32_f32(const float* x, void* out, int B, int H, int W, int C, const float* scale, void* stream) {
-  MRN_CHECK_ARG(x && out && C % 4 == 0 && B > 0 && H > 0 && W > 0, "mrn_transpose_oy3_hl32_f32: bad operands");
-  const long P = (long)B * H * W, lines = (P + 31) / 32, tiles_c = (C + 31) / 32, ntiles = lines * tiles_c;
-  long grid = ntiles > 65536 ? 65536 : ntiles;
-  hipLaunchKernelGGL(transpose_oy3_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (unsigned char*)out, B, H,
-                     W, C, P, lines, tiles_c, ntiles, (long)C * lines * 128, scale);
-  MRN_LAUNCH_CHECK("transpose_oy3_hl32");
-  return MRN_OK;
-}
-
-// The two operand passes and the final reduction of the Winograd-domain weight gradient of a 3x3 / stride 1 / pad 1 convolution
-// (transpose_oy_wino_hl32_kernel, wino_wgrad_finish_kernel): t NHWC [B][H][W][C] fp32 -> out [6][C][ceil(B*H*ceil(W/4) / 32)][128 B];
-// mode 0 = layer input (B^T over 6 columns), mode 1 = output gradient (A over 4 columns).
-MRN_EXPORT int mrn_transpose_oy_wino_hl32_f32(const float* t, void* out, int B, int H, int W, int C, int mode, const float* scale,
-                                              void* stream) {
-  MRN_CHECK_ARG(t && out && C % 4 == 0 && B > 0 && H > 0 && W > 0 && (mode == 0 || mode == 1), "mrn_transpose_oy_wino_hl32_f32: bad operands");
-  const int Wq = (W + 3) / 4;
-  const long Pq = (long)B * H * Wq, lines = (Pq + 31) / 32, tiles_c = (C + 31) / 32, ntiles = lines * tiles_c;
-  long grid = ntiles > 65536 ? 65536 : ntiles;
-  if (mode == 0)
-    hipLaunchKernelGGL(transpose_oy_wino_hl32_kernel<0>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, t, (unsigned char*)out, B,
-                       H, W, Wq, C, Pq, lines, tiles_c, ntiles, scale);
-  else
-    hipLaunchKernelGGL(transpose_oy_wino_hl32_kernel<1>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, t, (unsigned char*)out, B,
-                       H, W, Wq, C, Pq, lines, tiles_c, ntiles, scale);
-  MRN_LAUNCH_CHECK("transpose_oy_wino_hl32");
-  return MRN_OK;
-}
-
-// part [S][18][Cout][Cin] (group (m, ky) = m * 3 + ky of split-K chunk s, from mrn_gemm_x3_windows_hl32) -> dW [Cout][3][3][Cin]
-// (oihw_accumulate 0), or ADDED into dW [Cout][Cin][3][3], the parameter's own layout (oihw_accumulate 1)
-MRN_EXPORT int mrn_wino_wgrad_finish_f32(const float* part, float* dw, int S, int Cout, int Cin, int oihw_accumulate, void* stream) {
-  MRN_CHECK_ARG(part && dw && S >= 1 && Cout >= 1 && Cin >= 4 && Cin % 4 == 0, "mrn_wino_wgrad_finish_f32: bad operands (Cin %% 4 == 0)");
-  const long CC4 = (long)Cout * Cin / 4;
-  long grid = (CC4 + 255) / 256;
-  if (grid > 16384) grid = 16384;
-  if (oihw_accumulate)
-    hipLaunchKernelGGL(wino_wgrad_finish_kernel<true>, dim3((unsigned)grid, 3), dim3(256), 0, (hipStream_t)stream, part, dw, S, CC4, Cin / 4);
-  else
-    hipLaunchKernelGGL(wino_wgrad_finish_kernel<false>, dim3((unsigned)grid, 3), dim3(256), 0, (hipStream_t)stream, part, dw, S, CC4, Cin / 4);
-  MRN_LAUNCH_CHECK("wino_wgrad_finish");
-  return MRN_OK;
+  return launch_x3_tile(tile_m, tile_n, y_hl32 != nullptr, products, env_flags().w8, p, (hipStream_t)stream);   // (MRN_X3_W8=1: the 8-wave 256x256)
 }
 
 // Grouped GEMM over K-WINDOWS of two shared HL32 matrices on the conv_x3 kernel: for group g,
@@ -1479,119 +778,7 @@ MRN_EXPORT int mrn_gemm_x3_windows_hl32(const void* a_hl, int64_t a_bytes, int a
   magic_div(1u, p.kw_magic, p.kw_shift);
   // both operands carry their own power-of-two prescale: the epilogue multiplies by out_scale[1] * x_scale[1]; ONE pair serves every group
   p.out_scale = out_scale; p.os_stride = 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (products == 1) {
-    if (tile_n == 256) return launch_x3<4, 4, 2, 2, false, 1>(p, st);
-    if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2, false, 1>(p, st);
-    if (tile_m == 256) return launch_x3<4, 2, 2, 2, false, 1>(p, st);
-    return launch_x3<4, 2, 1, 2, false, 1>(p, st);
-  }
-  if (tile_m == 64) return launch_x3<2, 2, 1, 1>(p, st);
-  if (tile_m == 128 && tile_n == 64) return launch_x3<4, 1, 1, 2>(p, st);
-  if (tile_n == 256) return launch_x3<4, 4, 2, 2>(p, st);
-  if (tile_m == 256 && tile_n == 64) return launch_x3<8, 1, 1, 2>(p, st);
-  if (tile_m == 256) return launch_x3<4, 2, 2, 2>(p, st);
-  return launch_x3<4, 2, 1, 2>(p, st);
-}
-
-// ---- Winograd F(R,3) along W: weight transform + the convolution entry point ----------------------------------------------------
-namespace {
-
-// rows of G (F(4,3): interpolation points 0, +-1, +-2, inf; F(2,3): 0, +-1, inf) times the power-of-two row scale whose inverse
-// WinoAT folds into A^T, so that every transformed row sum of |.| stays <= 1.5 and ONE per-tensor prescale serves all components
-__device__ __forceinline__ double wino_g(int R, int m, int kx) {
-  if (R == 2) {
-    const double g[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
-    return g[m][kx];
-  }
-  const double g[6][3] = {{1, 0, 0},
-                          {-1. / 3, -1. / 3, -1. / 3},
-                          {-1. / 3, 1. / 3, -1. / 3},
-                          {1. / 12, 1. / 6, 1. / 3},
-                          {1. / 12, -1. / 6, 1. / 3},
-                          {0, 0, 1}};
-  return g[m][kx];
-}
-
-// w [Cout][3][3][Cin] fp32 (OHWI) -> U [Cout][NC][Cin/32][3 (ky)][hi 32 | lo 32] with U_m = scale * sum_kx G[m][kx] * w[.][ky][kx][.],
-// the sum in double, split to hi + lo from the double; one thread = 8 channels of one (cout, component, ky)
-__global__ __launch_bounds__(256) void pack_weight_wino_hl32_kernel(const float* __restrict__ w, unsigned char* __restrict__ out,
-                                                                    int Cout, int Cin, int R, const float* __restrict__ scale, int dense) {
-  const double sc = scale ? (double)scale[0] : 1.0;
-  const int Cb = Cin >> 5, NC = R + 2;
-  const long n8 = (long)Cout * NC * 3 * (Cin >> 3);
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-    const int c8 = (int)(i % (Cin >> 3));
-    long r = i / (Cin >> 3);
-    const int ky = (int)(r % 3);
-    r /= 3;
-    const int m = (int)(r % NC);
-    const long o_ = r / NC;
-    const float* src = w + ((o_ * 3 + ky) * 3) * Cin + c8 * 8;       // [kx][Cin]
-    f16v8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      double u = 0.0;
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) u += wino_g(R, m, kx) * (double)src[kx * Cin + e];
-      u *= sc;
-      const _Float16 hh = (_Float16)u;
-      const _Float16 ll = (_Float16)(u - (double)hh);
-      h[e] = hh; l[e] = ll;
-    }
-    if (dense) {           // plain fp16 (dense == 2: bfloat16), 64 channels per line: [Cout][NC][Cin/64][3][128 B]
-      unsigned char* dst = out + (((o_ * NC + m) * (Cin >> 6) + (c8 >> 3)) * 3 + ky) * 128 + (c8 & 7) * 16;
-      if (dense == 2) {
-        typedef unsigned short u16v8 __attribute__((ext_vector_type(8)));
-        u16v8 b;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          double u = 0.0;
-#pragma unroll
-          for (int kx = 0; kx < 3; ++kx) u += wino_g(R, m, kx) * (double)src[kx * Cin + e];
-          const unsigned bits = __float_as_uint((float)(u * sc));
-          b[e] = (unsigned short)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
-        }
-        *reinterpret_cast<u16v8*>(dst) = b;
-      } else {
-        *reinterpret_cast<f16v8*>(dst) = h;
-      }
-      continue;
-    }
-    const int cb = c8 >> 2;
-    unsigned char* o = out + (((o_ * NC + m) * Cb + cb) * 3 + ky) * 128 + (c8 & 3) * 16;
-    *reinterpret_cast<f16v8*>(o) = h;
-    *reinterpret_cast<f16v8*>(o + 64) = l;
-  }
-}
-
-}  // namespace
-
-// w [Cout][3][3][Cin] fp32 -> Winograd-domain HL32 weight [Cout][R+2][Cin/32][3][128 B] of scale[0] * (G w) (R = 2 or 4)
-MRN_EXPORT int mrn_pack_weight_wino_hl32(const float* w_ohwi, void* out, int Cout, int Cin, int R, const float* scale, void* stream) {
-  MRN_CHECK_ARG(w_ohwi && out && Cin % 32 == 0 && (R == 2 || R == 4), "mrn_pack_weight_wino_hl32: bad operands (Cin=%d R=%d)", Cin, R);
-  const long n8 = (long)Cout * (R + 2) * 3 * (Cin / 8);
-  if (n8 == 0) return MRN_OK;
-  long grid = (n8 + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(pack_weight_wino_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w_ohwi, (unsigned char*)out,
-                     Cout, Cin, R, scale, 0);
-  MRN_LAUNCH_CHECK("pack_weight_wino_hl32");
-  return MRN_OK;
-}
-
-// the same transform as PLAIN fp16 for the reduced-precision mode: w [Cout][3][3][Cin] fp32 -> [Cout][6][Cin/64][3][128 B] of
-// scale[0] * (G w), F(4,3), 64 channels per line (mrn_conv2d_x3_wino_d16's weight operand); Cin % 64 == 0
-MRN_EXPORT int mrn_pack_weight_wino_d16(const float* w_ohwi, void* out, int Cout, int Cin, const float* scale, int bf16, void* stream) {
-  MRN_CHECK_ARG(w_ohwi && out && Cin % 64 == 0, "mrn_pack_weight_wino_d16: bad operands (Cin=%d)", Cin);
-  const long n8 = (long)Cout * 6 * 3 * (Cin / 8);
-  if (n8 == 0) return MRN_OK;
-  long grid = (n8 + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(pack_weight_wino_hl32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w_ohwi, (unsigned char*)out,
-                     Cout, Cin, 4, scale, bf16 ? 2 : 1);
-  MRN_LAUNCH_CHECK("pack_weight_wino_d16");
-  return MRN_OK;
+  return launch_x3_tile(tile_m, tile_n, false, products, false, p, (hipStream_t)stream);
 }
 
 // row blocks of the BatchNorm partial statistics of one group: the x3 kernel writes one per 128 GEMM rows; the row-block kernel

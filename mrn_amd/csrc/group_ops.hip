@@ -6,12 +6,9 @@
 // Reference op sites: BatchNorm2d / ReLU / residual add / MaxPool2d of modules/feature_extraction.py:171-199,222-294
 // and modules/transformation.py:69-81, evaluated for every expert of modules/model.py:399-401.
 // All kernels are HBM-bound: each activation byte is read once, 32 B per lane, channels innermost.
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {
-
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
 
 struct F8 {
   f32x4 a, b;
@@ -29,18 +26,9 @@ __device__ __forceinline__ void store8(float* p, const F8& v) {
 }
 // 8 consecutive channels c8*8 .. +7 of row `row` -> their slots in the HL32 image
 __device__ __forceinline__ void store_hl(unsigned char* out, long row, int C, int c8, const F8& v) {
-  f16v8 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    _Float16 hh, ll;
-    split_f16_sat(v.a[e], hh, ll);       // (saturating: an activation beyond the fp16 range -- 6.5e4 plain, 6.5e3 under B^T of F(4,3) --
-    h[e] = hh; l[e] = ll;                //  stays finite instead of hi = inf, lo = -inf -> NaN products)
-    split_f16_sat(v.b[e], hh, ll);
-    h[4 + e] = hh; l[4 + e] = ll;
-  }
-  unsigned char* o = out + (row * (C >> 5) + (c8 >> 2)) * 128 + (c8 & 3) * 16;
-  *reinterpret_cast<f16v8*>(o) = h;
-  *reinterpret_cast<f16v8*>(o + 64) = l;
+  // (saturating: an activation beyond the fp16 range -- 6.5e4 plain, 6.5e3 under B^T of F(4,3) -- stays finite instead of
+  //  hi = inf, lo = -inf -> NaN products)
+  split_hl8<true>(v.a, v.b).store(out + (row * (C >> 5) + (c8 >> 2)) * 128 + (c8 & 3) * 16);
 }
 
 // the reduced-precision operand line: 64 channels of plain fp16 per 128 bytes (conv_wino.hip, DENSE), saturating like store_hl
@@ -572,18 +560,7 @@ __global__ __launch_bounds__(256) void add_layernorm_grouped_kernel(const float*
     const int c4 = sub + i * LPR;
     if (c4 < C4) {
       if (y_f32) reinterpret_cast<f32x4*>(y_f32 + row * C)[c4] = v[i];
-      if (y_hl) {
-        f16v4 h, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          _Float16 hh, ll;
-          split_f16(v[i][j], hh, ll);
-          h[j] = hh; l[j] = ll;
-        }
-        unsigned char* o = y_hl + (row * (C >> 5) + (c4 >> 3)) * 128 + (c4 & 7) * 8;
-        *reinterpret_cast<f16v4*>(o) = h;
-        *reinterpret_cast<f16v4*>(o + 64) = l;
-      }
+      if (y_hl) split_hl4(v[i]).store(y_hl + (row * (C >> 5) + (c4 >> 3)) * 128 + (c4 & 7) * 8);
     }
   }
 }

@@ -2,6 +2,7 @@
 //
 // Reference: modules/sequence_modeling.py:7-21 (nn.LSTM bidirectional, gate order i,f,g,o).  The workgroup geometry and the MFMA
 // helpers are recurrent.hpp's, shared with the attention decoders (attn_decode.hip).
+#include "hl32.hpp"
 #include "recurrent.hpp"
 #include <stdlib.h>
 
@@ -195,16 +196,16 @@ __global__ __launch_bounds__(LstmGeom<HS>::NTH) void lstm_layer_x3_kernel(const 
   constexpr int Q = HID / 32;
   // every global access is a buffer instruction -- resource + scalar offset + one 32-bit lane offset: no address lives in the vector file
   // (as 64-bit pointers per gate / row the compiler hoisted them out of the step loop and, at RB = 2, spilled them)
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 4 * HID * HID * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = make_rsrc(W, 4 * HID * HID * 4);
   const int wwave = __builtin_amdgcn_readfirstlane(wave) * (4 * Q * 64 * 32);
   const int wlane = lane * 32;
   constexpr int WPASS = NW * (4 * Q * 64 * 32);        // bytes between the unit tiles of two passes of a wave
   constexpr int UPASS = 16 * NW * 4;                  // bytes between their hidden units in a row of floats
   const unsigned xbytes = (unsigned)B * (unsigned)(T * ndir * 4 * HID) * 4u;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xproj, 0, xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, xbytes / 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gates_out, 0, gates_out ? xbytes : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)c_out, 0, gates_out ? xbytes / 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(xproj, xbytes);
+  const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, xbytes / 4);
+  const __amdgpu_buffer_rsrc_t rg = make_rsrc(gates_out, gates_out ? xbytes : 0);
+  const __amdgpu_buffer_rsrc_t rc = make_rsrc(c_out, gates_out ? xbytes / 4 : 0);
   const int n = lane & 15, kg = lane >> 4;
 
   for (int step = 0; step < T; ++step) {

@@ -8,7 +8,7 @@
 // lane-local (the i,f,g,o pre-activations of a unit land in the same lane and register index).
 // The k index is permuted (lane group g takes k = 16q+4g+r) so every operand read is one 16-byte access.
 #pragma once
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {   // (internal to each including unit, as the kernels are)
 
@@ -136,8 +136,6 @@ __device__ __forceinline__ void lstm_pointwise0(const f32x4 (&acc)[4], const flo
 // Up to MAX_GROUPS independent layers (the frozen experts of the router phase) share one launch: grid.x = groups * tiles.
 constexpr int MAX_GROUPS = 8;
 
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int LDH = HID + 8;   // fp16 LDS row (halves): 528 B, 16 rows hit 16 distinct 16-byte bank groups
 
 // acc[g] += A(16 x K, fp16 hi / lo planes in LDS) . W_g^T with W FRAGMENT-MAJOR fp16:

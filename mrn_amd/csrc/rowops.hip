@@ -4,7 +4,7 @@
 // rearrange() views of the reference (modules/dm_router.py:12,58-65) never need a copy.
 //
 // Reference op sites: nn.LayerNorm modules/dm_router.py:8,23,40 (eps 1e-5); nn.GELU :42; u*v :17, x*v :33.
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {
 
@@ -77,19 +77,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
       reinterpret_cast<f32x4*>(y + row * ldy)[c4] = o;
-      if constexpr (HL) {
-        typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-        f16v4 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          _Float16 hh, ll;
-          split_f16_sat(o[j] * sc, hh, ll);
-          hi[j] = hh; lo[j] = ll;
-        }
-        unsigned char* line = y_hl + (row * (C >> 5) + (c4 >> 3)) * 128 + (c4 & 7) * 8;
-        *reinterpret_cast<f16v4*>(line) = hi;
-        *reinterpret_cast<f16v4*>(line + 64) = lo;
-      }
+      if constexpr (HL) split_hl4<true>([&](int j) { return o[j] * sc; }).store(y_hl + (row * (C >> 5) + (c4 >> 3)) * 128 + (c4 & 7) * 8);
     }
   }
 }
@@ -287,7 +275,6 @@ __global__ __launch_bounds__(256) void ew_rows_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void ew_operand_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ d,
                                                          long rows_per_d, float* __restrict__ y, unsigned char* __restrict__ y_hl,
                                                          const float* __restrict__ scale, unsigned* __restrict__ amax_ws, long n4, int C4, int op) {
-  typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
   const float sc = (y_hl && scale) ? scale[0] : 1.f;
   float mx = 0.f;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -309,18 +296,10 @@ __global__ __launch_bounds__(256) void ew_operand_kernel(const float* __restrict
     }
     if (y) reinterpret_cast<f32x4*>(y)[i] = o;
     if (y_hl) {
-      f16v4 hi, lo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        _Float16 hh, ll;
-        split_f16_sat(o[j] * sc, hh, ll);
-        hi[j] = hh; lo[j] = ll;
-      }
+      const HalfLine<f16v4> hl = split_hl4<true>([&](int j) { return o[j] * sc; });
       const long r = i / C4;
       const int c4 = (int)(i - r * C4);
-      unsigned char* line = y_hl + (r * (C4 >> 3) + (c4 >> 3)) * 128 + (c4 & 7) * 8;
-      *reinterpret_cast<f16v4*>(line) = hi;
-      *reinterpret_cast<f16v4*>(line + 64) = lo;
+      hl.store(y_hl + (r * (C4 >> 3) + (c4 >> 3)) * 128 + (c4 & 7) * 8);
     }
     mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
   }

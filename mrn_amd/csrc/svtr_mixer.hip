@@ -30,14 +30,9 @@
 // (64 KiB) sits in LDS at a time.
 // C = 64 with up to 512 tokens (SVTR stage 1: 8 x 25 at 32 x 100 crops, 8 x 64 at 32 x 256) and C = 128 with up to 256 tokens (stage 2);
 // C = 256 (stage 3: the token fragments and the accumulators alone are 256 registers) uses the unfused chain.
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {
-
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16v4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr float LOG2E_F = 1.4426950408889634f;
 constexpr float PBIAS = 12.f;       // probabilities carry 2^12 (cancelled by 1 / l): small ones stay out of fp16's subnormal range
@@ -69,10 +64,6 @@ struct MixerParams {
                                   // columns) touches 3 tiles of 8 (stage 2) / 5 of 16 (stage 1) instead of every row's half-rows
   float scale, eps1, eps2;
 };
-
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16v8*>(&a), *reinterpret_cast<const f16v8*>(&b), c, 0, 0, 0);
-}
 
 #ifdef MRN_XPROBE_TIMING
 // timing probe (never in the product build; bash tools/build_probe.sh MRN_XPROBE_TIMING svtr_mixer.hip; tools/probe/xtiming.py): shader-clock
@@ -155,8 +146,8 @@ __global__ __launch_bounds__(NT * IMG * 64) void svtr_mixer_kernel(const MixerPa
   // ---- weight slabs, STEPS per head in the order Wk, Wv (own key chunk), Wq, [Wk, Wv (other chunk),] Wproj.  DMA instruction d moves 8
   // lines of 128 B: lane -> line 8 d + lane / 8, chunk lane & 7, source chunk XOR-swizzled with (line >> 1) & 7 (conflict-free
   // ds_read_b128 fragments)
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(p.wqkv + (long)g * 3 * C * CB * 128), 0, 3 * C * CB * 128, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(p.wproj + (long)g * C * CB * 128), 0, C * CB * 128, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(p.wqkv + (long)g * 3 * C * CB * 128, 3 * C * CB * 128);
+  const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.wproj + (long)g * C * CB * 128, C * CB * 128);
   auto issue = [&](int step, unsigned char* buf) {
     const int h = step / STEPS, sh = step % STEPS;
     const int ty = (!ATTN && sh == STEPS - 1) ? 3 : sh == 2 ? 2 : sh < 2 ? sh : sh - 3;      // 0: Wk, 1: Wv, 2: Wq, 3: Wproj

@@ -20,13 +20,9 @@
 // C = 64 and 128 (SVTR stages 1 and 2): eight waves of 32 tokens, two per SIMD.  C = 256 (stage 3): the token fragments (128 registers)
 // and the output accumulators (128) need the 512-register form -- four waves, one per SIMD, 128 tokens per workgroup, 2 x 64 KiB of
 // slab ring (the round-4 pricing: fc1 + fc2 as two GEMMs 0.89 ms per block against ~0.5 here).
-#include "common.hpp"
+#include "hl32.hpp"
 
 namespace {
-
-typedef _Float16 f16v8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct MlpParams {
   const unsigned char* x_hl;      // [rows][C/32][128 B] LayerNorm output (HL32)
@@ -50,10 +46,6 @@ struct MlpParams {
   long rows_per_drop;
   float eps;
 };
-
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16v8*>(&a), *reinterpret_cast<const f16v8*>(&b), c, 0, 0, 0);
-}
 
 // TAIL (C = 256 only): the second half of a stage-3 mixing block in one launch -- modules/svtr.py:196-204 from the attention context on:
 //   x <- x + drop * (ctx Wproj^T + bproj);  y = LayerNorm2(x);  branch = fc2(GELU(fc1(y)))
@@ -137,8 +129,8 @@ __global__ __launch_bounds__(C == 256 ? 256 : MRN_MLP_WAVES * 64, C == 256 ? 1 :
 
   // ---- weight slabs through LDS: DMA instruction d (0 .. N1+N2-1) moves 8 rows x 128 B; lane -> row 8 d' + lane / 8, chunk lane & 7,
   // source chunk XOR-swizzled with (row >> 1) & 7 as in conv_x3.hip (conflict-free ds_read_b128 fragment reads)
-  const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w1 + (long)g * HID * CB * 128), 0, HID * CB * 128, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w2 + (long)g * C * NH * 128), 0, C * NH * 128, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r1 = make_rsrc(p.w1 + (long)g * HID * CB * 128, HID * CB * 128);
+  const __amdgpu_buffer_rsrc_t r2 = make_rsrc(p.w2 + (long)g * C * NH * 128, C * NH * 128);
   // W1 rows of hidden block h1 -> the W1 region of ring buffer h1 & 1, W2' columns of hidden block h2 -> the W2 region of buffer h2 & 1
   // (either may be -1: nothing); the plain schedule moves both parts of one block, the skewed one (C = 256) W1 one block ahead of W2'
   auto issue2 = [&](int h1, int h2) {
@@ -150,13 +142,13 @@ __global__ __launch_bounds__(C == 256 ? 256 : MRN_MLP_WAVES * 64, C == 256 ? 1 :
         const int cb = d / 4, r = (d % 4) * 8 + (lane >> 3);
         const int coff = ((lane & 7) ^ ((r >> 1) & 7)) << 4;
         const int voff = ((h1 * 32 + r) * CB + cb) * 128 + coff;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (lds_ptr_t)(lds + (h1 & 1) * SLAB + d * 1024), 16, voff, 0, 0, 0);
+        dma16(r1, lds + (h1 & 1) * SLAB + d * 1024, voff, 0);
       } else {                                      // W2': LDS [C rows]; source row r, line h2
         if (h2 < 0) continue;
         const int d2 = d - N1, r = d2 * 8 + (lane >> 3);
         const int coff = ((lane & 7) ^ ((r >> 1) & 7)) << 4;
         const int voff = (r * NH + h2) * 128 + coff;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r2, (lds_ptr_t)(lds + (h2 & 1) * SLAB + W1_SLAB + d2 * 1024), 16, voff, 0, 0, 0);
+        dma16(r2, lds + (h2 & 1) * SLAB + W1_SLAB + d2 * 1024, voff, 0);
       }
     }
   };
@@ -179,14 +171,14 @@ __global__ __launch_bounds__(C == 256 ? 256 : MRN_MLP_WAVES * 64, C == 256 ? 1 :
   if (TAIL) {
     // ---- proj: eight slabs of 32 output channels x C input channels through the W1 half of the ring (slab o -> buffer o & 1; the
     // Mlp's first slab follows into buffer 0), then residual + LayerNorm2 in registers
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(p.wp + (long)g * C * CB * 128), 0, C * CB * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.wp + (long)g * C * CB * 128, C * CB * 128);
     auto issue_proj = [&](int o, unsigned char* buf) {
 #pragma unroll
       for (int i = 0; i < N1 / NW; ++i) {
         const int d = i * NW + wave;
         const int cb = d / 4, r = (d % 4) * 8 + (lane >> 3);
         const int coff = ((lane & 7) ^ ((r >> 1) & 7)) << 4;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (lds_ptr_t)(buf + d * 1024), 16, ((o * 32 + r) * CB + cb) * 128 + coff, 0, 0, 0);
+        dma16(rp, buf + d * 1024, ((o * 32 + r) * CB + cb) * 128 + coff, 0);
       }
     };
     static_assert(N1 % NW == 0, "proj slab DMA instructions divide over the waves");

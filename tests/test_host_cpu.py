@@ -503,3 +503,37 @@ def test_recurrent_helpers_are_defined_once():
     for unit in ("lstm.hip", "attn_decode.hip", "attn_bwd.hip", "backward.hip"):
         assert '#include "recurrent.hpp"' in open(os.path.join(csrc, unit)).read(), unit
     assert not os.path.exists(os.path.join(csrc, "rnn.hip"))
+
+
+def test_hl32_format_is_defined_once():
+    """the HL32 operand format has one home: the MFMA wrapper, the LDS DMA, the buffer descriptor (and its flag word), the fp16 splits
+    and the half-line split / store helpers are each defined exactly once in csrc/, in hl32.hpp, which every unit that uses one of them
+    includes; conv_x3.hip keeps the convolution kernel only -- the operand producers live in hl32_pack.hip and wgrad_operands.hip"""
+    import re
+    csrc = os.path.join(ROOT, "mrn_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".cpp", ".h"))}
+    helpers = (("mma", "f32x16"), ("dma16", "void"), ("make_rsrc", "__amdgpu_buffer_rsrc_t"), ("split_f16", "void"), ("split_f16_sat", "void"),
+               ("split_hl4", r"HalfLine<f16v4>"), ("split_hl8", r"HalfLine<f16v8>"), ("store", "void"))
+    for helper, ret in helpers:
+        defs = sorted({f for f, s in text.items() if re.search(r"\b%s\s+%s\(" % (ret, helper), s)})
+        assert defs == ["hl32.hpp"], (helper, defs)
+    assert [f for f, s in text.items() if "0x00020000" in s] == ["hl32.hpp"]
+    for alias in ("f16v8", "f16v4", "u32x4", "lds_ptr_t"):
+        assert [f for f, s in text.items() if re.search(r"typedef [^;]*\b%s\b[^;]*;" % alias, s)] == ["hl32.hpp"], alias
+    uses = re.compile(r"\b(mma|dma16|make_rsrc|split_f16|split_f16_sat|split_hl4|split_hl8)\s*(<\w+>)?\(")
+    users = [f for f, s in text.items() if f.endswith(".hip") and uses.search(s)]
+    assert {"conv_x3.hip", "conv_wino.hip", "conv_patch.hip", "svtr_mlp.hip", "svtr_mixer.hip", "group_ops.hip", "rowops.hip", "attention.hip",
+            "lstm.hip", "attn_decode.hip", "hl32_pack.hip", "wgrad_operands.hip"} <= set(users)
+    for unit in users:
+        assert '#include "hl32.hpp"' in text[unit], unit
+    assert '#include "hl32.hpp"' in text["recurrent.hpp"] and "split_f16" not in text["common.hpp"]
+    moved = {"hl32_pack.hip": ("split_hl32_kernel", "pack_weight_hl32_kernel", "multi_pack_amax_kernel", "multi_pack_kernel", "MultiPackDesc",
+                               "pack_weight_wino_hl32_kernel"),
+             "wgrad_operands.hip": ("split_hl32_t_kernel", "split_hl32_t_colsum_kernel", "im2col_t_hl32_kernel", "Im2colT", "transpose_oy_hl32_kernel",
+                                    "transpose_oy3_hl32_kernel", "transpose_oy_wino_hl32_kernel", "wino_wgrad_finish_kernel", "mrn_colsum_f32")}
+    for unit, names in moved.items():
+        for name in names:
+            assert name in text[unit] and name not in text["conv_x3.hip"], (unit, name)
+    assert not re.search(r"\bsplit_h\(", "".join(text.values()))
+    lines = {f: s.count("\n") for f, s in text.items()}
+    assert max(lines["hl32_pack.hip"], lines["wgrad_operands.hip"], lines["hl32.hpp"]) < lines["conv_x3.hip"]

@@ -408,7 +408,8 @@ def test_tps_backward_fiducial_gradient(ops):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# grouped kernels of the lock-step expert path (conv_x3.hip, group_ops.hip, grouped recurrences)
+# grouped kernels of the lock-step expert path (conv_x3.hip and its operand producers hl32_pack.hip / wgrad_operands.hip, group_ops.hip,
+# grouped recurrences)
 # ---------------------------------------------------------------------------------------------------------
 X3_CONVS = [
     # G, B, H, W, Cin, Cout, k, s, p, shared input
@@ -1048,7 +1049,7 @@ def test_wgrad_without_im2col_matches_exact_fp32(B, H, W, Cin, Cout):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Winograd F(R,3) form of the frozen experts' 3x3 convolutions (conv_x3.hip WINO, group_ops.hip producer)
+# Winograd F(R,3) form of the frozen experts' 3x3 convolutions (conv_x3.hip WINO, hl32_pack.hip weight transform, group_ops.hip producer)
 # ---------------------------------------------------------------------------------------------------------
 WINO_CONVS = [
     # G, B, H, W, Cin, Cout, shortcut ("none" | "f32" | "hl32"), relu
