@@ -31,10 +31,10 @@ struct FaninArgs {
 template <int N>
 __global__ __launch_bounds__(256) void fanin_fwd_kernel(const FaninArgs<N> a, const float* __restrict__ w, float* __restrict__ out,
                                                         long ldo, int T, int C) {
-  // grid: (ceil(C4/256), B*T)
-  const long row = blockIdx.y;
+  // grid: (B*T, ceil(C4/256)): the rows ride on grid.x, which is not held to 65535 as grid.y is (256 samples x 256 steps = 65536 rows)
+  const long row = blockIdx.x;
   const int b = (int)(row / T);
-  const int c4 = blockIdx.x * 256 + threadIdx.x;
+  const int c4 = blockIdx.y * 256 + threadIdx.x;
   const int c = c4 * 4;
   if (c >= C) return;
   float wi[N];
@@ -110,9 +110,9 @@ __global__ void fanin_bwd_reduce_kernel(const float* __restrict__ partial, float
 template <int N>
 __global__ __launch_bounds__(256) void select_expert_kernel(const FaninArgs<N> a, const int64_t* __restrict__ index,
                                                             float* __restrict__ out, long ldo, int T, int C) {
-  const long row = blockIdx.y;
+  const long row = blockIdx.x;          // grid: (B*T, ceil(C/256)), rows on grid.x as in fanin_fwd_kernel
   const int b = (int)(row / T);
-  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y * 256 + threadIdx.x;
   if (c >= C) return;
   const int i = (int)index[b];
   float v = 1.f;
@@ -129,21 +129,33 @@ __global__ void gate_tail_fwd_kernel(const float* __restrict__ r, const float* _
                                      int64_t* __restrict__ argmax_out, int B, int P, int I) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float s[N];
+  // One thread adds the P products of a score one after the other: plain fp32 let the P roundings of the running sum through (5e-7 of a
+  // score at P = 129, where a pairwise sum stays near 1e-8).  The sum is compensated instead: lo[i] collects what each product (fmaf
+  // residual) and each addition (two-sum) rounds away, so s comes out within a rounding or two of the exact sum.  The __f*_rn forms
+  // keep the compiler from contracting the steps into other fmas.
+  float s[N], lo[N];
 #pragma unroll
-  for (int i = 0; i < N; ++i) s[i] = 0.f;
-  for (int p = 0; p < P; ++p) {
-    const float wp = Wr[p];
+  for (int i = 0; i < N; ++i) s[i] = lo[i] = 0.f;
+  for (int p = 0; p <= P; ++p) {                     // (term P: 1 * br)
+    const float wp = p < P ? Wr[p] : br[0];
 #pragma unroll
     for (int i = 0; i < N; ++i)
-      if (i < I) s[i] = fmaf(wp, r[((long)b * P + p) * I + i], s[i]);
+      if (i < I) {
+        const float rv = p < P ? r[((long)b * P + p) * I + i] : 1.f;
+        const float prod = __fmul_rn(wp, rv);
+        const float t = __fadd_rn(s[i], prod);
+        const float bb = __fsub_rn(t, s[i]);
+        const float err = __fadd_rn(__fsub_rn(s[i], __fsub_rn(t, bb)), __fsub_rn(prod, bb));
+        lo[i] = __fadd_rn(lo[i], __fadd_rn(err, fmaf(wp, rv, -prod)));
+        s[i] = t;
+      }
   }
   float m = -INFINITY;
   int am = 0;
 #pragma unroll
   for (int i = 0; i < N; ++i)
     if (i < I) {
-      s[i] += br[0];
+      s[i] = __fadd_rn(s[i], lo[i]);
       if (s[i] > m) { m = s[i]; am = i; }
       if (s_out) s_out[(long)b * I + i] = s[i];
     }
@@ -227,7 +239,7 @@ static int fanin_fwd(const void* const* logits, const int64_t* lds, const int* c
   MRN_CHECK_ARG(w && out && ldo >= C && ldo % 4 == 0 && ((uintptr_t)out % 16 == 0),
                 "%s: output must be 16-byte aligned with a row stride that is a multiple of 4", who);
   if (B * T == 0) return MRN_OK;
-  hipLaunchKernelGGL(fanin_fwd_kernel<N>, dim3(ceil_div(ceil_div(C, 4), 256), B * T), dim3(256), 0, (hipStream_t)stream, a, w, out,
+  hipLaunchKernelGGL(fanin_fwd_kernel<N>, dim3(B * T, ceil_div(ceil_div(C, 4), 256)), dim3(256), 0, (hipStream_t)stream, a, w, out,
                      (long)ldo, T, C);
   MRN_LAUNCH_CHECK("fanin_fwd");
   return MRN_OK;
@@ -256,7 +268,7 @@ static int select_expert(const void* const* logits, const int64_t* lds, const in
   if (rc) return rc;
   MRN_CHECK_ARG(index && out, "%s: null operand", who);
   if (B * T == 0) return MRN_OK;
-  hipLaunchKernelGGL(select_expert_kernel<N>, dim3(ceil_div(C, 256), B * T), dim3(256), 0, (hipStream_t)stream, a, index, out,
+  hipLaunchKernelGGL(select_expert_kernel<N>, dim3(B * T, ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, a, index, out,
                      (long)ldo, T, C);
   MRN_LAUNCH_CHECK("select_expert");
   return MRN_OK;

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ x
   const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   if (row >= rows) return;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = 0;                         // a row of nothing but -inf: no element beats `best`, and torch.max answers index 0
   for (int c = lane; c < C; c += 64) {
     const float v = x[row * ld + c];
     if (v > best || (v != v && best == best)) { best = v; bi = c; }  // NaN propagates like torch
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256) void argmax_prob_kernel(const float* __restric
   const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   if (row >= rows) return;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = 0;                         // (all -inf: index 0, as argmax_kernel)
   for (int c = lane; c < C; c += 64) {
     const float v = x[row * ld + c];
     if (v > best || (v != v && best == best)) { best = v; bi = c; }

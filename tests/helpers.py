@@ -437,3 +437,150 @@ def ewc_reference(grads, fisher_max, p, mean, coef, grad0, dtype=torch.float64):
     penalty = (fisher * d * d).sum() / 2
     grad = grad0.detach().to(dtype) + coef * fisher * d
     return dict(acc=acc, fisher=fisher, penalty=penalty, grad=grad)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# written-out yardsticks of the DM-Router's kernels (tests/test_router_kernels_*.py): rowops.hip, router.hip and DMRouterFn.  As above:
+# operands cast to `dtype` first, float64 the reference, float32 the baseline.
+# ---------------------------------------------------------------------------------------------------------
+def layernorm_reference(x, gamma, beta, eps=1e-5, dy=None, dtype=torch.float64):
+    """LayerNorm over the last dim of x [rows, C], two-pass: mean = sum(x) / C, var = sum((x - mean)^2) / C, rstd = 1 / sqrt(var + eps),
+    xhat = (x - mean) * rstd, y = xhat * gamma + beta; with dy: dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = dy * gamma,
+    dgamma = sum_rows(dy * xhat), dbeta = sum_rows(dy) -> dict y, mean, rstd (, dx, dgamma, dbeta)"""
+    x, gamma, beta = x.detach().to(dtype), gamma.detach().to(dtype), beta.detach().to(dtype)
+    C = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / C
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).sum(-1, keepdim=True) / C + eps)
+    xhat = d * rstd
+    out = dict(y=xhat * gamma + beta, mean=mean.squeeze(-1), rstd=rstd.squeeze(-1))
+    if dy is not None:
+        dy = dy.detach().to(dtype)
+        g = dy * gamma
+        out["dx"] = rstd * (g - g.sum(-1, keepdim=True) / C - xhat * ((g * xhat).sum(-1, keepdim=True) / C))
+        out["dgamma"] = (dy * xhat).reshape(-1, C).sum(0)
+        out["dbeta"] = dy.reshape(-1, C).sum(0)
+    return out
+
+
+def colnorm_reference(x, gamma, beta, eps=1e-5, dy=None, dtype=torch.float64):
+    """the same normalisation over the MIDDLE axis of x [B, P, W] (gamma, beta [P]): ChannelDomainGating's LayerNorm(patch) on the
+    'b (d c) p' rearrangement, without the transpose -> dict y, mean [B, W], rstd [B, W] (, dx, dgamma [P], dbeta [P])"""
+    r = layernorm_reference(x.detach().permute(0, 2, 1), gamma, beta, eps, None if dy is None else dy.detach().permute(0, 2, 1), dtype)
+    return {k: (v.permute(0, 2, 1) if k in ("y", "dx") else v) for k, v in r.items()}
+
+
+def gelu_reference(x, dtype=torch.float64):
+    """nn.GELU(), the erf form: x * Phi(x), Phi(x) = (1 + erf(x / sqrt 2)) / 2"""
+    x = x.detach().to(dtype)
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def gelu_grad_reference(x, dtype=torch.float64):
+    """d gelu / dx = Phi(x) + x * phi(x), phi(x) = exp(-x^2 / 2) / sqrt(2 pi)"""
+    x = x.detach().to(dtype)
+    return 0.5 * (1.0 + torch.erf(x * 0.7071067811865476)) + x * (0.3989422804014327 * torch.exp(-0.5 * x * x))
+
+
+def gate_tail_reference(r, w_route, b_route, beta, dw=None, dtype=torch.float64, w=None):
+    """route Linear(P -> 1) over the patch axis of r [B, P, I], squeeze, softmax(beta * s): s[b][i] = sum_p Wr[p] r[b][p][i] + br,
+    w = softmax(beta * s); with dw [B, I]: ds = beta * w * (dw - sum_i(dw * w)), dr[b][p][i] = Wr[p] * ds[b][i],
+    dWr[p] = sum_{b,i} ds[b][i] * r[b][p][i], dbr = sum(ds) -> dict s, w, argmax (first maximum of s) (, ds, dr, dWr, dbr).
+    w [B, I]: the backward formulas on THESE weights instead of the softmax (ops.gate_tail_bwd takes w as an operand; with the
+    softmax's own w, sum(ds) is zero and dbr all rounding)"""
+    r, Wr, br = r.detach().to(dtype), w_route.detach().to(dtype).reshape(-1), b_route.detach().to(dtype).reshape(-1)
+    s = (r * Wr.view(1, -1, 1)).sum(1) + br
+    m = s.max(1, keepdim=True).values
+    e = torch.exp(beta * (s - m))
+    soft = e / e.sum(1, keepdim=True)
+    out = dict(s=s, w=soft, argmax=(s == m).to(torch.int64).argmax(1))
+    w = soft if w is None else w.detach().to(dtype)
+    if dw is not None:
+        dw = dw.detach().to(dtype)
+        ds = beta * w * (dw - (dw * w).sum(1, keepdim=True))
+        out.update(ds=ds, dr=Wr.view(1, -1, 1) * ds.unsqueeze(1), dWr=(ds.unsqueeze(1) * r).sum((0, 2)), dbr=ds.sum().reshape(1))
+    return out
+
+
+def fanin_reference(logits, w, dout=None, dtype=torch.float64):
+    """MRN fan-in: logits a list of I tensors [B, T, C_i] (C_i <= C = the last one's), each padded to C classes with ONES;
+    out[b][t][c] = sum_i w[b][i] * Lpad_i[b][t][c]; with dout: dw[b][i] = sum_{t,c} dout[b][t][c] * Lpad_i[b][t][c] -> (out, dw or None)"""
+    C = logits[-1].shape[-1]
+    w = w.detach().to(dtype)
+    pad = [torch.cat([l.detach().to(dtype), torch.ones(*l.shape[:2], C - l.shape[-1], dtype=dtype)], -1) for l in logits]
+    out = sum(w[:, i].view(-1, 1, 1) * p for i, p in enumerate(pad))
+    dw = None
+    if dout is not None:
+        dout = dout.detach().to(dtype)
+        dw = torch.stack([(dout * p).sum((1, 2)) for p in pad], 1)
+    return out, dw
+
+
+DM_ROUTER_PARAMS = ("n_w", "n_b", "w1", "b1", "sn_w", "sn_b", "wsp", "bsp", "w2", "b2", "cn_w", "cn_b", "wch", "bch", "w3", "b3")
+DM_ROUTER_GRADS = ("dx",) + tuple("d" + k for k in DM_ROUTER_PARAMS)
+
+
+def dm_router_reference(x, params, dout, eps=1e-5, dtype=torch.float64, stages=None):
+    """DM_Router.forward and its backward, stage by stage, on the router-internal layout x [B, P, I, C] (functional.DMRouterFn's);
+    params: the 16 tensors in DMRouterFn's order (DM_ROUTER_PARAMS); dout like x.  The spatial gate mixes the tokens in the reference's
+    '(d p)' order (token n = d * P + p), the channel gate normalises every (b, d, c) column over p and mixes the (d c) axis:
+        xn = LN(x; n)           hpre = xn W1^T + b1        h = gelu(hpre) = [u | v]      vn = LN(v; sn)
+        vp[b][n] = sum_m Wsp[n][m] vn[b][m] + bsp[n]       g = u * vp                    y = g W2^T + b2 + x
+        zn = LN_p(y; cn)        zp = zn Wch^T + bch over (d c)                           z2 = y * zp      out = z2 W3^T + b3 + x
+    -> (out [B, P, I, C], dict of the 17 gradients named in DM_ROUTER_GRADS); stages: a dict that receives the intermediate tensors
+    (in the dtype of the evaluation)"""
+    B, P, I, C = x.shape
+    N = P * I
+    p = {k: v.detach().to(dtype) for k, v in zip(DM_ROUTER_PARAMS, params)}
+    X = x.detach().to(dtype).reshape(-1, C)
+    dout = dout.detach().to(dtype).reshape(-1, C)
+
+    def to_ref(t):                                  # rows in L2 order (b, p, d) -> [B, N, width] with n = d * P + p
+        return t.reshape(B, P, I, -1).permute(0, 2, 1, 3).reshape(B, N, -1)
+
+    def to_l2(t):
+        return t.reshape(B, I, P, -1).permute(0, 2, 1, 3).reshape(B * N, -1)
+
+    ln1 = layernorm_reference(X, p["n_w"], p["n_b"], eps, dtype=dtype)
+    xn = ln1["y"]
+    hpre = xn @ p["w1"].t() + p["b1"]
+    h = gelu_reference(hpre, dtype)
+    u, v = h[:, :C], h[:, C:]
+    ln2 = layernorm_reference(v, p["sn_w"], p["sn_b"], eps, dtype=dtype)
+    vn_r = to_ref(ln2["y"])                                                         # [B, N, C]
+    vp_r = torch.einsum("nm,bmc->bnc", p["wsp"], vn_r) + p["bsp"].view(1, N, 1)
+    vp = to_l2(vp_r)
+    g = u * vp
+    y = g @ p["w2"].t() + p["b2"] + X
+    y3 = y.reshape(B, P, I * C)
+    cn = colnorm_reference(y3, p["cn_w"], p["cn_b"], eps, dtype=dtype)
+    zn = cn["y"].reshape(B * P, I * C)
+    zp = (zn @ p["wch"].t() + p["bch"]).reshape(-1, C)
+    z2 = y * zp
+    out = z2 @ p["w3"].t() + p["b3"] + X
+
+    G = {}
+    G["dw3"], G["db3"] = dout.t() @ z2, dout.sum(0)
+    dz2 = dout @ p["w3"]
+    dy, dzp = dz2 * zp, (dz2 * y).reshape(B * P, I * C)
+    G["dwch"], G["dbch"] = dzp.t() @ zn, dzp.sum(0)
+    dzn = (dzp @ p["wch"]).reshape(B, P, I * C)
+    cb = colnorm_reference(y3, p["cn_w"], p["cn_b"], eps, dzn, dtype)
+    G["dcn_w"], G["dcn_b"] = cb["dgamma"], cb["dbeta"]
+    dy = dy + cb["dx"].reshape(-1, C)
+    G["dw2"], G["db2"] = dy.t() @ g, dy.sum(0)
+    dg = dy @ p["w2"]
+    du, dvp_r = dg * vp, to_ref(dg * u)
+    G["dwsp"] = torch.einsum("bnc,bmc->nm", dvp_r, vn_r)
+    G["dbsp"] = dvp_r.sum((0, 2))
+    dvn = to_l2(torch.einsum("nm,bnc->bmc", p["wsp"], dvp_r))
+    lb2 = layernorm_reference(v, p["sn_w"], p["sn_b"], eps, dvn, dtype)
+    G["dsn_w"], G["dsn_b"] = lb2["dgamma"], lb2["dbeta"]
+    dhpre = torch.cat([du, lb2["dx"]], 1) * gelu_grad_reference(hpre, dtype)
+    G["dw1"], G["db1"] = dhpre.t() @ xn, dhpre.sum(0)
+    lb1 = layernorm_reference(X, p["n_w"], p["n_b"], eps, dhpre @ p["w1"], dtype)
+    G["dn_w"], G["dn_b"] = lb1["dgamma"], lb1["dbeta"]
+    G["dx"] = (lb1["dx"] + dout + dy).reshape(B, P, I, C)
+    if stages is not None:
+        stages.update(xn=xn, hpre=hpre, vn_r=vn_r, vp=vp, g=g, y=y, zn=zn, zp=zp, z2=z2, dy=dy, dvp_r=dvp_r, dhpre=dhpre)
+    return out.reshape(B, P, I, C), G
