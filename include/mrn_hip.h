@@ -610,6 +610,8 @@ int mrn_svtr_attention_block_x3_f32(const float* x, const float* pending, const 
  * out_hl32 (the same tensor as the HL32 operand of the proj Linear: a head IS one 32-channel block).  Online softmax
  * on the exact-fp32 MFMA (x3 = 0) or, for frozen experts, with both products as split-fp16 x3 on the f16 MFMA (x3 = 1, 22-bit
  * products like the experts' other GEMMs): the [B][heads][N][N] score tensor of modules/svtr.py:140-149 never reaches HBM.
+ * x3 = 1 splits 64 k, 64 v and 64 scale log2e q with no range scale: |k|, |v| < 1023.75 and |q| < 1023.75 / (scale log2e), else
+ * NaN (inf - inf); operands below 2^-9 are held in steps of 2^-30 (error 2^-31) instead of to 22 bits (see the comment above the definition).
  * mask_bits: instead of `mask`, the visibility bits [N][ceil(N/32)] of a mask whose entries are 0 or -inf (SVTR's local window
  * mask, svtr.py:117-128): bit k of word t of row q set = key 32t + k is visible to query q. */
 int mrn_svtr_attention_f32(const float* qkv, const float* mask, const void* mask_bits, float* out, void* out_hl32, float* lse,

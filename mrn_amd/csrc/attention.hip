@@ -678,6 +678,13 @@ __global__ __launch_bounds__(AW * 64) void svtr_attention_dkv_kernel(const AttnB
 // out_hl32 (HL32 operand of the proj Linear).
 // Replaces the q k^T / softmax / attn v chain of modules/svtr.py:140-149 without materialising [B][heads][N][N].
 // x3 != 0: both products as split-fp16 x3 (frozen experts; lse must be NULL), else exact fp32 products.
+// Operand range of the x3 variant: 64 k, 64 v and 64 scale log2e q are split into fp16 pairs with NO range scale.
+//   upper end: |k|, |v| < 1023.75 and |q| < 1023.75 / (scale log2e) (4014 at scale 32^-1/2) -- from there on a hi half rounds to
+//     inf, the lo half to -inf, and the product is inf - inf = NaN;
+//   lower end: an operand below 2^-9 (64 |x| 2^-11 < 2^-14) has its lo half in fp16's subnormals: the pair then steps by 2^-30 (the subnormal
+//     quantum 2^-24 over 64; rounding error 2^-31) instead of holding 2^-22 relatively; the result degrades gradually with it (at max|qkv| = 1e-3 it is still within 8 x the error of
+//     the same formula on exactly split operands, tests/test_svtr_kernels_gpu.py: test_attention_x3_magnitude_sweep).
+//   LayerNorm-ed activations times trunc_normal(0.02)-scale weights put qkv at O(1); a caller outside [2^-9, 1023] uses x3 = 0.
 // mask_bits (optional, instead of mask): [N][ceil(N/32)] visibility bits of a 0 / -inf mask (bit k of word t of row q = key
 // 32t + k is visible to query q): one word per (query, key tile) instead of 16 floats per lane.
 // hl_scale (optional, fp32 kernel only): {s, 1/s} -- out_hl32 = split(s * out), the range-scaled operand of the proj Linear of an expert

@@ -2624,10 +2624,31 @@ def _mask_bits(mask):
     return got[1]
 
 
+def _mask_is_symmetric(mask):
+    return mask.dim() == 2 and mask.shape[0] == mask.shape[1] and bool(torch.equal(mask, mask.t()))
+
+
+def _require_symmetric(mask, entry):
+    """the forward and dq kernels read the additive mask as mask[key][query], the dk/dv kernel and the bit form as mask[query][key]: a
+    mask that is not symmetric would give a forward and a dq from one mask and a dk / dv from its transpose.  Refused here -- one
+    comparison (and one device->host check) per mask tensor and version, cached on the tensor as _mask_bits caches"""
+    got = getattr(mask, "_mrn_symmetric", None)
+    if got is None or got[0] != mask._version:
+        got = (mask._version, _mask_is_symmetric(mask))
+        mask._mrn_symmetric = got
+    if not got[1]:
+        raise ValueError(f"ops.{entry}: the additive mask must be a symmetric [N, N] tensor (mask[i][j] == mask[j][i]); "
+                         f"got shape {tuple(mask.shape)} with mask != mask^T")
+
+
 def svtr_attention(qkv, heads, scale, mask=None, want_f32=True, want_hl=False, want_lse=False, x3=False, hl_scale=None):
     """qkv [B,N,3C] (q | k | v, head dim 32), mask [N,N] additive symmetric or None -> [B,N,C]: fused q k^T / softmax / attn v.
     want_hl: also (or only) the HL32 operand of the proj Linear; returns the fp32 tensor, the HL32 bytes, or (fp32, hl).
-    want_lse: returns (fp32, lse [B,heads,N]) -- what svtr_attention_bwd needs.  x3: split-fp16 x3 products (frozen experts)"""
+    want_lse: returns (fp32, lse [B,heads,N]) -- what svtr_attention_bwd needs.  x3: split-fp16 x3 products (frozen experts), for
+    operands in the range written above mrn_svtr_attention_f32 (csrc/attention.hip).  A mask that is not symmetric is refused
+    (ValueError)."""
+    if mask is not None:
+        _require_symmetric(mask, "svtr_attention")
     _chk(qkv, mask)
     B, N, C3 = qkv.shape
     C = C3 // 3
@@ -2645,7 +2666,9 @@ def svtr_attention(qkv, heads, scale, mask=None, want_f32=True, want_hl=False, w
 
 def svtr_attention_bwd(qkv, mask, out, dout, lse, heads, scale, want_range=None):
     """-> dqkv [B,N,3C]; recomputes the probabilities from lse (nothing of size N x N is stored).  want_range = range target: max|dqkv|
-    is folded into both kernels and (dqkv, {s, 1/s}) is returned"""
+    is folded into both kernels and (dqkv, {s, 1/s}) is returned.  A mask that is not symmetric is refused (ValueError)"""
+    if mask is not None:
+        _require_symmetric(mask, "svtr_attention_bwd")
     _chk(qkv, mask, out, dout, lse)
     B, N, C3 = qkv.shape
     assert qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()

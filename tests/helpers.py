@@ -584,3 +584,213 @@ def dm_router_reference(x, params, dout, eps=1e-5, dtype=torch.float64, stages=N
     if stages is not None:
         stages.update(xn=xn, hpre=hpre, vn_r=vn_r, vp=vp, g=g, y=y, zn=zn, zp=zp, z2=z2, dy=dy, dvp_r=dvp_r, dhpre=dhpre)
     return out.reshape(B, P, I, C), G
+
+
+# ---------------------------------------------------------------------------------------------------------
+# written-out yardsticks of the SVTR attention kernels and of one trained SVTR block (tests/test_svtr_kernels_*.py): attention.hip,
+# SvtrAttentionFn and modules.svtr.Block.forward_train.  As above: operands cast to `dtype` first, float64 the reference, float32 the
+# baseline.  x3=...: the baseline of a path whose products run as split-fp16 x3 -- the same formulas in float64 with every operand of
+# such a product replaced by its HL32 value (hl_split) at the scale the code under test uses, and hi*hi + hi*lo + lo*hi in place of the
+# product (lo*lo is what the kernels drop: a' b' - lo_a lo_b exactly, x3_matmul).  Its distance from plain float64 stands where the
+# fp32 baseline's error stands in within_baseline.
+# ---------------------------------------------------------------------------------------------------------
+FP16_PEAK = 16384.0                # ops.FP16_WEIGHT_PEAK: the range target of every power-of-two operand scale
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+
+
+def hl_parts(x, s=1.0):
+    """the two halves of the HL32 value of x at scale s, as the kernels form them (csrc/hl32.hpp split_f16): t = fp32(s x),
+    hi = fp16(t), lo = fp16(t - hi) (exact in fp32) -> (hi / s, lo / s) in float64.  Round to nearest even, fp16 subnormals kept,
+    |t| >= 65520 overflows to inf as it does on the device."""
+    s = s.detach().double() if torch.is_tensor(s) else float(s)
+    t = (x.detach().double() * s).to(torch.float32)
+    hi = t.to(torch.float16)
+    lo = (t - hi.to(torch.float32)).to(torch.float16)
+    return hi.double() / s, lo.double() / s
+
+
+def hl_split(x, s=1.0):
+    """CPU emulation of the HL32 value of x at scale s: (fp16(s x) + fp16(s x - fp16(s x))) / s in float64"""
+    hi, lo = hl_parts(x, s)
+    return hi + lo
+
+
+def pow2_scale_of(x, target=FP16_PEAK):
+    """the largest power of two s with s * max|x| <= target (ops.pow2_scale / mrn_pow2_finalize_f32); 1 where x is all zero"""
+    m = float(x.detach().abs().max()) if x.numel() else 0.0
+    if not (m > 0.0 and m < float("inf")):
+        return 1.0
+    return 2.0 ** float(np.floor(np.log2(np.float32(target) / np.float32(m))))
+
+
+def layernorm_bound_scale(gamma, beta, C, target=FP16_PEAK):
+    """the scale layernorm_fwd_operand derives from the parameters: s (sqrt(C) max|gamma| + max|beta|) <= target"""
+    bound = float(np.float32(np.sqrt(np.float32(C))) * np.float32(gamma.detach().abs().max()) + np.float32(beta.detach().abs().max()))
+    return 2.0 ** float(np.floor(np.log2(np.float32(target) / np.float32(bound))))
+
+
+def x3_matmul(a, b, sa, sb):
+    """a @ b as the split-fp16 x3 kernels form it, in float64: hi hi + hi lo + lo hi of the HL32 values of a (scale sa) and b (sb)"""
+    ah, al = hl_parts(a, sa)
+    bh, bl = hl_parts(b, sb)
+    return (ah + al) @ (bh + bl) - al @ bl
+
+
+def _heads_of(qkv, heads, dtype):
+    B, N, C3 = qkv.shape
+    d = C3 // 3 // heads
+    x = qkv.detach().to(dtype).reshape(B, N, 3, heads, d).permute(2, 0, 3, 1, 4)
+    return x[0], x[1], x[2]                                  # [B, heads, N, d] each
+
+
+def _tokens_of(t):
+    B, h, N, d = t.shape
+    return t.permute(0, 2, 1, 3).reshape(B, N, h * d)
+
+
+def svtr_attention_reference(qkv, mask, heads, scale, dout=None, dtype=torch.float64, mutant=None):
+    """softmax(scale q k^T + mask) v per head on qkv [B, N, 3C] (q | k | v, each (head, d) innermost, d = C / heads: any head
+    dimension), mask [N, N] additive (mask[query][key]) or None, and its backward, written out:
+        S = scale q k^T + mask    P = exp(S - max) / l    lse = max + log l (natural log)    O = P v
+        dP = dO v^T    D = rowsum(dO o O)    dS = P o (dP - D)    dq = scale dS k    dk = scale dS^T q    dv = P^T dO
+    -> dict out [B, N, C], lse [B, heads, N] (, dq, dk, dv [B, N, C] with dout [B, N, C]).
+    mutant: a deliberately wrong variant, for the proof that the test inputs discriminate (test_svtr_kernels_cpu.py)"""
+    q, k, v = _heads_of(qkv, heads, dtype)
+    if mutant == "next_head_v":
+        v = torch.roll(v, -1, 1)
+    S = (q @ k.transpose(-1, -2)) * scale
+    m = None if mask is None else mask.detach().to(dtype)
+    if m is not None:
+        S = S + m
+    mx = S.max(-1, keepdim=True).values
+    e = torch.exp(S - mx)
+    l = e.sum(-1, keepdim=True)
+    P = e / l
+    O = P @ v
+    out = dict(out=_tokens_of(O), lse=(mx + torch.log(l)).squeeze(-1))
+    if dout is None:
+        return out
+    B, N, C = out["out"].shape
+    dO = dout.detach().to(dtype).reshape(B, N, heads, C // heads).permute(0, 2, 1, 3)
+    dP = dO @ v.transpose(-1, -2)
+    D = (dO * O).sum(-1, keepdim=True)
+    if mutant == "no_D":
+        D = torch.zeros_like(D)
+    if mutant == "lse_base":                   # a backward that takes the natural lse it is handed for the base-2 one it stores
+        P = torch.exp2(S * LOG2E - out["lse"].unsqueeze(-1))
+    dS = P * (dP - D)
+    dSk = dS
+    if mutant == "mask_transposed_dkv":        # dk / dv from the probabilities of the TRANSPOSED mask (lse is the forward's)
+        Pt = torch.exp((q @ k.transpose(-1, -2)) * scale + m.t() - out["lse"].unsqueeze(-1))
+        dSk, P = Pt * (dP - D), Pt
+    out["dq"] = _tokens_of(dS @ k) * scale
+    out["dk"] = _tokens_of(dSk.transpose(-1, -2) @ q) * (1.0 if mutant == "dk_no_scale" else scale)
+    out["dv"] = _tokens_of(P.transpose(-1, -2) @ dO)
+    return out
+
+
+X3_OPSCALE, X3_PBIAS = 64.0, 12.0          # csrc/attention.hip: OPSCALE, PBIAS of svtr_attention_x3_kernel
+
+
+def svtr_attention_x3_baseline(qkv, mask, heads, scale):
+    """the x3 baseline of svtr_attention_x3_kernel's output, in float64: q' = HL32(64 scale log2e q) (the factor applied in fp32, as
+    the kernel does), k' = HL32(64 k), v' = HL32(64 v); base-2 scores q' k' (x3) / 4096 + log2e mask; per 32-key tile the running
+    maximum m_t of the tiles so far, p = exp2(s - m_t + 12) (0 where every key so far is masked), l = sum of the UNSPLIT p,
+    O = sum of HL32(p) v' (x3), every tile's share brought to the last maximum by the exact factor exp2(m_t - m_last) -> out [B, N, C]"""
+    q, k, v = _heads_of(qkv, heads, torch.float32)
+    qs = (q * np.float32(np.float32(scale) * np.float32(LOG2E) * np.float32(X3_OPSCALE))).double()      # already 64 x: split at scale 1
+    B, h, N, d = q.shape
+    S = x3_matmul(qs, k.double().transpose(-1, -2), 1.0, X3_OPSCALE) / X3_OPSCALE
+    if mask is not None:
+        S = S + mask.detach().double() * LOG2E
+    T = (N + 31) // 32
+    Sp = torch.full((B, h, N, T * 32), float("-inf"), dtype=torch.float64)
+    Sp[..., :N] = S
+    run = torch.cummax(Sp.view(B, h, N, T, 32).amax(-1), -1).values                      # [B, h, N, T]
+    safe = torch.where(torch.isinf(run), torch.zeros_like(run), run)
+    last = safe[..., -1:]
+    p = torch.exp2(Sp.view(B, h, N, T, 32) - safe.unsqueeze(-1) + X3_PBIAS).to(torch.float32).double()
+    w = torch.exp2(safe - last).unsqueeze(-1)                                            # exact powers in float64 up to rounding 2^-53
+    l = (p * w).sum((-1, -2)).unsqueeze(-1)
+    ph, pl = hl_parts(p, 1.0)
+    ph, pl = (ph * w).reshape(B, h, N, T * 32)[..., :N], (pl * w).reshape(B, h, N, T * 32)[..., :N]
+    vh, vl = hl_parts(v, X3_OPSCALE)
+    O = ((ph + pl) @ (vh + vl) - pl @ vl) / l
+    return _tokens_of(O)
+
+
+SVTR_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "mixer.qkv.weight", "mixer.qkv.bias", "mixer.proj.weight", "mixer.proj.bias",
+                     "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
+def svtr_block_reference(x, params, drop1, drop2, mask, heads, dout, eps=1e-6, dtype=torch.float64, x3=None, mutant=None):
+    """modules.svtr.Block.forward_train and its backward, stage by stage.  x, dout [B, N, C]; params: a dict under the block's
+    state_dict names (SVTR_BLOCK_PARAMS; "mixer.qkv.bias" absent or None: no qkv bias); drop1 / drop2 [B]: the DropPath multipliers of
+    the two branches (0 or 1 / keep) or None; mask [N, N] or None.
+        y1 = LN(x; norm1)    qkv = y1 Wqkv^T + bqkv    ctx = attention(qkv)    pr = ctx Wp^T + bp    x1 = x + drop1 pr
+        y2 = LN(x1; norm2)   f = y2 W1^T + b1          g = gelu(f)             o = g W2^T + b2       out = x1 + drop2 o
+    -> (out [B, N, C], dict of gradients: "dx" and "d" + name for every parameter present: 12, or 13 with the qkv bias).
+    x3: None, or "fused" / "separate": the x3 baseline of the default mode / of TRAIN_OPERAND_FUSION off.  The four forward Linears and
+    their four data gradients are the x3 products (the weight gradients run exact at these row counts: functional.linear_wgrad takes
+    the x3 path from 4096 rows); weights split at the power of two of max|W|; activations and gradients at the power of two of their
+    own max ("separate"), or at what the producer hands on ("fused"): the LayerNorm bound, the scale of max|qkv| for ctx, of max|f| for
+    g, of max|dg| at half the target for df.
+    mutant: a deliberately wrong variant (test_svtr_kernels_cpu.py)"""
+    B, N, C = x.shape
+    p = {k: (None if params.get(k) is None else params[k].detach().to(dtype)) for k in SVTR_BLOCK_PARAMS}
+    X, dout2 = x.detach().to(dtype).reshape(-1, C), dout.detach().to(dtype).reshape(-1, C)
+    rows = lambda d: torch.ones(B * N, 1, dtype=dtype) if d is None else d.detach().to(dtype).repeat_interleave(N).view(-1, 1)
+    d1, d2 = rows(drop1), rows(drop2)
+    scale = (C // heads) ** -0.5
+
+    def mm(a, w, sa=None):                          # a @ w^T
+        if x3 is None:
+            return a @ w.t()
+        sa = pow2_scale_of(a) if (sa is None or x3 == "separate") else sa
+        return x3_matmul(a, w.t(), sa, pow2_scale_of(w))
+
+    ln1 = layernorm_reference(X, p["norm1.weight"], p["norm1.bias"], eps, dtype=dtype)
+    y1 = ln1["y"]
+    qkv = mm(y1, p["mixer.qkv.weight"], layernorm_bound_scale(p["norm1.weight"], p["norm1.bias"], C))
+    if p["mixer.qkv.bias"] is not None:
+        qkv = qkv + p["mixer.qkv.bias"]
+    att = svtr_attention_reference(qkv.reshape(B, N, 3 * C), mask, heads, scale, dtype=dtype)
+    ctx = att["out"].reshape(-1, C)
+    pr = mm(ctx, p["mixer.proj.weight"], pow2_scale_of(qkv)) + p["mixer.proj.bias"]
+    x1 = X + d1 * pr
+    ln2 = layernorm_reference(x1, p["norm2.weight"], p["norm2.bias"], eps, dtype=dtype)
+    y2 = ln2["y"]
+    f = mm(y2, p["mlp.fc1.weight"], layernorm_bound_scale(p["norm2.weight"], p["norm2.bias"], C)) + p["mlp.fc1.bias"]
+    g = gelu_reference(f, dtype)
+    o = mm(g, p["mlp.fc2.weight"], pow2_scale_of(f)) + p["mlp.fc2.bias"]
+    out = x1 + d2 * o
+
+    G = {}
+    do = dout2 if mutant == "no_drop_in_gradient" else d2 * dout2
+    G["dmlp.fc2.weight"] = do.t() @ g
+    G["dmlp.fc2.bias"] = do.reshape(C, -1).sum(1) if mutant == "fc2_bias_wrong_axis" else do.sum(0)
+    dg = mm(do, p["mlp.fc2.weight"].t())
+    df = dg * gelu_grad_reference(f, dtype)
+    G["dmlp.fc1.weight"], G["dmlp.fc1.bias"] = df.t() @ y2, df.sum(0)
+    dy2 = mm(df, p["mlp.fc1.weight"].t(), pow2_scale_of(dg, FP16_PEAK / 2))
+    lb2 = layernorm_reference(x1, p["norm2.weight"], p["norm2.bias"], eps, dy2, dtype)
+    G["dnorm2.weight"], G["dnorm2.bias"] = lb2["dgamma"], lb2["dbeta"]
+    dln2 = lb2["dx"]
+    if mutant == "ln2_no_xhat":
+        gg = dy2 * p["norm2.weight"]
+        dln2 = ln2["rstd"].unsqueeze(-1) * (gg - gg.sum(-1, keepdim=True) / C)
+    dx1 = dout2 + dln2
+    dpr = dx1 if mutant == "no_drop_in_gradient" else d1 * dx1
+    G["dmixer.proj.weight"], G["dmixer.proj.bias"] = dpr.t() @ ctx, dpr.sum(0)
+    dctx = mm(dpr, p["mixer.proj.weight"].t())
+    ab = svtr_attention_reference(qkv.reshape(B, N, 3 * C), mask, heads, scale, dctx.reshape(B, N, C), dtype)
+    dqkv = torch.cat([ab["dq"], ab["dk"], ab["dv"]], -1).reshape(-1, 3 * C)
+    G["dmixer.qkv.weight"] = dqkv.t() @ y1
+    if p["mixer.qkv.bias"] is not None:
+        G["dmixer.qkv.bias"] = dqkv.sum(0)
+    dy1 = mm(dqkv, p["mixer.qkv.weight"].t())
+    lb1 = layernorm_reference(X, p["norm1.weight"], p["norm1.bias"], eps, dy1, dtype)
+    G["dnorm1.weight"], G["dnorm1.bias"] = lb1["dgamma"], lb1["dbeta"]
+    G["dx"] = (dx1 + lb1["dx"]).reshape(B, N, C)
+    return out.reshape(B, N, C), G
