@@ -872,12 +872,8 @@ static size_t attn_tile_lds(bool x3, int dc, int T, size_t extra) {
   return sizeof(float) * (2 * BT * HLD + BT * (dc + 4) + BT * T + HID) + (x3 ? 1024 : 0) + extra;
 }
 
-// the placement of groups x tiles workgroups that group_tile reads back: `pinned` and the grid
-static dim3 attn_grid(int groups, int tiles, bool balance, int& pinned) {
-  pinned = groups > 1 && tiles * ceil_div(groups, 8) <= 32;
-  if (balance && groups > 1 && (groups * tiles) % 8 == 0 && groups * tiles <= 256) pinned = 2;
-  return dim3(pinned == 1 ? 8 * ceil_div(groups, 8) * tiles : groups * tiles);
-}
+// the placement of groups x tiles workgroups (recurrent.hpp: group_grid): the three decoder kernels pin from two experts
+static dim3 attn_grid(int groups, int tiles, bool balance, int& pinned) { return group_grid(groups, tiles, 2, balance, pinned); }
 
 // samples per workgroup: the fewest (from two) that keep the launch within one workgroup per CU
 static int attn_vb(int groups, int B) {

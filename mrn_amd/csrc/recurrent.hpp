@@ -1,5 +1,5 @@
 // What the recurrent translation units share, each thing defined once: lstm.hip (BiLSTM layer), attn_decode.hip (attention decoders:
-// teacher-forced, greedy, beam, lexicon-constrained beam) and their backward, backward.hip and attn_bwd.hip.
+// teacher-forced, greedy, beam, lexicon-constrained beam) and their backward, lstm_bwd.hip and attn_bwd.hip.
 //
 // Samples are independent along the time recurrence, so one workgroup owns a 16-sample batch tile for the
 // whole sequence: hidden state lives in LDS, cell state in registers, and only the recurrent weights stream
@@ -45,34 +45,8 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
 // so every wave-level load is one contiguous 1 KiB line instead of 16 rows x 64 B (pack_fragment_major on the host).
 // Weight fragments of step q+1 are fetched before the MFMAs of step q issue; consecutive MFMAs target different
 // accumulators (the 16x16x4 f32 MFMA has a 40-cycle dependent latency vs 32-cycle issue).
-template <int NG>
-__device__ __forceinline__ void mma_rows(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
-                                         const float* __restrict__ Wp, int K, int wave, int lane) {
-  const int n = lane & 15, g4 = (lane >> 4) * 4;
-  const float* ap = a_lds + n * lda + g4;
-  const int Q = K / 16;
-  const f32x4* wp = reinterpret_cast<const f32x4*>(Wp) + (long)wave * NG * Q * 64 + lane;
-  f32x4 wv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) wv[g] = wp[(long)g * Q * 64];
-#pragma unroll 1   // keep the one-step-ahead register pipeline; full unrolling hoists every load and spills
-  for (int q = 0; q < Q; ++q) {
-    f32x4 wn[NG];
-    const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wn[g] = wp[((long)g * Q + qn) * 64];
-    const f32x4 av = *reinterpret_cast<const f32x4*>(ap + q * 16);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int g = 0; g < NG; ++g) acc[g] = mfma4(av[r], wv[g][r], acc[g]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wv[g] = wn[g];
-  }
-}
-
-// mma_rows over the k-steps of the columns [k0, k0 + kn) of a K-wide fragment-major W, with A holding just those kn columns (from its
-// column 0): the wide-context decoder keeps one chunk of the context in LDS at a time.  Chunk after chunk on the same accumulators,
+// mma_rows_k is the product over the k-steps of the columns [k0, k0 + kn) of the K-wide W, with A holding just those kn columns (from
+// its column 0): the wide-context decoder keeps one chunk of the context in LDS at a time.  Chunk after chunk on the same accumulators,
 // the MFMAs run in the order of one mma_rows over all of K.
 template <int NG>
 __device__ __forceinline__ void mma_rows_k(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
@@ -99,25 +73,14 @@ __device__ __forceinline__ void mma_rows_k(f32x4 (&acc)[NG], const float* __rest
     for (int g = 0; g < NG; ++g) wv[g] = wn[g];
   }
 }
-
-// act[g][r] receives the post-activation gates (i, f, g, o) for the backward pass
-__device__ __forceinline__ void lstm_pointwise(const f32x4 (&acc)[4], const float (&xg)[4][4], const float (&bh)[4],
-                                               float (&c)[4], float (&h)[4], float (&act)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float gi = acc[0][r] + xg[0][r] + bh[0];
-    const float gf = acc[1][r] + xg[1][r] + bh[1];
-    const float gg = acc[2][r] + xg[2][r] + bh[2];
-    const float go = acc[3][r] + xg[3][r] + bh[3];
-    const float ig = sigmoidf_acc(gi), fg = sigmoidf_acc(gf), og = sigmoidf_acc(go), cg = tanhf(gg);
-    const float cn = fg * c[r] + ig * cg;
-    c[r] = cn;
-    h[r] = og * tanhf(cn);
-    act[0][r] = ig; act[1][r] = fg; act[2][r] = cg; act[3][r] = og;
-  }
+template <int NG>
+__device__ __forceinline__ void mma_rows(f32x4 (&acc)[NG], const float* __restrict__ a_lds, int lda,
+                                         const float* __restrict__ Wp, int K, int wave, int lane) {
+  mma_rows_k<NG>(acc, a_lds, lda, Wp, K, 0, K, wave, lane);
 }
 
-// (the form whose accumulators already hold the input projection)
+// The LSTM cell on accumulators that hold the input projection plus the recurrent product: c and h of the four samples of a lane;
+// act[g][r] receives the post-activation gates (i, f, g, o) for the backward pass
 __device__ __forceinline__ void lstm_pointwise0(const f32x4 (&acc)[4], const float (&bh)[4], float (&c)[4], float (&h)[4], float (&act)[4][4]) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -131,6 +94,17 @@ __device__ __forceinline__ void lstm_pointwise0(const f32x4 (&acc)[4], const flo
     h[r] = og * tanhf(cn);
     act[0][r] = ig; act[1][r] = fg; act[2][r] = cg; act[3][r] = og;
   }
+}
+
+// (the form that gets the input projection xg apart: acc + xg first, then the bias)
+__device__ __forceinline__ void lstm_pointwise(const f32x4 (&acc)[4], const float (&xg)[4][4], const float (&bh)[4],
+                                               float (&c)[4], float (&h)[4], float (&act)[4][4]) {
+  f32x4 sum[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sum[g][r] = acc[g][r] + xg[g][r];
+  lstm_pointwise0(sum, bh, c, h, act);
 }
 
 // Up to MAX_GROUPS independent layers (the frozen experts of the router phase) share one launch: grid.x = groups * tiles.
@@ -179,50 +153,9 @@ __device__ __forceinline__ void mma_rows_h(f32x4 (&acc)[NG], const _Float16* __r
 }
 
 // mma_rows_h with the weight stream behind a buffer resource: scalar (wave, gate, k-step) offsets + one 32-bit lane offset, no 64-bit
-// fragment pointers in the vector file (the pointer form put the decoder kernel 60 registers over its 128)
-template <int NG>
-__device__ __forceinline__ void mma_rows_hb(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
-                                            const __amdgpu_buffer_rsrc_t rw, int K, int wave, int lane, int ld = LDH) {
-  const int n = lane & 15, kg = lane >> 4;
-  const int Q = K / 32;
-  const int wwave = __builtin_amdgcn_readfirstlane(wave) * NG * Q * 2048;
-  const int wlane = lane * 32;
-  auto wfrag = [&](int g, int q, int plane) -> f16v8 {
-    return __builtin_bit_cast(f16v8, __builtin_amdgcn_raw_buffer_load_b128(rw, wlane, wwave + ((g * Q + q) * 128 + plane) * 16, 0));
-  };
-  const _Float16* ah = a_hi + n * ld + kg * 8;
-  const _Float16* al = a_lo + n * ld + kg * 8;
-  f16v8 wh[NG], wl[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    wh[g] = wfrag(g, 0, 0);
-    wl[g] = wfrag(g, 0, 1);
-  }
-#pragma unroll 1
-  for (int q = 0; q < Q; ++q) {
-    f16v8 nh[NG], nl[NG];
-    const int qn = (q + 1 < Q) ? q + 1 : q;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      nh[g] = wfrag(g, qn, 0);
-      nl[g] = wfrag(g, qn, 1);
-    }
-    const f16v8 xh = *reinterpret_cast<const f16v8*>(ah + q * 32), xl = *reinterpret_cast<const f16v8*>(al + q * 32);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[g], acc[g], 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      wh[g] = nh[g];
-      wl[g] = nl[g];
-    }
-  }
-}
-
-// mma_rows_hb over the k-steps of the columns [k0, k0 + kn) of a K-wide stream, A holding just those kn columns (see mma_rows_k)
+// fragment pointers in the vector file (the pointer form put the decoder kernel 60 registers over its 128).
+// mma_rows_hb_k is the product over the k-steps of the columns [k0, k0 + kn) of the K-wide stream, A holding just those kn columns
+// (see mma_rows_k)
 template <int NG>
 __device__ __forceinline__ void mma_rows_hb_k(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
                                               const __amdgpu_buffer_rsrc_t rw, int K, int k0, int kn, int wave, int lane, int ld) {
@@ -264,6 +197,11 @@ __device__ __forceinline__ void mma_rows_hb_k(f32x4 (&acc)[NG], const _Float16* 
     }
   }
 }
+template <int NG>
+__device__ __forceinline__ void mma_rows_hb(f32x4 (&acc)[NG], const _Float16* __restrict__ a_hi, const _Float16* __restrict__ a_lo,
+                                            const __amdgpu_buffer_rsrc_t rw, int K, int wave, int lane, int ld = LDH) {
+  mma_rows_hb_k<NG>(acc, a_hi, a_lo, rw, K, 0, K, wave, lane, ld);
+}
 
 __device__ __forceinline__ void store_h_split(_Float16* hi, _Float16* lo, int idx, float v) {
   _Float16 h, l;
@@ -286,6 +224,19 @@ __device__ __forceinline__ void group_tile(int groups, int tiles, int pinned, in
     tile = pinned ? (int)((blockIdx.x / 8) % tiles) : (int)blockIdx.x % tiles;
   }
 }
+
+// The host side of group_tile: `pinned` and the grid of a launch of groups x tiles workgroups.  A group owns one weight stream (1 MiB at
+// hidden 256): from `pin_from` groups on, and while a group's tiles fit the 32 CUs of an XCD, its tiles share one XCD's 4 MiB L2 instead
+// of every XCD cycling through every group's weights (pinned == 1: whole rounds of eight groups; the workgroups past the last group
+// return).  `balance` prefers the eight equal runs (pinned == 2) where the pairs divide by eight and fit one workgroup per CU
+inline dim3 group_grid(int groups, int tiles, int pin_from, bool balance, int& pinned) {
+  pinned = groups >= pin_from && tiles * ceil_div(groups, 8) <= 32;
+  if (balance && groups >= pin_from && (groups * tiles) % 8 == 0 && groups * tiles <= 256) pinned = 2;
+  return dim3(pinned == 1 ? 8 * ceil_div(groups, 8) * tiles : groups * tiles);
+}
+
+// the hidden sizes the LSTM layer kernels, forward and backward, are instantiated for (LstmGeom)
+inline bool lstm_hidden_ok(int hidden) { return hidden == 128 || hidden == 256 || hidden == 512; }
 
 __device__ __forceinline__ float fast_tanh(float x) {
   // tanh(x) = 1 - 2/(exp(2x)+1); saturates correctly through inf / 0

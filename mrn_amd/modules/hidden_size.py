@@ -2,7 +2,7 @@
 
 The reference is generic in opt.hidden_size (modules/model.py: BidirectionalLSTM(..., opt.hidden_size, opt.hidden_size), nn.Linear(512,
 opt.hidden_size) for SVTR, DM_Router(out_dim, 2 * out_dim, ...), DERNet.feature_dim = out_dim * len(self.model)).  Here the LSTM layer
-kernels (csrc/lstm.hip, csrc/backward.hip) are built for 128, 256 and 512 hidden units -- 8 waves of one 16-unit tile at 128, 16 waves at 256,
+kernels (csrc/lstm.hip, csrc/lstm_bwd.hip) are built for 128, 256 and 512 hidden units -- 8 waves of one 16-unit tile at 128, 16 waves at 256,
 16 waves of two tiles each at 512 -- and with them the whole CTC family runs at those sizes: CRNN, and SVTR with its single Linear.  The
 attention decoder (attn_decoder_kernel, csrc/attn_bwd.hip) is built for 256 only, so a net with the attention head runs 256 only.
 """

@@ -492,17 +492,23 @@ def test_reduced_mode_winograd_eligibility():
 
 
 def test_recurrent_helpers_are_defined_once():
-    """the MFMA wrapper and the fast tanh that the recurrent forward and backward units must agree on are each defined exactly once in
-    csrc/, in recurrent.hpp, which those units include"""
+    """the MFMA wrapper, the fast tanh, the LSTM geometry, the workgroup placement rule (its host and its device side) and the hidden-size
+    rule that the recurrent forward and backward units must agree on are each defined exactly once in csrc/, in recurrent.hpp, which
+    those units include; the LSTM backward has a unit of its own"""
     import re
     csrc = os.path.join(ROOT, "mrn_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".cpp", ".h")))
-    for helper, ret in (("mfma4", "f32x4"), ("fast_tanh", "float")):
-        defs = [f for f in files for _ in re.finditer(r"\b%s\s+%s\(" % (ret, helper), open(os.path.join(csrc, f)).read())]
+    text = {f: open(os.path.join(csrc, f)).read() for f in files}
+    for helper, ret in (("mfma4", "f32x4"), ("fast_tanh", "float"), ("group_grid", "dim3"), ("group_tile", "void"), ("lstm_hidden_ok", "bool")):
+        defs = [f for f in files for _ in re.finditer(r"\b%s\s+%s\(" % (ret, helper), text[f])]
         assert defs == ["recurrent.hpp"], (helper, defs)
-    for unit in ("lstm.hip", "attn_decode.hip", "attn_bwd.hip", "backward.hip"):
-        assert '#include "recurrent.hpp"' in open(os.path.join(csrc, unit)).read(), unit
+    assert [f for f in files for _ in re.finditer(r"\bstruct\s+LstmGeom\b", text[f])] == ["recurrent.hpp"]
+    for unit in ("lstm.hip", "lstm_bwd.hip", "attn_decode.hip", "attn_bwd.hip"):
+        assert '#include "recurrent.hpp"' in text[unit], unit
     assert not os.path.exists(os.path.join(csrc, "rnn.hip"))
+    assert "lstm_layer_bwd" not in text["backward.hip"] and "lstm_layer_bwd_kernel" in text["lstm_bwd.hip"]
+    for gone in ("f16v8h", "MRN_LSTM_RB"):
+        assert [f for f in files if gone in text[f]] == [], gone
 
 
 def test_hl32_format_is_defined_once():

@@ -567,7 +567,7 @@ def test_lstm_recurrence_on_f16_mfma(ops):
 
 def test_lstm_x3_batch_beyond_the_32bit_row_offsets(ops):
     """the x3 layer kernel addresses its rows with 32-bit byte offsets into [B][T][ndir][4H]; the launcher cuts a batch whose array is
-    beyond 4 GiB into chunks of whole tiles (lstm.hip: lstm_x3_launch).  T = 2048: 224 samples fit, B = 256 goes as 224 + 32 -- the same
+    beyond 4 GiB into chunks of whole tiles (lstm.hip: lstm_launch).  T = 2048: 224 samples fit, B = 256 goes as 224 + 32 -- the same
     bits as the two parts launched separately"""
     G, B, T, Hd = 1, 256, 2048, 256
     gen = torch.Generator(device="cuda").manual_seed(77)

@@ -1,6 +1,6 @@
 """The frozen experts' LSTM layer (split-fp16 x3 recurrent product) at BASELINE sizes: G experts x 2 directions, B = 256, T = 65 (CRNN) /
-T = 26-step geometry of TRBA's encoder (T = 65 as well).  MRN_LSTM_RB = 1 / 2 forces the 16- / 32-sample tile form (read once per
-process: run the script once per form for an A/B)."""
+T = 26-step geometry of TRBA's encoder (T = 65 as well); then one layer being trained, forward with saves and backward through time.
+MRN_LIB_PATH selects the library: run the script once per library for an A/B."""
 import os
 import sys
 import torch
@@ -8,7 +8,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mrn_amd import ops
 dev = torch.device("cuda:0")
 Hd, T = 256, 65
-print("MRN_LSTM_RB =", os.environ.get("MRN_LSTM_RB", "(default)"))
 for G, B in ((1, 256), (3, 256), (6, 256), (6, 64), (3, 32)):
     torch.manual_seed(G)
     xproj = torch.randn(G, B, T, 8 * Hd, device=dev) * 0.7
