@@ -863,6 +863,179 @@ __global__ __launch_bounds__(NTH) void attn_lexicon_kernel(const BeamGroup grp, 
   attn_beam_body<X3, true>(grp, &lex);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exact scoring of per-sample candidate words on the attention head (attn_score_kernel, include/mrn_attn_score.h; the algorithm is
+// stated in mrn_amd/modules/decoding.py): score[b][k] = log p(word, eos | sample b) of word cand[b][k], every (sample, slot) pair a
+// teacher-forced roll-out of its own, all steps of all experts in one launch.  The 16 MFMA rows of a workgroup are 16 / per samples x
+// per slots (per = the smallest of 1, 2, 4, 8, 16 that is >= K; K > 16: one sample per workgroup, ceil(K / 16) workgroups per sample):
+// row r is slot k0 + r % per of sample b0 + r / per, rows of one sample read the same Hproj / Hb slices.  Per step:
+//   (0)-(7) the shared step in its whole-context form with the greedy kernel's token feed and generator: the row's input is the start
+//       token, then the word's classes; a row's logits are bit-identical to the greedy kernel's for the same token history
+//   (8) the generator's sink keeps, per lane and row, a running (max, sum of exp) over the lane's classes (a NaN logit counts as -inf)
+//       and hands the logit of the row's target class (the word's next class, eos behind the last) to LDS; the pairs are merged over
+//       the 16 class columns by shuffles, then over the 16 waves through LDS in wave order -- one order of operations for every row,
+//       so the same (sample, word) gives the same bits in any slot.  No logits are written
+//   (9) thread r, row r: lp = target logit - (max + log sum); added to the row's score (and stored to logp) while step <= the word's
+//       length, then the next step's input and target
+// The loop runs to the longest word of the workgroup's rows.  A slot is dead (score -inf, logp 0) when it is unused (-1), when a class
+// of its word is not below the expert's num_class, or when its score is -inf or NaN.  Lengths are clamped to min(Lmax, S - 1) and a
+// word index outside the table counts as unused, so no read or write leaves the arrays whatever the tables hold
+// ---------------------------------------------------------------------------------------------
+struct ScoreParams {
+  GreedyParams g;                   // the greedy operands (logits / tokens_out unused)
+  float* score_all;                 // [B][K]
+  float* logp;                      // optional [B][K][S]
+};
+struct ScoreGroup {
+  ScoreParams g[MAX_GROUPS];
+  const int32_t* lex_tokens;        // [N][Lmax]
+  const int32_t* lex_len;           // [N]
+  const int32_t* cand;              // [B][K]
+  int tiles, groups, pinned, per, nblk, K, N, Lmax, eos;
+};
+constexpr int SCORE_LDS_EXTRA = 4 * (5 * BT + 2 * NW * BT);  // word, length, input token, target, target logit + 16 x 16 (max, sum) pairs
+
+// (m, s) <- the log-sum-exp pair of both: s = sum of exp(x - m) over the classes seen; an empty pair is (-inf, 0)
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+  const float M = fmaxf(m, om);
+  s = M > -INFINITY ? s * expf(m - M) + os * expf(om - M) : 0.f;
+  m = M;
+}
+
+template <bool X3>
+__global__ __launch_bounds__(NTH) void attn_score_kernel(const ScoreGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int gi, tile_;
+  group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
+  if (gi >= grp.groups) return;
+  const ScoreParams& sp = grp.g[gi];
+  const GreedyParams& gp = sp.g;
+  const AttnDecParams& p = gp.a;
+  const int C = gp.num_class, S = p.S, K = grp.K, per = grp.per, eos = grp.eos, Lmax = grp.Lmax;
+  const int k0 = (tile_ % grp.nblk) * BT;          // the first slot of this workgroup (K > 16: nblk workgroups per sample)
+  const float inv_gen = X3 ? p.w_inv[3] : 1.f;     // the generator stream (x3: fp16 hi / lo behind a buffer resource) and its inverse prescale
+  const __amdgpu_buffer_rsrc_t r_gen = make_rsrc(gp.w_gen, X3 ? (C + 15) / 16 * 16 * HID * 4 : 0);
+  const AttnTile<X3> v = attn_tile<X3>(lds, p, p.D, tile_ / grp.nblk, BT / per, per);
+  int* word_lds = reinterpret_cast<int*>(v.sw_lds + HID);    // behind the shared map: the row state of SCORE_LDS_EXTRA
+  int* wlen_lds = word_lds + BT;
+  int* tok_lds = wlen_lds + BT;
+  int* tgt_lds = tok_lds + BT;
+  float* tl_lds = reinterpret_cast<float*>(tgt_lds + BT);
+  float* red_m = tl_lds + BT;
+  float* red_s = red_m + NW * BT;
+  const int t_ = v.t_, lane = v.lane, wave = v.wave, rbase = v.rbase, j = v.j;
+
+  // wave r, row r: its word, and whether this expert can spell it
+  {
+    const int row = wave, b = v.sample(row), slot = k0 + row % per;
+    const bool mine = row < v.nrows && b < v.Bend && slot < K;
+    int w = mine ? grp.cand[(long)b * K + slot] : -1;
+    if (w >= grp.N) w = -1;
+    int L = -1;
+    if (w >= 0) {
+      L = min(max(grp.lex_len[w], 0), min(Lmax, S - 1));
+      int bad = 0;
+      for (int i = lane; i < L; i += 64) {
+        const int cl = grp.lex_tokens[(long)w * Lmax + i];
+        bad |= (cl < 0 || cl >= C) ? 1 : 0;
+      }
+      if (__any(bad)) L = -1;
+    }
+    if (lane == 0) {
+      const long k = gp.start[0];
+      word_lds[row] = w;
+      wlen_lds[row] = L;
+      tok_lds[row] = (k >= C || k < 0) ? 0 : (int)k;
+      tgt_lds[row] = L > 0 ? grp.lex_tokens[(long)w * Lmax] : eos;
+      tl_lds[row] = 0.f;
+    }
+    if (sp.logp && mine) {                       // 0 past the word's end (a dead slot: everywhere)
+      float* lp = sp.logp + ((long)b * K + slot) * S;
+      for (int s = L + 1 + lane; s < S; s += 64) lp[s] = 0.f;
+    }
+  }
+  float c[4] = {0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+  int nsteps = 0;                                // the longest word of the workgroup's rows and its eos
+  for (int r = 0; r < BT; ++r) nsteps = max(nsteps, wlen_lds[r] + 1);
+  const int row_ = t_ < BT ? t_ : 0;             // thread r < 16 owns row r's score
+  const int myL = wlen_lds[row_];
+  const int32_t* const mytok = grp.lex_tokens + (long)max(word_lds[row_], 0) * Lmax;
+  const int myb = v.sample(row_), myslot = k0 + row_ % per;
+  const bool mine = t_ < BT && row_ < v.nrows && myb < v.Bend && myslot < K;
+  float* const mylp = (sp.logp && mine) ? sp.logp + ((long)myb * K + myslot) * S : nullptr;
+  float total = 0.f;
+
+  for (int step = 0; step < nsteps; ++step) {
+    attn_scores<X3, false>(v, p, step);
+    // (0) the token's row of etab
+    f32x4 acc5[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* ep = gp.etab + (long)tok_lds[rbase + r] * (4 * HID) + j;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc5[g][r] = ep[g * HID];
+    }
+    float h[4], act[4][4];
+    attn_cell<X3, false, false>(v, p, step, acc5, c, h, act);
+    __syncthreads();
+    // (7) generator on the new h, (8) running (max, sum) of the lane's classes and the target's logit
+    int tg[4];
+    float m[4], s[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      tg[r] = tgt_lds[rbase + r];
+      m[r] = -INFINITY;
+      s[r] = 0.f;
+    }
+    generator_tiles<X3>(v, gp, r_gen, inv_gen, [&](int r, int cls, float x) {
+      x = x == x ? x : -INFINITY;
+      if (cls == tg[r]) tl_lds[rbase + r] = x;
+      if (x > m[r]) {
+        s[r] = s[r] * expf(m[r] - x) + 1.f;
+        m[r] = x;
+      } else if (x > -INFINITY) {
+        s[r] += expf(x - m[r]);
+      }
+    });
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float om = __shfl_xor(m[r], o);
+        const float os = __shfl_xor(s[r], o);
+        lse_merge(m[r], s[r], om, os);
+      }
+    }
+    if (v.col == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        red_m[wave * BT + rbase + r] = m[r];
+        red_s[wave * BT + rbase + r] = s[r];
+      }
+    }
+    __syncthreads();
+    if (t_ < BT) {                 // (9); the next step reads tok_lds and tgt_lds behind the barriers of its phases (1)-(3)
+      float M = red_m[t_], sum = red_s[t_];
+      for (int w = 1; w < NW; ++w) lse_merge(M, sum, red_m[w * BT + t_], red_s[w * BT + t_]);
+      const float lp = tl_lds[t_] - (M + logf(sum));
+      if (step <= myL) {
+        total += lp;
+        if (mylp) mylp[step] = lp;
+      }
+      tok_lds[t_] = step < myL ? mytok[step] : eos;
+      tgt_lds[t_] = step + 1 < myL ? mytok[step + 1] : eos;
+    }
+  }
+
+  if (mine) {
+    const bool live = myL >= 0 && total == total && total > -INFINITY;
+    sp.score_all[(long)myb * K + myslot] = live ? total : -INFINITY;
+    if (!live && mylp)
+      for (int s = 0; s <= myL; ++s) mylp[s] = 0.f;
+  }
+}
+
 }  // namespace
 
 // ---- launch rules of the three attention decoder kernels ------------------------------------------------------
@@ -1318,4 +1491,90 @@ MRN_EXPORT int mrn_attn_lexicon_decode_x3_grouped(const void* const* Hb, const v
   const LexOperands trie{child_off, child_tok, child_node, word_of, nodes, depth, word};
   return beam_grouped("mrn_attn_lexicon_decode_x3_grouped", true, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
                       groups, hidden, stream, &trie);
+}
+
+// ---- exact scoring of per-sample candidate words on the attention head: attn_score_kernel (include/mrn_attn_score.h) ----
+// the whole-context tile plus the row state (SCORE_LDS_EXTRA); there is no chunked form.  ops.attn_score_whole_context restates the rule
+static int score_launch(ScoreGroup& grp, int groups, int D, int T, hipStream_t st) {
+  grp.groups = groups;
+  const int B = grp.g[0].g.a.B, K = grp.K;
+  int per = 1;                               // slots of a sample in a workgroup: the smallest of 1, 2, 4, 8, 16 that is >= K
+  while (per < K && per < BT) per *= 2;
+  grp.per = per;
+  grp.nblk = ceil_div(K, BT);                // K > 16: one sample per workgroup, nblk workgroups per sample
+  grp.tiles = K > BT ? B * grp.nblk : ceil_div(B, BT / per);
+  const dim3 grid = attn_grid(groups, grp.tiles, true, grp.pinned);
+  const bool x3 = grp.g[0].g.a.w_inv != nullptr;
+  const size_t lds = attn_tile_lds(x3, D, T, SCORE_LDS_EXTRA);
+  if (x3) attn_kernel_launch(attn_score_kernel<true>, grp, grid, lds, st);
+  else attn_kernel_launch(attn_score_kernel<false>, grp, grid, lds, st);
+  MRN_LAUNCH_CHECK("attn_score");
+  return MRN_OK;
+}
+
+// `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch per MAX_GROUPS experts; the word table
+// and the candidate table are shared.  Every limit is checked for every group before the first launch
+static int score_grouped(const char* who, bool x3, const DecodeOperands& o, int eos, const int32_t* lex_tokens, int Lmax,
+                         const int32_t* lex_len, int N, const int32_t* cand, int K, PtrArray score_all, PtrArray logp, int groups,
+                         int hidden, void* stream) {
+  const int B = o.B, T = o.T, D = o.D, S = o.S;
+  MRN_CHECK_ARG(decode_arrays_given(o, x3) && score_all && groups >= 1, "%s: null operand", who);
+  MRN_CHECK_ARG(hidden == HID, "%s: hidden=%d unsupported (library is built for %d)", who, hidden, HID);
+  MRN_CHECK_ARG(S >= 1 && S <= 512, "%s: S=%d steps outside 1 ... 512", who, S);
+  MRN_CHECK_ARG(D > 0 && D % (x3 ? 32 : 16) == 0, "%s: D=%d must be a multiple of %d", who, D, x3 ? 32 : 16);
+  MRN_CHECK_ARG(B >= 0 && T > 0, "%s: bad geometry (B=%d T=%d)", who, B, T);
+  MRN_CHECK_ARG(attn_tile_lds(x3, D, T, SCORE_LDS_EXTRA) <= 160 * 1024, "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+  MRN_CHECK_ARG(N >= 1 && N <= (1 << 20), "%s: N=%d words outside 1 ... 2^20", who, N);
+  MRN_CHECK_ARG(Lmax >= 0 && lex_len && (lex_tokens || Lmax == 0), "%s: null word table (Lmax=%d)", who, Lmax);
+  MRN_CHECK_ARG(K >= 1 && cand, "%s: K=%d candidate slots, needs K >= 1 and a table", who, K);
+  MRN_CHECK_ARG((long)B * ceil_div(K, BT) <= (1L << 24), "%s: B=%d samples x K=%d slots: too many workgroups", who, B, K);
+  for (int g = 0; g < groups; ++g) {
+    MRN_CHECK_ARG(decode_group_given(o, x3, g) && (B == 0 || score_all[g]), "%s: null operand in group %d", who, g);
+    MRN_CHECK_ARG(o.num_class[g] >= 2 && o.num_class[g] <= 65535, "%s: num_class=%d in group %d outside 2 ... 65535", who, o.num_class[g], g);
+    MRN_CHECK_ARG(eos >= 0 && eos < o.num_class[g], "%s: eos=%d outside the %d classes of group %d", who, eos, o.num_class[g], g);
+  }
+  if (B == 0) return MRN_OK;
+  for (int g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
+    const int n = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
+    ScoreGroup grp;
+    memset(&grp, 0, sizeof(grp));
+    grp.lex_tokens = lex_tokens; grp.lex_len = lex_len; grp.cand = cand;
+    grp.K = K; grp.N = N; grp.Lmax = Lmax; grp.eos = eos;
+    for (int i = 0; i < n; ++i) {
+      const int g = g0 + i;
+      ScoreParams& sp = grp.g[i];
+      greedy_fill(sp.g, o, x3, g);
+      sp.score_all = (float*)score_all[g];
+      sp.logp = logp ? (float*)logp[g] : nullptr;
+    }
+    const int rc = score_launch(grp, n, D, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return MRN_OK;
+}
+
+MRN_EXPORT int mrn_attn_score_candidates_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                     const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                     const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                     const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                                     const int* num_class, int eos, const int32_t* lex_tokens, int Lmax,
+                                                     const int32_t* lex_len, int N, const int32_t* cand, int K,
+                                                     const void* const* score_all, const void* const* logp, int groups, int B, int T,
+                                                     int D, int S, int hidden, void* stream) {
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return score_grouped("mrn_attn_score_candidates_grouped_f32", false, o, eos, lex_tokens, Lmax, lex_len, N, cand, K, score_all, logp, groups,
+                       hidden, stream);
+}
+
+MRN_EXPORT int mrn_attn_score_candidates_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                    const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                    const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                    const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                                    const void* const* b_gen, const int* num_class, int eos, const int32_t* lex_tokens,
+                                                    int Lmax, const int32_t* lex_len, int N, const int32_t* cand, int K,
+                                                    const void* const* score_all, const void* const* logp, int groups, int B, int T, int D,
+                                                    int S, int hidden, void* stream) {
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  return score_grouped("mrn_attn_score_candidates_x3_grouped", true, o, eos, lex_tokens, Lmax, lex_len, N, cand, K, score_all, logp, groups,
+                       hidden, stream);
 }

@@ -209,12 +209,10 @@ def _attn_search_host(who, sd, batch_H, sos, eos, width, batch_max_length, trie,
     if Hb.ndim != 3 or W < 1 or S < 1:
         raise ValueError(f"{who} needs batch_H [B][T][D], width >= 1 and batch_max_length >= 0, got {Hb.shape}, {W}, {S - 1}")
     B, T, D = Hb.shape
-    emb, gen_w, gen_b = w["char_embeddings.weight"], w["generator.weight"], w["generator.bias"]
-    C, Hd = gen_w.shape
+    C, Hd = w["generator.weight"].shape
     if not 0 <= eos < C:
         raise ValueError(f"eos={eos} outside the {C} classes")
-    a = "attention_cell."
-    Hproj = Hb @ w[a + "i2h.weight"].T                                    # [B][T][H]
+    Hproj = Hb @ w["attention_cell.i2h.weight"].T                         # [B][T][H]
     h, c = np.zeros((B, W, Hd)), np.zeros((B, W, Hd))
     last = np.full((B, W), int(sos), dtype=np.int64)
     score = np.full((B, W), -np.inf)
@@ -229,21 +227,8 @@ def _attn_search_host(who, sd, batch_H, sos, eos, width, batch_max_length, trie,
         if not ((score > -np.inf) & ~finished).any():
             break
         tok = np.where((last >= C) | (last < 0), 0, last)
-        hp = h @ w[a + "h2h.weight"].T + w[a + "h2h.bias"]
-        e = np.tanh(Hproj[:, None] + hp[:, :, None, :]) @ w[a + "score.weight"][0]              # [B][W][T]
-        e = np.exp(e - e.max(axis=2, keepdims=True))
-        alpha = e / e.sum(axis=2, keepdims=True)
-        ctx = np.einsum("bwt,btd->bwd", alpha, Hb)
-        g = (np.concatenate([ctx, emb[tok]], axis=2) @ w[a + "rnn.weight_ih"].T + w[a + "rnn.bias_ih"]
-             + h @ w[a + "rnn.weight_hh"].T + w[a + "rnn.bias_hh"])
-        gi, gf, gg, go = np.split(g, 4, axis=2)
-        c2 = _sigmoid(gf) * c + _sigmoid(gi) * np.tanh(gg)
-        h2 = _sigmoid(go) * np.tanh(c2)
-        x = h2 @ gen_w.T + gen_b                                          # [B][W][C]
-        x = np.where(np.isnan(x), -np.inf, x)
-        peak = x.max(axis=2, keepdims=True)
+        h2, c2, lp = _attn_cell_host(w, Hb, Hproj, h, c, tok)            # lp [B][W][C]
         with np.errstate(invalid="ignore", divide="ignore"):
-            lp = x - (peak + np.log(np.exp(x - peak).sum(axis=2, keepdims=True)))
             cand = score[:, :, None] + lp
         done = np.full((B, W, C), -np.inf)
         done[:, :, eos] = score
@@ -629,3 +614,214 @@ def attn_lexicon_request(attn_lexicon, width):
     if attn_lexicon is not None and width is None:
         raise ValueError("attn_lexicon constrains the beam search of attn_beam=<width>: pass both (evaluation under no_grad, attention head)")
     return attn_lexicon
+
+
+# ---- exact scoring of per-sample candidate words on the attention head -----------------------------------------------------------------
+# With opt.candidates every image is decoded against a word list of its own (the protocol of IIIT5K-50, SVT-50, IC03-50).  A CTC head
+# takes ctc_lexicon_host / mrn_ctc_lexicon_decode_f32 with a candidate table.  On the attention head B x K roll-outs are affordable
+# where N x B were not: mrn_attn_score_candidates_* (mrn_amd/csrc/attn_decode.hip attn_score_kernel) scores every (sample, slot) pair
+# by a teacher-forced roll-out in float32, all steps of all experts in one launch, attn_candidates_host below in float64.  For sample
+# b and slot k, word w = cand[b][k] with classes c_1 .. c_L (L >= 0):
+#
+#   the inputs of steps 0 .. L are sos, c_1, .., c_L (a start token >= num_class or < 0 counts as 0, as in greedy);
+#   the targets are c_1, .., c_L, eos;
+#   lp_s = log_softmax(generator(h_s)) over the num_class classes, a NaN logit counting as -inf;
+#   score = sum_s lp_s[target_s] = log p(word, eos | image) of the model, exactly: no beam, nothing pruned, nothing renormalised.
+#
+# A slot is dead, with index -1 and score -inf, when it is unused (-1), when a class of its word is not below num_class, or when its
+# score is -inf or NaN.  Per sample the slots are ranked as ctc_lexicon_host ranks them: descending score, a tie to the lower slot,
+# dead slots last.  Outputs, in ops.ctc_lexicon_decode's order: index int32 [B][n] (WORD indices), score [B][n], score_all [B][K], and
+# for the best entry path int64 [B][S] (its classes, then eos) and prob float32 [B][S] (its per-token probabilities, 1 behind the
+# first eos) -- the form attn_beam_decode gives its best entry; a sample without a live slot gets path all eos and prob all 0 (the
+# empty prediction with confidence 0).  Optional: logp [B][K][S], the per-token log-probabilities, 0 behind a word's eos and in a
+# dead slot.
+CANDIDATES_MAX_STEPS = 512
+CANDIDATES_MAX_CLASSES = 65535
+CANDIDATES_MAX_WORDS = 1 << 20
+CANDIDATES_MAX_TOP_N = 16
+
+
+def candidates_options(opt):
+    """(candidates or None, n) of an options object: opt.candidates is absent / None (off), a callable (the batch's list of label
+    strings -> one sequence of words per sample) or a dict label -> words; n = opt.lexicon_top_n (default 1).  The option replaces the
+    decoding of either head, so together with lexicon, attn_lexicon, ctc_decode='beam' or attn_decode='beam' it is a ValueError"""
+    n = _positive_int(opt, "lexicon_top_n", DEFAULT_LEXICON_TOP_N)
+    cands = getattr(opt, "candidates", None)
+    if cands is None:
+        return None, n
+    if not callable(cands) and not isinstance(cands, dict):
+        raise ValueError(f"candidates must be a callable (labels -> word lists) or a dict label -> words, got {type(cands).__name__}")
+    for key, on in (("lexicon", getattr(opt, "lexicon", None) is not None), ("attn_lexicon", getattr(opt, "attn_lexicon", None) is not None),
+                    ("ctc_decode='beam'", getattr(opt, "ctc_decode", "greedy") == "beam"),
+                    ("attn_decode='beam'", getattr(opt, "attn_decode", "greedy") == "beam")):
+        if on:
+            raise ValueError(f"candidates and {key} both replace the head's decoding: set one of them")
+    return cands, n
+
+
+def candidate_lists(candidates, labels):
+    """the word lists of a batch: one list of str per label.  A dict without a label, a callable that returns another number of lists
+    than labels, and an entry that is no word are ValueErrors"""
+    labels = list(labels)
+    if isinstance(candidates, dict):
+        missing = [gt for gt in labels if gt not in candidates]
+        if missing:
+            raise ValueError(f"candidates: no word list for the label {missing[0]!r}")
+        lists = [candidates[gt] for gt in labels]
+    else:
+        lists = list(candidates(labels))
+        if len(lists) != len(labels):
+            raise ValueError(f"candidates: {len(lists)} word lists for {len(labels)} labels")
+    out = []
+    for words in lists:
+        if isinstance(words, (str, bytes)) or not hasattr(words, "__iter__"):
+            raise ValueError(f"candidates: a sample's words must be a sequence of str, got {type(words).__name__}")
+        words = list(words)
+        for w in words:
+            if not isinstance(w, str):
+                raise ValueError(f"candidates: a sample's words must be a sequence of str, got an entry {w!r}")
+        out.append(words)
+    return out
+
+
+class CandidateTable:
+    """the word table of one validation() call: the union of the candidate lists, encoded once by the head's lexicon encoder
+    (encode_lexicon / encode_attn_lexicon: words the converter cannot spell are dropped); rows() gives a batch's cand int32 [B][K]"""
+
+    def __init__(self, converter, lists, attn, batch_max_length):
+        union = list(dict.fromkeys(w for words in lists for w in words))
+        if attn:
+            self.tokens, self.lengths, self.words = encode_attn_lexicon(converter, union, batch_max_length)
+        else:
+            self.tokens, self.lengths, self.words = encode_lexicon(converter, union)
+        self.index = {w: i for i, w in enumerate(self.words)}
+
+    def rows(self, lists):
+        """cand int32 [B][K] of a batch: the table indices of every sample's words in their order (a dropped or unknown word leaves no
+        slot), -1 behind; K >= 1"""
+        rows = [[self.index[w] for w in words if w in self.index] for words in lists]
+        K = max([len(r) for r in rows] + [1])
+        cand = np.full((len(rows), K), -1, dtype=np.int32)
+        for b, r in enumerate(rows):
+            cand[b, :len(r)] = r
+        return cand
+
+
+def check_word_table(lex_tokens, lex_len, cand, B, S):
+    """the host check of a word table and a candidate table (numpy) before any launch: int tokens [N >= 1][Lmax] with classes >= 0,
+    lengths [N] in 0 .. min(Lmax, S - 1), cand [B][K >= 1] in -1 .. N - 1 -> (N, Lmax, K); anything else is a ValueError"""
+    tokens, lengths, cand = np.asarray(lex_tokens), np.asarray(lex_len), np.asarray(cand)
+    if tokens.ndim != 2 or lengths.shape != tokens.shape[:1] or len(lengths) < 1 or len(lengths) > CANDIDATES_MAX_WORDS:
+        raise ValueError(f"candidates: a word table needs tokens [1 <= N <= 2^20][Lmax] and lengths [N], got {tokens.shape}, {lengths.shape}")
+    N, Lmax = tokens.shape
+    if lengths.min() < 0 or lengths.max() > min(Lmax, S - 1):
+        raise ValueError(f"candidates: word lengths outside 0..{min(Lmax, S - 1)} (the longest word and its end token take S = {S} steps)")
+    if (tokens[np.arange(Lmax)[None, :] < lengths[:, None]] < 0).any():
+        raise ValueError("candidates: negative class in a word")
+    if cand.ndim != 2 or cand.shape[0] != B or cand.shape[1] < 1:
+        raise ValueError(f"candidates: a candidate table needs cand [B = {B}][K >= 1], got {cand.shape}")
+    if cand.size and (cand.min() < -1 or cand.max() > N - 1):
+        raise ValueError(f"candidates: a candidate index outside -1..{N - 1}")
+    return N, Lmax, cand.shape[1]
+
+
+def _attn_cell_host(w, Hb, Hproj, h, c, tok):
+    """one step of the attention cell of modules/prediction.py in float64 on rows [B][R]: h, c [B][R][H], tok int [B][R] -> (h, c,
+    log-softmax of the generator [B][R][C] with a NaN logit counting as -inf) -- _attn_search_host's arithmetic in its order"""
+    a = "attention_cell."
+    hp = h @ w[a + "h2h.weight"].T + w[a + "h2h.bias"]
+    e = np.tanh(Hproj[:, None] + hp[:, :, None, :]) @ w[a + "score.weight"][0]
+    e = np.exp(e - e.max(axis=2, keepdims=True))
+    alpha = e / e.sum(axis=2, keepdims=True)
+    ctx = np.einsum("bwt,btd->bwd", alpha, Hb)
+    g = (np.concatenate([ctx, w["char_embeddings.weight"][tok]], axis=2) @ w[a + "rnn.weight_ih"].T + w[a + "rnn.bias_ih"]
+         + h @ w[a + "rnn.weight_hh"].T + w[a + "rnn.bias_hh"])
+    gi, gf, gg, go = np.split(g, 4, axis=2)
+    c2 = _sigmoid(gf) * c + _sigmoid(gi) * np.tanh(gg)
+    h2 = _sigmoid(go) * np.tanh(c2)
+    x = h2 @ w["generator.weight"].T + w["generator.bias"]
+    x = np.where(np.isnan(x), -np.inf, x)
+    peak = x.max(axis=2, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lp = x - (peak + np.log(np.exp(x - peak).sum(axis=2, keepdims=True)))
+    return h2, c2, lp
+
+
+def rank_candidates(score_all, cand, n):
+    """score_all float [B][K] (-inf = dead), cand int [B][K] -> (index int32 [B][n], score [B][n], best slot int64 [B], -1 without a live
+    slot): descending score, a tie to the lower slot, dead slots last with index -1 and score -inf"""
+    B, K = score_all.shape
+    index = np.full((B, n), -1, dtype=np.int32)
+    score = np.full((B, n), -np.inf, dtype=score_all.dtype)
+    best = np.full(B, -1, dtype=np.int64)
+    order = np.argsort(-score_all, axis=1, kind="stable")[:, :n]
+    for b in range(B):
+        live = [q for q in order[b] if score_all[b, q] > -np.inf]
+        index[b, :len(live)] = cand[b, live]
+        score[b, :len(live)] = score_all[b, live]
+        if live:
+            best[b] = live[0]
+    return index, score, best
+
+
+def attn_candidates_host(sd, batch_H, sos, eos, lex_tokens, lex_len, cand, n, batch_max_length, want_logp=False):
+    """float64 exact scoring of per-sample candidate words on the attention head: sd = a state dict of modules/prediction.py Attention,
+    batch_H [B][T][D], the word table lex_tokens int [N][Lmax] / lex_len int [N], cand int [B][K] (-1 = unused slot), n entries per
+    sample -> (index int32 [B][n], score float64 [B][n], score_all float64 [B][K], path int64 [B][S], prob float32 [B][S]) and, with
+    want_logp, logp float64 [B][K][S]: the outputs of ops.attn_score_candidates, for CPU tensors and as the kernel's yardstick.  Any
+    K >= 1 and n >= 1"""
+    S, n = int(batch_max_length) + 1, int(n)
+    w = {k: _f64(v) for k, v in sd.items()}
+    Hb = _f64(batch_H)
+    if Hb.ndim != 3 or S < 1 or n < 1:
+        raise ValueError(f"attn_candidates_host needs batch_H [B][T][D], n >= 1 and batch_max_length >= 0, got {Hb.shape}, {n}, {S - 1}")
+    B, T, D = Hb.shape
+    C, Hd = w["generator.weight"].shape
+    if not 0 <= eos < C:
+        raise ValueError(f"eos={eos} outside the {C} classes")
+    tokens, lengths, cand = np.asarray(lex_tokens).astype(np.int64), np.asarray(lex_len).astype(np.int64), np.asarray(cand).astype(np.int64)
+    N, Lmax, K = check_word_table(tokens, lengths, cand, B, S)
+    tokens = np.where(np.arange(Lmax)[None, :] < lengths[:, None], tokens, 0)
+    spelled = (tokens < C).all(axis=1)                                     # a class this head does not have: the word is dead here
+    word = np.maximum(cand, 0)
+    live = (cand >= 0) & spelled[word]                                     # [B][K]
+    L = np.where(live, lengths[word], -1)
+    text = np.full((B, K, S), eos, dtype=np.int64)                         # the targets: the word's classes, then eos
+    text[:, :, :Lmax] = np.where(np.arange(Lmax)[None, None, :] < L[:, :, None], tokens[word], eos)[:, :, :S]
+    text[~live] = eos
+    first = int(sos)
+    first = 0 if first >= C or first < 0 else first
+    Hproj = Hb @ w["attention_cell.i2h.weight"].T
+    h, c = np.zeros((B, K, Hd)), np.zeros((B, K, Hd))
+    logp = np.zeros((B, K, S))
+    rows, slots = np.arange(B)[:, None], np.arange(K)[None, :]
+    for s in range(int(L.max()) + 1):
+        tok = np.full((B, K), first, dtype=np.int64) if s == 0 else text[:, :, s - 1]
+        h, c, lp = _attn_cell_host(w, Hb, Hproj, h, c, tok)
+        logp[:, :, s] = np.where(s <= L, lp[rows, slots, text[:, :, s]], 0.0)
+    with np.errstate(invalid="ignore"):
+        score_all = logp.sum(axis=2)
+    dead = ~live | np.isnan(score_all) | (score_all == -np.inf)
+    score_all[dead] = -np.inf
+    logp[dead] = 0.0
+    index, score, best = rank_candidates(score_all, cand, n)
+    path = np.full((B, S), eos, dtype=np.int64)
+    prob = np.zeros((B, S), dtype=np.float32)
+    has = best >= 0
+    path[has] = text[has, best[has]]
+    prob[has] = np.exp(logp[has, best[has]]).astype(np.float32)
+    out = (index, score, score_all, path, prob)
+    return out + (logp,) if want_logp else out
+
+
+def attn_candidates_request(attn_candidates, prediction, is_train, attn_beam=None):
+    """the candidate handle an evaluation forward scores its batch against, or None: attn_candidates is set, the head is an attention
+    head, the call is an evaluation under no_grad.  Together with a beam width the handle is an error: both replace greedy decoding"""
+    import torch
+    if attn_candidates is None:
+        return None
+    if attn_beam is not None:
+        raise ValueError("attn_candidates and attn_beam both replace the greedy pair of an evaluation forward: pass one of them")
+    if "Attn" not in prediction or is_train or torch.is_grad_enabled():
+        return None
+    return attn_candidates

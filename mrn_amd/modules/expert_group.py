@@ -752,10 +752,21 @@ class HeadsGroup(SequenceGroup):
         """beam search of all G attention experts in lock-step: ONE mrn_attn_beam_decode_* launch on run_greedy's features, Hproj and
         greedy_args() columns where every head takes the fused form; else every head's own Attention.beam_search (stepwise)
         -> (path int64 [G,B,S], prob [G,B,S]).  attn_lexicon (the handle of ops.upload_trie, one trie for all experts): the same with
-        mrn_attn_lexicon_decode_* / Attention.lexicon_search -> (path, prob, word int32 [G,B])"""
+        mrn_attn_lexicon_decode_* / Attention.lexicon_search -> (path, prob, word int32 [G,B]).  A candidate handle
+        (ops.upload_words(...).with_cand(...)) in its place, width None: every sample's candidate words scored exactly under all G
+        experts, mrn_attn_score_candidates_* / Attention.score_candidates -> (path, prob, word) of each expert's best word"""
         heads = [e.Prediction for e in self.experts]
         G, B, T, D = feat.shape
         L = self.experts[0].opt.batch_max_length
+        if isinstance(attn_lexicon, ops.CandidateHandle):
+            cands = attn_lexicon
+            if all(h.score_fused(D, T, L + 1, eos, cands.n) for h in heads):
+                res = ops.attn_score_candidates_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos,
+                                                        cands.tokens_dev, cands.lengths_dev, cands.cand_dev, n=cands.n,
+                                                        w_inv=cols[9] if cols[9][0] is not None else None, check=False)
+                return res[3], res[4], res[0][:, :, 0]
+            each = [h.score_candidates(feat[g], start, eos, cands, L) for g, h in enumerate(heads)]
+            return torch.stack([r[3] for r in each]), torch.stack([r[4] for r in each]), torch.stack([r[0][:, 0] for r in each])
         if attn_lexicon is not None:
             if all(h.lexicon_fused(D, T, L + 1, eos, width, attn_lexicon) for h in heads):
                 res = ops.attn_lexicon_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,

@@ -18,7 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
-from .decoding import ATTN_EOS, attn_beam_request, attn_lexicon_request
+from .decoding import ATTN_EOS, attn_beam_request, attn_candidates_request, attn_lexicon_request
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import check_call, frames
@@ -123,15 +123,20 @@ class Model(nn.Module):
             raise Exception("Prediction is neither CTC or Attn")
         self.Prediction.to(device)
 
-    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None):
-        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam, attn_lexicon=attn_lexicon)
+    def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None,
+                attn_candidates=None):
+        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam, attn_lexicon=attn_lexicon,
+                          attn_candidates=attn_candidates)
 
-    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None):
+    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None,
+              attn_candidates=None):
         """SequenceModeling + Prediction on precomputed backbone features.  attn_beam (a width; attention head, evaluation under
         no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of a beam search on the same features
         (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's.  attn_lexicon (the handle of
         ops.upload_trie, beside attn_beam): the search is walked along the lexicon's trie, and the dict also has beam_word [B], the
-        lexicon index of the best entry (-1: no word of the lexicon can be spelled)"""
+        lexicon index of the best entry (-1: no word of the lexicon can be spelled).  attn_candidates (the handle of
+        ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's candidate words are scored exactly
+        (Attention.score_candidates) and the same three keys hold the best word's pair and its table index"""
         feat = self.model.sequence(visual, out=feature_out)
         if self.stages["Pred"] == "CTC":
             if needs_grad(self.Prediction, feat):
@@ -143,7 +148,11 @@ class Model(nn.Module):
         out = {"predict": pred, "feature": feat}
         width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
         trie = attn_lexicon_request(attn_lexicon, attn_beam)
-        if width is not None and trie is not None:
+        cands = attn_candidates_request(attn_candidates, self.stages["Pred"], is_train, attn_beam)
+        if cands is not None:
+            res = self.Prediction.score_candidates(feat, text, ATTN_EOS, cands, self.opt.batch_max_length)
+            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
+        elif width is not None and trie is not None:
             res = self.Prediction.lexicon_search(feat, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
             out["beam_path"], out["beam_prob"], out["beam_word"] = res[4], res[5], res[6][:, 0]
         elif width is not None:
@@ -307,16 +316,21 @@ class DERNet(Model):
             return ops.linear(feat, head.weight, head.bias)
         return head(feat if feat.is_contiguous() else feat.contiguous(), text, is_train, batch_max_length=self.opt.batch_max_length)
 
-    def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None, attn_lexicon=None):
-        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon: as Model.heads (the main head's beam
-        pair and beam_word)"""
+    def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None, attn_lexicon=None, attn_candidates=None):
+        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon, attn_candidates: as Model.heads (the
+        main head's pair and beam_word)"""
         feat = self._features(image, frozen)
         logits = self._head(self.Prediction, feat, text, is_train)
         aux = self._head(self.aux_Prediction, feat[:, :, -self.out_dim:], text, is_train)
         out = {"logits": logits, "aux_logits": aux, "features": feat}
         width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
         trie = attn_lexicon_request(attn_lexicon, attn_beam)
-        if width is not None:
+        cands = attn_candidates_request(attn_candidates, self.stages["Pred"], is_train, attn_beam)
+        if cands is not None:
+            res = self.Prediction.score_candidates(feat if feat.is_contiguous() else feat.contiguous(), text, ATTN_EOS, cands,
+                                                   self.opt.batch_max_length)
+            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
+        elif width is not None:
             rows = feat if feat.is_contiguous() else feat.contiguous()
             if trie is not None:
                 res = self.Prediction.lexicon_search(rows, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
@@ -481,28 +495,31 @@ class MRNNet(nn.Module):
         else:
             hg.run(visual, text, feats, logits)
 
-    def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None, attn_lexicon=None):
+    def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None, attn_lexicon=None, attn_candidates=None):
         """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier.
         attn_beam (a width; attention experts, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of
         a beam search (modules/decoding.py) of the expert the hard routing index picks for each sample, for cross=False of the newest
         expert; one more launch per heads group on the same features, `logits` is still the greedy decoder's.  attn_lexicon (the handle
         of ops.upload_trie, beside attn_beam): the search of every expert is walked along the one trie, and the dict also has beam_word
-        [B], as Model.heads"""
+        [B], as Model.heads.  attn_candidates (the handle of ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's
+        candidate words are scored exactly under ALL experts in one grouped launch per heads group (a word with a class an expert lacks
+        is dead for that expert) and the same three keys hold the routed expert's best word"""
         check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
         width = attn_beam_request(attn_beam, self.opt.Prediction, is_train)
         trie = attn_lexicon_request(attn_lexicon, attn_beam)
         if width is None:                      # (a CTC head, training: the request is ignored like attn_beam)
             trie = None
+        cands = attn_candidates_request(attn_candidates, self.opt.Prediction, is_train, attn_beam)
         pair = None
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
-            newest = self.model[-1](image, text, is_train, attn_beam=width, attn_lexicon=trie)
+            newest = self.model[-1](image, text, is_train, attn_beam=width, attn_lexicon=trie, attn_candidates=cands)
             features, index = newest["predict"], None
-            if width is not None:
-                pair = (newest["beam_path"], newest["beam_prob"]) + ((newest["beam_word"],) if trie is not None else ())
+            if width is not None or cands is not None:
+                pair = (newest["beam_path"], newest["beam_prob"]) + ((newest["beam_word"],) if "beam_word" in newest else ())
         elif is_train == False:  # noqa: E712
-            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width, attn_lexicon=trie)
+            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width, attn_lexicon=trie, attn_candidates=cands)
             features, index = routed[:2]
-            if width is not None:
+            if width is not None or cands is not None:
                 pair = routed[2]
         else:
             features, index = self.cross_forward(image, text, is_train, experts=experts)
@@ -574,7 +591,7 @@ class MRNNet(nn.Module):
 
     def _experts_and_gate(self, image, text, is_train, experts=None, beam=None):
         """beam: None or (width, empty list, trie handle or None): the list takes (first expert, path [G,B,S], prob [G,B,S]) per heads
-        group / expert, with a trie also word [G,B]"""
+        group / expert, with a trie also word [G,B]; (None, empty list, candidate handle): the same three from the exact scorer"""
         I = len(self.model)
         B = image.shape[0]
         dev = image.device
@@ -631,7 +648,7 @@ class MRNNet(nn.Module):
                 for i, expert in enumerate(self.model):
                     streams[i].wait_stream(main)
                     with torch.cuda.stream(streams[i]):
-                        kw = {} if beam is None else {"attn_beam": beam[0], "attn_lexicon": beam[2]}
+                        kw = self._beam_kw(beam)
                         if visuals is None:
                             res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
                         else:
@@ -644,8 +661,7 @@ class MRNNet(nn.Module):
                     image.record_stream(st)
             else:
                 for i, expert in enumerate(self.model):
-                    res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i],
-                                 **({} if beam is None else {"attn_beam": beam[0], "attn_lexicon": beam[2]}))
+                    res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **self._beam_kw(beam))
                     if beam is not None:
                         beam[1].append(self._beam_part(i, res))
         r = self.dm_router[0].forward_l2(feats)               # [B,P,I,C]
@@ -662,16 +678,29 @@ class MRNNet(nn.Module):
         return FaninFn.apply(w, *logits), w
 
     @staticmethod
+    def _beam_kw(beam):
+        """the request of _experts_and_gate's `beam` as the keywords of an expert's own forward"""
+        if beam is None:
+            return {}
+        if isinstance(beam[2], ops.CandidateHandle):
+            return {"attn_candidates": beam[2]}
+        return {"attn_beam": beam[0], "attn_lexicon": beam[2]}
+
+    @staticmethod
     def _beam_part(i, res):
         """expert i's record for cross_forward_expert from its own forward's dict"""
         keys = ("beam_path", "beam_prob") + (("beam_word",) if "beam_word" in res else ())
         return (i,) + tuple(res[k].unsqueeze(0) for k in keys)
 
-    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None, attn_lexicon=None):
+    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None, attn_lexicon=None, attn_candidates=None):
         """-> (the routed expert's logits, the hard routing index); with attn_beam (a width) also the routed expert's beam pair
-        (path, prob) [B,S] as a third value, with attn_lexicon (a trie handle) beside it (path, prob, word [B])"""
+        (path, prob) [B,S] as a third value, with attn_lexicon (a trie handle) beside it, or with attn_candidates (a candidate handle)
+        instead of both, (path, prob, word [B])"""
         with torch.no_grad():
             beam = None if attn_beam is None else (attn_beam, [], attn_lexicon_request(attn_lexicon, attn_beam))
+            cands = attn_candidates_request(attn_candidates, self.opt.Prediction, is_train, attn_beam)
+            if cands is not None:
+                beam = (None, [], cands)
             logits, r = self._experts_and_gate(image, text, is_train, beam=beam)
             _, index = ops.gate_tail_fwd(r.contiguous(), self.route.weight.view(-1), self.route.bias, float(self.beta), hard=True)
             pair = None

@@ -163,6 +163,86 @@ class Attention(nn.Module):
                                            self.hidden_size, S, eos, W, trie_handle, w_inv=w_inv)
         return self._search_stepwise(batch_H, Hproj, start, eos, W, S, trie_handle)
 
+    def score_fused(self, D, T, S, eos, n):
+        """does score_candidates take the fused launch (mrn_attn_score_candidates_*): its limits, the LDS budget and MRN_ATTN_BEAM (read
+        per call: "stepwise" forces the step form of every search and scorer on the attention head)"""
+        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and 2 <= self.num_class <= 65535
+                and 0 <= eos < self.num_class and 1 <= n <= 16 and ops.attn_score_whole_context(D, T, self.x3_ok()))
+
+    SCORE_ROWS_BYTES = 256 << 20      # the stepwise scorer's (sample, slot) rows go in chunks whose features and logits stay within this
+
+    @torch.no_grad()
+    def score_candidates(self, batch_H, sos, eos, handle, batch_max_length=25, want_logp=False):
+        """exact log p(word, eos | sample) of every sample's candidate words (modules/decoding.py states the algorithm): batch_H
+        [B,T,D], sos as in beam_search, handle = ops.upload_words(...).with_cand(cand [B,K], S) -> (index int32 [B,n], score [B,n],
+        score_all [B,K], path int64 [B,S], prob [B,S]) and, with want_logp, logp [B,K,S].  One launch where the kernel's limits and
+        the LDS budget allow, otherwise (or under MRN_ATTN_BEAM=stepwise) the teacher-forced decoder on the (sample, slot) rows;
+        CPU tensors go to decoding.attn_candidates_host.  Inference only (no_grad)"""
+        from .decoding import attn_candidates_host
+        check_hidden(None, "Attn", self.hidden_size)
+        S, eos = int(batch_max_length) + 1, int(eos)
+        if not isinstance(handle, ops.CandidateHandle) or handle.cand is None:
+            raise ValueError(f"score_candidates needs the handle of ops.upload_words(...).with_cand(...), got {type(handle).__name__}")
+        if not 0 <= eos < self.num_class:
+            raise ValueError(f"score_candidates needs 0 <= eos < {self.num_class}, got {eos}")
+        B, T, D = batch_H.shape
+        if handle.cand.shape[0] != B:
+            raise ValueError(f"score_candidates: {handle.cand.shape[0]} candidate rows for {B} samples")
+        if not batch_H.is_cuda:
+            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
+            res = attn_candidates_host(self.state_dict(), batch_H, first, eos, handle.tokens, handle.lengths, handle.cand, handle.n, S - 1,
+                                       want_logp=want_logp)
+            return tuple(torch.from_numpy(r).to(torch.float32) if r.dtype == "float64" else torch.from_numpy(r) for r in res)
+        cell = self.attention_cell
+        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
+        batch_H = batch_H.contiguous()
+        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        tokens, lengths, cand = handle.tokens_dev, handle.lengths_dev, handle.cand_dev
+        if self.score_fused(D, T, S, eos, handle.n):
+            etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+            return ops.attn_score_candidates(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                             self.hidden_size, S, eos, tokens, lengths, cand, n=handle.n, want_logp=want_logp,
+                                             w_inv=w_inv, check=False)
+        score_all, logp = self._score_stepwise(batch_H, Hproj, start, eos, tokens, lengths, cand, S)
+        index, score, path, prob = (r[0] for r in ops.rank_candidates(score_all.unsqueeze(0), logp.unsqueeze(0), tokens, lengths, cand,
+                                                                      handle.n, eos))
+        out = (index, score, score_all, path, prob)
+        return out + (logp,) if want_logp else out
+
+    def _score_stepwise(self, batch_H, Hproj, start, eos, tokens, lengths, cand, S):
+        """score_candidates outside the fused launch: the teacher-forced decoder and the generator on chunks of the B * K (sample,
+        slot) rows, log-softmax and gather in torch -> (score_all [B,K], logp [B,K,S])"""
+        cell = self.attention_cell
+        B, T, D = batch_H.shape
+        K, C, dev = cand.shape[1], self.num_class, batch_H.device
+        neg = torch.tensor(float("-inf"), device=dev)
+        Lmax = tokens.shape[1]
+        used = torch.arange(Lmax, device=dev).unsqueeze(0) < lengths.unsqueeze(1)
+        spelled = ((tokens < C) | ~used).all(dim=1)
+        word = cand.long().clamp(min=0)
+        live = (cand >= 0) & spelled[word]
+        L = torch.where(live, lengths.long()[word], -1)                                  # [B,K]
+        cols = min(Lmax, S)
+        target = torch.full((B, K, S), eos, dtype=torch.int64, device=dev)              # the word's classes, then eos
+        target[:, :, :cols] = torch.where(torch.arange(cols, device=dev) < L.unsqueeze(2), tokens.long()[word][:, :, :cols], eos)
+        fed = torch.cat([start.expand(B * K, 1), target.view(B * K, S)[:, :S - 1]], dim=1)
+        w_emb = cell.rnn.weight_ih[:, D:]
+        logp = torch.empty(B * K, S, device=dev)
+        chunk = max(1, self.SCORE_ROWS_BYTES // (4 * (T * (D + self.hidden_size) + S * (C + 5 * self.hidden_size))))
+        for r0 in range(0, B * K, chunk):
+            r1 = min(B * K, r0 + chunk)
+            b = torch.arange(r0, r1, device=dev) // K
+            emb = ops.embed_gather(fed[r0:r1].contiguous(), self.char_embeddings.weight, C)
+            eproj = ops.linear(emb, w_emb, cell.rnn.bias_ih)
+            hid = self._decode(batch_H[b], Hproj[b], eproj)
+            x = ops.linear(hid, self.generator.weight, self.generator.bias)
+            lp = torch.log_softmax(torch.where(torch.isnan(x), neg, x), dim=2)
+            logp[r0:r1] = lp.gather(2, target.view(B * K, S)[r0:r1].unsqueeze(2)).squeeze(2)
+        logp = torch.where(torch.arange(S, device=dev) <= L.unsqueeze(2), logp.view(B, K, S), torch.zeros((), device=dev))
+        score_all = logp.sum(dim=2)
+        dead = ~live | torch.isnan(score_all) | (score_all == float("-inf"))
+        return torch.where(dead, neg, score_all), torch.where(dead.unsqueeze(2), torch.zeros((), device=dev), logp)
+
     @staticmethod
     def _admitted(trie, node, C, eos):
         """node int64 [B * W] -> (admitted bool [B * W, C], step_to int64 [B * W, C]): the classes the rows' nodes admit and the node

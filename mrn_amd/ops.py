@@ -1636,6 +1636,148 @@ def attn_lexicon_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_h
     return tuple(r[0] for r in res)
 
 
+ATTN_SCORE_LDS_EXTRA = 4 * (5 * 16 + 2 * 16 * 16)      # attn_score_kernel: five 16-row state arrays + 16 x 16 (max, sum) pairs
+
+
+def attn_score_whole_context(D, T, x3=None):
+    """does the fused candidate scorer (csrc/attn_decode.hip score_launch / score_grouped) take D context columns and T frames: the
+    whole-context tile of attn_greedy_whole_context with ATTN_SCORE_LDS_EXTRA bytes in place of the arg-max pairs within 160 KiB (the 16
+    rows are samples x slots, so the tile does not grow with K), D a multiple of 16 (32 in the x3 form).  There is no chunked form:
+    what does not fit is scored stepwise (Attention.score_candidates)"""
+    x3 = DECODER_X3 if x3 is None else x3
+    return D > 0 and D % (32 if x3 else 16) == 0 and _attn_tile_lds(D, T, x3, ATTN_SCORE_LDS_EXTRA) <= 160 * 1024
+
+
+def _check_word_tensors(lex_tokens, lex_len, cand, B, S):
+    """decoding.check_word_table on device tensors: one reduction and one read-back, before any launch of the scorer"""
+    for t, nd in ((lex_tokens, 2), (lex_len, 1), (cand, 2)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != nd or not t.is_contiguous():
+            raise ValueError("attn_score_candidates needs contiguous int32 tensors: tokens [N,Lmax], lengths [N], cand [B,K]")
+    N, Lmax = lex_tokens.shape
+    if N < 1 or N > (1 << 20) or lex_len.shape[0] != N:
+        raise ValueError(f"attn_score_candidates: a word table needs tokens [1 <= N <= 2^20, Lmax] and lengths [N], got "
+                         f"{tuple(lex_tokens.shape)}, {tuple(lex_len.shape)}")
+    if cand.shape[0] != B or cand.shape[1] < 1:
+        raise ValueError(f"attn_score_candidates: a candidate table needs cand [B = {B}, K >= 1], got {tuple(cand.shape)}")
+    used = torch.arange(Lmax, device=lex_len.device).unsqueeze(0) < lex_len.unsqueeze(1)
+    bad = torch.stack([((lex_len < 0) | (lex_len > min(Lmax, S - 1))).any(), ((lex_tokens < 0) & used).any(),
+                       ((cand < -1) | (cand > N - 1)).any()]).tolist()
+    if bad[0]:
+        raise ValueError(f"attn_score_candidates: a word length outside 0..{min(Lmax, S - 1)} (the longest word and its end token take "
+                         f"S = {S} steps)")
+    if bad[1]:
+        raise ValueError("attn_score_candidates: a negative class in a word")
+    if bad[2]:
+        raise ValueError(f"attn_score_candidates: a candidate index outside -1..{N - 1}")
+
+
+def rank_candidates(score_all, logp, lex_tokens, lex_len, cand, n, eos):
+    """the selection behind the scorer, on the device: score_all [G,B,K] (-inf = dead), logp [G,B,K,S] -> (index int32 [G,B,n], score
+    [G,B,n], path int64 [G,B,S], prob [G,B,S]) -- descending score, a tie to the lower slot, dead slots last (index -1, score -inf); the
+    best entry's classes then eos and its per-token probabilities, 1 behind its eos; path all eos and prob all 0 without a live slot
+    (modules/decoding.py rank_candidates on the host)"""
+    G, B, K = score_all.shape
+    S = logp.shape[3]
+    val, slot = torch.sort(score_all, dim=2, descending=True, stable=True)
+    val, slot = val[:, :, :n], slot[:, :, :n]
+    live = val > float("-inf")
+    words = cand.long().unsqueeze(0).expand(G, B, K)
+    index = torch.where(live, words.gather(2, slot), -1).to(torch.int32)
+    if K < n:
+        index = torch.cat([index, index.new_full((G, B, n - K), -1)], dim=2)
+        val = torch.cat([val, val.new_full((G, B, n - K), float("-inf"))], dim=2)
+    best, has = slot[:, :, 0], live[:, :, 0]
+    word = words.gather(2, best.unsqueeze(2)).squeeze(2).clamp(min=0)                 # [G,B]
+    cols = min(lex_tokens.shape[1], S)
+    path = torch.full((G, B, S), int(eos), dtype=torch.int64, device=score_all.device)
+    inside = torch.arange(cols, device=path.device) < lex_len.long()[word].unsqueeze(2)
+    path[:, :, :cols] = torch.where(inside & has.unsqueeze(2), lex_tokens.long()[word][:, :, :cols], int(eos))
+    prob = torch.exp(logp.gather(2, best.view(G, B, 1, 1).expand(G, B, 1, S)).squeeze(2))
+    prob = torch.where(has.unsqueeze(2), prob, torch.zeros_like(prob))
+    return index, val, path, prob
+
+
+def attn_score_candidates_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos,
+                                  lex_tokens, lex_len, cand, n=1, want_logp=False, w_inv=None, check=True):
+    """exact scoring of per-sample candidate words on the attention head for G experts of one geometry in one launch (per eight
+    experts; include/mrn_attn_score.h): the operands of attn_greedy_decode_grouped, the end token, the word table lex_tokens int32
+    [N,Lmax] / lex_len int32 [N] and cand int32 [B,K] (-1 = unused slot), shared by the experts -> (index int32 [G,B,n], score fp32
+    [G,B,n], score_all fp32 [G,B,K], path int64 [G,B,S], prob fp32 [G,B,S]) and, with want_logp, logp fp32 [G,B,K,S]
+    (modules/decoding.py).  A word with a class an expert lacks is dead for that expert.  Out-of-range lengths, classes or candidates
+    and a table without slots are ValueErrors before any launch (check=False: the caller has run decoding.check_word_table on the host
+    arrays).  The limits are the caller's to keep (attn_score_whole_context, S <= 512, 2 <= classes <= 65535, N <= 2^20, n <= 16,
+    hidden 256): outside them the call is an error"""
+    import ctypes
+    from .modules.decoding import CANDIDATES_MAX_TOP_N
+    _chk(Hb, Hproj)
+    G, B, T, D = Hb.shape
+    S, n = int(S), int(n)
+    assert Hb.is_contiguous() and Hproj.is_contiguous() and start.dtype == torch.int64 and start.is_cuda
+    if not 1 <= n <= CANDIDATES_MAX_TOP_N:
+        raise ValueError(f"attn_score_candidates: n={n} entries outside 1..{CANDIDATES_MAX_TOP_N}")
+    dev = Hb.device
+    for t in (lex_tokens, lex_len, cand):
+        if not torch.is_tensor(t) or t.device != dev:
+            raise ValueError("attn_score_candidates needs the word table and the candidate table on the device of the features")
+    if check:
+        _check_word_tensors(lex_tokens, lex_len, cand, B, S)
+    classes = [int(b.shape[0]) for b in b_gen]
+    for g in range(G):
+        assert etab[g].shape[0] == classes[g] and etab[g].is_contiguous() and w_gen[g].is_contiguous()
+        assert w_gen[g].shape[0] == (classes[g] + 15) // 16 and b_gen[g].is_contiguous()
+    N, Lmax = lex_tokens.shape
+    K = cand.shape[1]
+    score_all = torch.empty(G, B, K, device=dev, dtype=torch.float32)
+    logp = torch.empty(G, B, K, max(S, 0), device=dev, dtype=torch.float32)     # (the best entry's probabilities come from it: always written)
+    _x3_call("attn_score_candidates", True, w_inv, _decode_operands(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh),
+             (_ptrs(b_hh), _ptrs(w_gen), _ptrs(b_gen), (ctypes.c_int * G)(*classes), int(eos), _p(lex_tokens) if Lmax else None, Lmax,
+              _p(lex_len), N, _p(cand), K, _ptrs(score_all), _ptrs(logp), G, B, T, D, S, hidden, _stream()))
+    index, score, path, prob = rank_candidates(score_all, logp, lex_tokens, lex_len, cand, n, eos)
+    out = (index, score, score_all, path, prob)
+    return out + (logp,) if want_logp else out
+
+
+def attn_score_candidates(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, lex_tokens,
+                          lex_len, cand, n=1, want_logp=False, w_inv=None, check=True):
+    """attn_score_candidates_grouped for one expert (G = 1): Hb [B,T,D], Hproj [B,T,H], the operands of attn_greedy_decode -> the
+    outputs without the expert dimension"""
+    res = attn_score_candidates_grouped(Hb.unsqueeze(0), Hproj.unsqueeze(0), [etab], start, [w_h2h], [b_h2h], [w_score], [w_ih], [w_hh],
+                                        [b_hh], [w_gen], [b_gen], hidden, S, eos, lex_tokens, lex_len, cand, n=n, want_logp=want_logp,
+                                        w_inv=None if w_inv is None else [w_inv], check=check)
+    return tuple(r[0] for r in res)
+
+
+class CandidateHandle:
+    """what an evaluation forward scores its batch against (attn_candidates=): the word table of a validation() call, checked on the
+    host and uploaded once (upload_words), the batch's cand int32 [B,K] (with_cand) and n, the entries ranked per sample"""
+
+    def __init__(self, tokens, lengths, device, n=1):
+        import numpy as np
+        self.tokens, self.lengths = np.ascontiguousarray(tokens, dtype=np.int32), np.ascontiguousarray(lengths, dtype=np.int32)
+        self.device, self.n = torch.device(device), int(n)
+        self.cand = self.cand_dev = self.tokens_dev = self.lengths_dev = None
+
+    def with_cand(self, cand, S):
+        """the handle for one batch: cand [B,K] (numpy) is checked against the table on the host (decoding.check_word_table) and
+        uploaded; the table goes up with the first batch"""
+        import copy
+        import numpy as np
+        from .modules.decoding import check_word_table
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        check_word_table(self.tokens, self.lengths, cand, cand.shape[0], S)
+        if self.tokens_dev is None:
+            pad = self.tokens if self.tokens.shape[1] else np.zeros((len(self.lengths), 1), dtype=np.int32)
+            self.tokens_dev, self.lengths_dev = torch.from_numpy(pad).to(self.device), torch.from_numpy(self.lengths).to(self.device)
+        batch = copy.copy(self)
+        batch.cand, batch.cand_dev = cand, torch.from_numpy(cand).to(self.device)
+        return batch
+
+
+def upload_words(tokens, lengths, device, n=1):
+    """a word table (decoding.encode_attn_lexicon: tokens int32 [N,Lmax], lengths int32 [N]) -> CandidateHandle on `device`"""
+    return CandidateHandle(tokens, lengths, device, n)
+
+
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):
     """(h2h.weight [H,H], rnn.weight_ih [4H, D+E], rnn.weight_hh [4H,H]) -> (three pack_fragment_major_h streams, w_inv float[3])"""
     a, b, c = pack_fragment_major_h(w_h2h.detach()), pack_fragment_major_h(w_ih.detach()[:, :D].contiguous()), pack_fragment_major_h(w_hh.detach())

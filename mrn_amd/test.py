@@ -45,6 +45,16 @@ batch_max_length characters are encoded, the trie built, checked and uploaded on
 constrained beam pair (attn_beam=width, attn_lexicon=handle: one more launch per heads group, one trie for all experts) and the pair
 goes to the unchanged scorer as in beam mode: the confidence is the product of the kept tokens' probabilities, the loss is still the
 greedy logits'.  A sample none of whose words the routed expert can spell scores as an empty prediction with confidence 0.
+
+opt.candidates (absent or None: as above, bit for bit) gives every image a word list of its own, the protocol of IIIT5K-50, SVT-50 and
+IC03-50: a callable that takes the batch's list of label strings and returns one sequence of words per sample, or a dict label ->
+words (a label without an entry is an error).  Nothing relies on the order of the loader.  The word table is the union of the lists,
+encoded once per call by the head's lexicon encoder (words the converter cannot spell are dropped; for a callable the loader's labels
+are read once more before the first batch), the candidate table cand [B, K] is built per batch.  A CTC head takes
+ops.ctc_lexicon_decode(cand=) or its host form; an attention head scores every (sample, word) pair exactly (attn_candidates=handle on
+the evaluation forward: one more launch per heads group, modules/decoding.py), so the best word is the arg-max of log p(word, [EOS] |
+image) over the list whatever a beam width would have been.  opt.lexicon_top_n entries are ranked, the best one is scored, by the
+unchanged scorer.  Together with lexicon, attn_lexicon, ctc_decode = "beam" or attn_decode = "beam" the option is an error.
 """
 import time
 
@@ -72,10 +82,11 @@ def edit_distance(a, b):
     return prev[-1]
 
 
-def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None):
+def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None):
     """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
     attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits; attn_lexicon (a
-    trie handle beside it): the pair of the lexicon-constrained search"""
+    trie handle beside it): the pair of the lexicon-constrained search; attn_candidates (a candidate handle instead of both): the pair
+    of the batch's exact candidate scoring"""
     if "CTC" in opt.Prediction:
         if val_choose == "FF":
             out = model(image, cross=False, is_train=False)
@@ -88,6 +99,8 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
         kw = {} if attn_beam is None else {"attn_beam": attn_beam}
         if attn_lexicon is not None:
             kw["attn_lexicon"] = attn_lexicon
+        if attn_candidates is not None:
+            kw["attn_candidates"] = attn_candidates
         if val_choose == "FF":
             out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
@@ -95,10 +108,11 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
         else:
             out = model(image, text=sos, is_train=False, **kw)
     logits = out["logits"] if "logits" in out else out["predict"]
-    if attn_beam is None:
+    if attn_beam is None and attn_candidates is None:
         return logits
     if "beam_path" not in out:
-        raise RuntimeError("attn_decode='beam': the evaluation forward returned no beam pair (it runs under torch.no_grad() only)")
+        what = "attn_decode='beam'" if attn_candidates is None else "candidates"
+        raise RuntimeError(f"{what}: the evaluation forward returned no beam pair (it runs under torch.no_grad() only)")
     return logits, (out["beam_path"], out["beam_prob"])
 
 
@@ -196,6 +210,40 @@ class _AttnLexicon:
         return self.handle
 
 
+class _Candidates:
+    """opt.candidates: the union of the word lists encoded once per validation() call, the candidate table built per batch"""
+
+    def __init__(self, converter, candidates, loader, attn, batch_max_length, n):
+        self.candidates, self.attn, self.n, self.S = candidates, attn, n, batch_max_length + 1
+        if isinstance(candidates, dict):
+            lists = D.candidate_lists(candidates, list(candidates))
+        else:                               # the union is over the loader's labels, whatever order they come in
+            lists = [words for _, labels in loader for words in D.candidate_lists(candidates, labels)]
+        self.table = D.CandidateTable(converter, lists, attn, batch_max_length)
+        self.device = self.handle = None
+
+    def cand(self, labels):
+        return self.table.rows(D.candidate_lists(self.candidates, labels))
+
+    def on(self, device, labels):
+        """attention head: the handle of the evaluation forward for this batch"""
+        if self.handle is None:
+            self.handle = ops.upload_words(self.table.tokens, self.table.lengths, device, self.n)
+        return self.handle.with_cand(self.cand(labels), self.S)
+
+    def pair(self, preds, prediction, labels):
+        """CTC head: the lexicon decoder's (path, prob) for logits [B,T,C] against the batch's candidate table, on the device of
+        `preds`: the kernel when it takes the batch, else the host form"""
+        cand, t = self.cand(labels), self.table
+        if preds.is_cuda and D.lexicon_supported(prediction, preds.size(1), preds.size(2), int(t.lengths.max()), len(t.lengths), self.n):
+            if self.device is None:
+                self.device = (torch.from_numpy(t.tokens).to(preds.device), torch.from_numpy(t.lengths).to(preds.device))
+            return ops.ctc_lexicon_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), *self.device, n=self.n,
+                                          cand=torch.from_numpy(cand).to(preds.device))[3:]
+        path, prob = D.ctc_lexicon_host(preds.detach().cpu().numpy(), t.tokens, t.lengths, self.n, cand)[3:]
+        return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
+
+
 def validation(model, criterion, evaluation_loader, converter, opt, val_choose="val", tqdm_position=1):
     n_correct, norm_ED, length_of_data, infer_time = 0, 0.0, 0, 0.0
     loss_sum, loss_n = 0.0, 0
@@ -215,8 +263,12 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     if lexicon_words is not None and not attn and ctc_decode == "beam":
         raise ValueError("lexicon and ctc_decode='beam' both replace best-path decoding on a CTC head: set one of them")
     lexicon = _Lexicon(converter, lexicon_words, lexicon_n) if lexicon_words is not None and not attn else None
-    if attn_beam is not None and converter.dict["[EOS]"] != D.ATTN_EOS:
-        what = "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'"
+    cand_fn, cand_n = D.candidates_options(opt)
+    candidates = None
+    if cand_fn is not None:
+        candidates = _Candidates(converter, cand_fn, evaluation_loader, attn, opt.batch_max_length, cand_n)
+    if (attn_beam is not None or (attn and candidates is not None)) and converter.dict["[EOS]"] != D.ATTN_EOS:
+        what = "candidates" if candidates is not None else "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'"
         raise ValueError(f"{what} ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
@@ -226,9 +278,10 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         if image.is_cuda:
             torch.cuda.synchronize()                 # the launches are asynchronous: infer_time is forward time, not host issue time
         start = time.time()
+        attn_cands = candidates.on(image.device, labels) if attn and candidates is not None else None
         preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam,
-                         attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device))
-        if attn_beam is not None:
+                         attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device), attn_candidates=attn_cands)
+        if attn_beam is not None or attn_cands is not None:
             preds, beam_pair = preds
         if image.is_cuda:
             torch.cuda.synchronize()
@@ -243,11 +296,13 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         loss_n += 1
         if SCORE_TIMER is not None:
             t_score = time.perf_counter()
-        if lexicon is not None:
+        if candidates is not None and not attn:
+            preds_index, preds_max_prob = candidates.pair(preds, opt.Prediction, labels)
+        elif lexicon is not None:
             preds_index, preds_max_prob = lexicon.pair(preds, opt.Prediction)
         elif ctc_decode == "beam" and not attn:
             preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
-        elif attn_beam is not None:
+        elif attn_beam is not None or attn_cands is not None:
             preds_index, preds_max_prob = beam_pair
         else:
             preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                     # :211, :218-219
