@@ -1,7 +1,7 @@
 """ctypes binding of libmrn_hip.so.
 
 Signatures are parsed from include/mrn_hip.h, include/mrn_decode.h, include/mrn_attn_beam.h, include/mrn_lexicon.h,
-include/mrn_attn_lexicon.h and include/mrn_attn_score.h, so the headers are
+include/mrn_attn_lexicon.h, include/mrn_attn_score.h and include/mrn_shortlist.h, so the headers are
 the single source of truth for the C ABI.
 There is no CPU fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -21,6 +21,7 @@ ATTN_BEAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_att
 LEXICON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_lexicon.h")     # lexicon-constrained decoding
 ATTN_LEXICON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_attn_lexicon.h")     # the same on the attention head
 ATTN_SCORE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_attn_score.h")     # exact scoring of per-sample candidate words
+SHORTLIST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_shortlist.h")     # lexicon shortlists by edit distance
 
 _CTYPES = {
     "int": ctypes.c_int,
@@ -77,7 +78,7 @@ class _Lib:
         dll = ctypes.CDLL(LIB_PATH)
         self._protos = {**parse_header(), **parse_header(DECODE_HEADER_PATH), **parse_header(ATTN_BEAM_HEADER_PATH),
                         **parse_header(LEXICON_HEADER_PATH), **parse_header(ATTN_LEXICON_HEADER_PATH),
-                        **parse_header(ATTN_SCORE_HEADER_PATH)}
+                        **parse_header(ATTN_SCORE_HEADER_PATH), **parse_header(SHORTLIST_HEADER_PATH)}
         for name, (ret, argtypes, _) in self._protos.items():
             fn = getattr(dll, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = _CTYPES[ret]

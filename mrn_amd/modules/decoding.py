@@ -825,3 +825,149 @@ def attn_candidates_request(attn_candidates, prediction, is_train, attn_beam=Non
     if "Attn" not in prediction or is_train or torch.is_grad_enabled():
         return None
     return attn_candidates
+
+
+# ---- lexicon shortlists by edit distance ---------------------------------------------------------------------------------------------
+# With opt.lexicon_shortlist = K a large shared lexicon (opt.lexicon on a CTC head, opt.attn_lexicon on the attention head) is decoded
+# by the lexicon protocol of the CRNN paper (Shi et al., section 3.3): take the lexicon-free transcription, keep the K words nearest
+# to it by edit distance, choose among those by the model's probability.  The first step is the greedy decode the forward already
+# runs, the last the exact candidate scoring above (ctc_lexicon_host / attn_candidates_host and their kernels on a table cand [B][K]);
+# the middle one is mrn_lexicon_shortlist_i32 (mrn_amd/csrc/lexicon_shortlist.hip), restated in numpy by lexicon_shortlist_host
+# below.  For sample b with the hypothesis hyp[b][:n_b], n_b = hyp_len[b] clipped to 0 .. Hmax, and word w with the classes
+# lex_tokens[w][:lex_len[w]]:
+#
+#   d(b, w) = the Levenshtein distance with unit costs over class tokens (mrn_amd/test.py edit_distance on the two token rows);
+#   the words with max_dist None or d <= max_dist are ranked by (d, w) ascending: a tie goes to the lower word index;
+#   the first K go to cand[b] (word indices) and dist[b] (their distances), in that order; unused slots are -1 in both, the value
+#   ctc_lexicon_host(cand=) and CandidateHandle.with_cand take for an unused slot.
+#
+# Duplicate words are distinct indices and are all kept, as the encoders keep them.  Everything is integer arithmetic: the kernel's
+# result is the host form's, element for element.  The kernel holds a hypothesis as one 64-bit word of Myers' bit-vector algorithm: a
+# sample with more than 64 tokens is flagged and finished by the host form (ops.lexicon_shortlist merges the rows).  The shortlist only
+# orders the candidates: with K >= N and no cut-off nothing is lost and the best word is the exact arg-max over the lexicon.  A sample
+# whose shortlist is empty (every word beyond max_dist) has no live slot and gets the empty prediction with confidence 0.
+SHORTLIST_MAX_K = 256
+SHORTLIST_MAX_WORDS = 1 << 20
+SHORTLIST_MAX_LENGTH = 255        # a distance is at most max(64, 255) and is kept as a byte between the two launches
+SHORTLIST_MAX_HYPOTHESIS = 64
+SHORTLIST_MAX_CLASS = 65534
+
+
+def shortlist_options(opt):
+    """(K or None, max_dist or None) of an options object: opt.lexicon_shortlist is absent / None (off) or an integer >= 1, the words
+    kept per sample; opt.lexicon_max_distance is absent / None (no cut-off) or an integer >= 0"""
+    K = getattr(opt, "lexicon_shortlist", None)
+    if K is not None:
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+            raise ValueError(f"lexicon_shortlist must be an integer >= 1 (or None), got {K!r}")
+        K = int(K)
+    max_dist = getattr(opt, "lexicon_max_distance", None)
+    if max_dist is not None:
+        if isinstance(max_dist, bool) or not isinstance(max_dist, (int, np.integer)) or max_dist < 0:
+            raise ValueError(f"lexicon_max_distance must be an integer >= 0 (or None), got {max_dist!r}")
+        max_dist = int(max_dist)
+    return K, max_dist
+
+
+def shortlist_request(opt, attn):
+    """(K, max_dist) of validation() on an attention (attn) or CTC head, or None with the option off.  The shortlist is taken from the
+    head's own lexicon option (attn_lexicon / lexicon; the other head's is ignored, as without a shortlist): without it the option is a
+    ValueError, and so it is together with candidates, which names every sample's words itself"""
+    K, max_dist = shortlist_options(opt)
+    if K is None:
+        return None
+    if getattr(opt, "candidates", None) is not None:
+        raise ValueError("lexicon_shortlist and candidates both choose the words a sample is scored against: set one of them")
+    key = "attn_lexicon" if attn else "lexicon"
+    if getattr(opt, key, None) is None:
+        raise ValueError(f"lexicon_shortlist={K} shortlists the words of {key}, which is not set "
+                         f"(a{'n attention' if attn else ' CTC'} head reads {key})")
+    return K, max_dist
+
+
+def shortlist_supported(Lmax, N, K, max_class):
+    """does mrn_lexicon_shortlist_i32 take a table of N words of at most Lmax classes, the largest of them max_class, and K slots"""
+    return (1 <= K <= SHORTLIST_MAX_K and 1 <= N <= SHORTLIST_MAX_WORDS and 1 <= Lmax <= SHORTLIST_MAX_LENGTH
+            and 0 <= max_class <= SHORTLIST_MAX_CLASS)
+
+
+def lexicon_shortlist_host(hyp, hyp_len, lex_tokens, lex_len, K, max_dist=None):
+    """the K nearest words of every sample in numpy: hyp int [B][Hmax], hyp_len int [B] (clipped to 0 .. Hmax), the word table
+    lex_tokens int [N][Lmax] / lex_len int [N] -> (cand int32 [B][K], dist int32 [B][K]), -1 in unused slots: the outputs of
+    ops.lexicon_shortlist, for CPU tensors, for tables outside the kernel's limits and for the samples it flags.  Any hypothesis
+    length, any K >= 1.  One Levenshtein row per hypothesis token over all words at once: the row's left-to-right minimum is a
+    running minimum of (value - column)"""
+    hyp, hyp_len = np.asarray(hyp).astype(np.int64), np.asarray(hyp_len).astype(np.int64)
+    tokens, lengths = np.asarray(lex_tokens).astype(np.int64), np.asarray(lex_len).astype(np.int64)
+    K = int(K)
+    if hyp.ndim != 2 or hyp_len.shape != hyp.shape[:1] or K < 1:
+        raise ValueError(f"lexicon_shortlist_host needs hyp [B][Hmax], hyp_len [B] and K >= 1, got {hyp.shape}, {hyp_len.shape}, {K}")
+    if tokens.ndim != 2 or lengths.shape != tokens.shape[:1] or len(lengths) < 1:
+        raise ValueError(f"lexicon_shortlist_host needs tokens [N >= 1][Lmax] and lengths [N], got {tokens.shape}, {lengths.shape}")
+    if max_dist is not None and max_dist < 0:
+        raise ValueError(f"lexicon_shortlist_host: max_dist={max_dist} must be >= 0 or None")
+    B, Hmax = hyp.shape
+    N, Lmax = tokens.shape
+    if lengths.min() < 0 or lengths.max() > Lmax:
+        raise ValueError(f"lexicon_shortlist_host: word lengths outside 0..{Lmax}")
+    cols = np.arange(Lmax + 1)
+    words = np.arange(N)
+    cand = np.full((B, K), -1, dtype=np.int32)
+    dist = np.full((B, K), -1, dtype=np.int32)
+    for b in range(B):
+        row = np.broadcast_to(cols, (N, Lmax + 1))                       # D[0][j] = j
+        for i in range(int(min(max(hyp_len[b], 0), Hmax))):
+            new = np.empty((N, Lmax + 1), dtype=np.int64)
+            new[:, 0] = i + 1
+            new[:, 1:] = np.minimum(row[:, 1:] + 1, row[:, :-1] + (tokens != hyp[b, i]))
+            row = np.minimum.accumulate(new - cols, axis=1) + cols        # D[i][j] = min over k <= j of new[k] + (j - k)
+        d = row[words, lengths]
+        kept = words if max_dist is None else np.flatnonzero(d <= max_dist)
+        order = kept[np.argsort(d[kept], kind="stable")][:K]
+        cand[b, :len(order)] = order
+        dist[b, :len(order)] = d[order]
+    return cand, dist
+
+
+def hypothesis_of_path(path, eos):
+    """attention head: the greedy tokens path int [B][S] -> (hyp int32 [B][S], hyp_len int32 [B]): the tokens before the first eos
+    (all S where there is none); numpy"""
+    path = np.asarray(path)
+    is_eos = path == eos
+    n = np.where(is_eos.any(axis=1), is_eos.argmax(axis=1), path.shape[1])
+    return path.astype(np.int32), n.astype(np.int32)
+
+
+def hypothesis_of_frames(index):
+    """CTC head: the per-frame arg-max index int [B][T] -> (hyp int32 [B][T], hyp_len int32 [B]): the best path collapsed (repeats of
+    the raw index merged, blanks dropped), front-packed, 0 behind; numpy"""
+    index = np.asarray(index)
+    B, T = index.shape
+    keep = index != 0
+    keep[:, 1:] &= index[:, 1:] != index[:, :-1]
+    hyp = np.zeros((B, T), dtype=np.int32)
+    for b in range(B):
+        row = index[b, keep[b]]
+        hyp[b, :len(row)] = row
+    return hyp, keep.sum(axis=1).astype(np.int32)
+
+
+def attn_shortlist_request(attn_shortlist, prediction, is_train, attn_beam=None, attn_candidates=None):
+    """the (handle, K, max_dist) an evaluation forward shortlists and scores its batch with, or None: attn_shortlist is set, the head is
+    an attention head, the call is an evaluation under no_grad.  Together with a beam width or a candidate handle it is an error: all
+    three replace greedy decoding"""
+    import torch
+    if attn_shortlist is None:
+        return None
+    if attn_beam is not None or attn_candidates is not None:
+        raise ValueError("attn_shortlist replaces the greedy pair of an evaluation forward as attn_beam and attn_candidates do: pass one "
+                         "of them")
+    if not isinstance(attn_shortlist, tuple) or len(attn_shortlist) != 3:
+        raise ValueError(f"attn_shortlist must be (handle of ops.upload_words, K, max_dist or None), got {attn_shortlist!r}")
+    from types import SimpleNamespace
+    K, max_dist = shortlist_options(SimpleNamespace(lexicon_shortlist=attn_shortlist[1], lexicon_max_distance=attn_shortlist[2]))
+    if K is None:
+        raise ValueError("attn_shortlist: K must be an integer >= 1")
+    if "Attn" not in prediction or is_train or torch.is_grad_enabled():
+        return None
+    return attn_shortlist[0], K, max_dist

@@ -728,11 +728,12 @@ class HeadsGroup(SequenceGroup):
             return False
         return SequenceGroup.sequence_supported([e.model for e in experts])
 
-    def run_greedy(self, visual, start, feats_out, logits_out, beam=None):
+    def run_greedy(self, visual, start, feats_out, logits_out, beam=None, keep=None):
         """run() for attention experts at evaluation time: start = device int64 tensor whose first element is the start token ([SOS]);
         logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  beam = (width, eos) or (width, eos,
         trie handle or None): one more launch for the group on the same features, Hproj and operands (run_beam) -> (path [G,B,S], prob
-        [G,B,S]), with a trie also word [G,B]; else None."""
+        [G,B,S]), with a trie also word [G,B]; else None.  keep (a list): takes (features, Hproj, start, operand columns), what
+        run_beam needs to score a candidate table later."""
         G = self.G
         _, B, _, T, Cf = visual.shape
         feat = self.sequence(visual)                                              # [G,B,T,hidden]
@@ -746,6 +747,8 @@ class HeadsGroup(SequenceGroup):
         cols = list(zip(*args))
         ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out,
                                        w_inv=cols[9] if args[0][9] is not None else None)
+        if keep is not None:
+            keep.extend((feat, Hproj, start, cols))
         return None if beam is None else self.run_beam(feat, Hproj, start, cols, *beam)
 
     def run_beam(self, feat, Hproj, start, cols, width, eos, attn_lexicon=None):

@@ -172,12 +172,13 @@ class Attention(nn.Module):
     SCORE_ROWS_BYTES = 256 << 20      # the stepwise scorer's (sample, slot) rows go in chunks whose features and logits stay within this
 
     @torch.no_grad()
-    def score_candidates(self, batch_H, sos, eos, handle, batch_max_length=25, want_logp=False):
+    def score_candidates(self, batch_H, sos, eos, handle, batch_max_length=25, want_logp=False, Hproj=None):
         """exact log p(word, eos | sample) of every sample's candidate words (modules/decoding.py states the algorithm): batch_H
         [B,T,D], sos as in beam_search, handle = ops.upload_words(...).with_cand(cand [B,K], S) -> (index int32 [B,n], score [B,n],
         score_all [B,K], path int64 [B,S], prob [B,S]) and, with want_logp, logp [B,K,S].  One launch where the kernel's limits and
         the LDS budget allow, otherwise (or under MRN_ATTN_BEAM=stepwise) the teacher-forced decoder on the (sample, slot) rows;
-        CPU tensors go to decoding.attn_candidates_host.  Inference only (no_grad)"""
+        CPU tensors go to decoding.attn_candidates_host.  Hproj: i2h(batch_H) where the caller has it already.  Inference only
+        (no_grad)"""
         from .decoding import attn_candidates_host
         check_hidden(None, "Attn", self.hidden_size)
         S, eos = int(batch_max_length) + 1, int(eos)
@@ -196,7 +197,8 @@ class Attention(nn.Module):
         cell = self.attention_cell
         start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
         batch_H = batch_H.contiguous()
-        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        if Hproj is None:
+            Hproj = ops.linear(batch_H, cell.i2h.weight)
         tokens, lengths, cand = handle.tokens_dev, handle.lengths_dev, handle.cand_dev
         if self.score_fused(D, T, S, eos, handle.n):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
@@ -208,6 +210,45 @@ class Attention(nn.Module):
                                                                       handle.n, eos))
         out = (index, score, score_all, path, prob)
         return out + (logp,) if want_logp else out
+
+    @torch.no_grad()
+    def shortlist_search(self, batch_H, sos, eos, handle, K, max_dist=None, batch_max_length=25, want_logp=False, tokens=None):
+        """the lexicon protocol on a shared word table (modules/decoding.py, "lexicon shortlists"): the greedy decode, the hypothesis =
+        its tokens before the first eos, the K words nearest to it by edit distance (ops.lexicon_shortlist), and the exact scores of
+        those (score_candidates): batch_H [B,T,D], sos as in beam_search, handle = ops.upload_words(...) -> score_candidates' outputs
+        (index int32 [B,n], score [B,n], score_all [B,K], path int64 [B,S], prob [B,S], and logp [B,K,S] with want_logp), then cand
+        int32 [B,K] and dist int32 [B,K].  No beam is run and no width is read.  The greedy decode is the fused launch
+        (mrn_attn_greedy_decode*), the forward's own step loop under MRN_GREEDY_DECODE=stepwise; CPU tensors take the host forms
+        (decoding.attn_beam_host at width 1 is greedy decoding).  tokens int64 [B,S]: the greedy tokens where the caller has decoded
+        already (the arg-max of the forward's logits): no greedy launch then.  Inference only (no_grad)"""
+        from . import decoding as D
+        check_hidden(None, "Attn", self.hidden_size)
+        S, eos = int(batch_max_length) + 1, int(eos)
+        if not isinstance(handle, ops.CandidateHandle):
+            raise ValueError(f"shortlist_search needs the handle of ops.upload_words, got {type(handle).__name__}")
+        if not 0 <= eos < self.num_class:
+            raise ValueError(f"shortlist_search needs 0 <= eos < {self.num_class}, got {eos}")
+        B, T, Dm = batch_H.shape
+        if not batch_H.is_cuda:
+            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
+            path = D.attn_beam_host(self.state_dict(), batch_H, first, eos, 1, S - 1)[4] if tokens is None else tokens.numpy()
+            hyp, hyp_len = D.hypothesis_of_path(path, eos)
+            cand, dist = D.lexicon_shortlist_host(hyp, hyp_len, handle.tokens, handle.lengths, K, max_dist)
+            res = self.score_candidates(batch_H, sos, eos, handle.with_cand(cand, S), S - 1, want_logp=want_logp)
+            return res + (torch.from_numpy(cand), torch.from_numpy(dist))
+        cell = self.attention_cell
+        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
+        batch_H = batch_H.contiguous()
+        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        if tokens is None and ops.greedy_decode_mode() == "fused":
+            etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+            tokens = ops.attn_greedy_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                            self.hidden_size, S, want_tokens=True, w_inv=w_inv)[1]
+        elif tokens is None:
+            tokens = ops.argmax_lastdim(self.forward(batch_H, start, is_train=False, batch_max_length=S - 1))
+        cand, dist = ops.lexicon_shortlist(*ops.hypothesis_of_path(tokens, eos), handle, K, max_dist)
+        res = self.score_candidates(batch_H, start, eos, handle.with_cand(cand, S), S - 1, want_logp=want_logp, Hproj=Hproj)
+        return res + (cand, dist)
 
     def _score_stepwise(self, batch_H, Hproj, start, eos, tokens, lengths, cand, S):
         """score_candidates outside the fused launch: the teacher-forced decoder and the generator on chunks of the B * K (sample,

@@ -1757,17 +1757,47 @@ class CandidateHandle:
         self.device, self.n = torch.device(device), int(n)
         self.cand = self.cand_dev = self.tokens_dev = self.lengths_dev = None
 
-    def with_cand(self, cand, S):
-        """the handle for one batch: cand [B,K] (numpy) is checked against the table on the host (decoding.check_word_table) and
-        uploaded; the table goes up with the first batch"""
-        import copy
+    def is_on(self, device):
+        """is `device` the handle's ("cuda" is the current device, whatever its index)"""
+        mine = self.device
+        return mine.type == device.type and (mine.index is None or device.index is None or mine.index == device.index)
+
+    def on_device(self):
+        """(tokens int32 [N,max(Lmax,1)], lengths int32 [N]) on the handle's device: the table goes up with the first call"""
         import numpy as np
-        from .modules.decoding import check_word_table
-        cand = np.ascontiguousarray(cand, dtype=np.int32)
-        check_word_table(self.tokens, self.lengths, cand, cand.shape[0], S)
         if self.tokens_dev is None:
             pad = self.tokens if self.tokens.shape[1] else np.zeros((len(self.lengths), 1), dtype=np.int32)
             self.tokens_dev, self.lengths_dev = torch.from_numpy(pad).to(self.device), torch.from_numpy(self.lengths).to(self.device)
+        return self.tokens_dev, self.lengths_dev
+
+    def max_class(self):
+        """the largest class of any word (0 for a table of empty words), computed once"""
+        import numpy as np
+        if getattr(self, "_max_class", None) is None:
+            used = self.tokens[np.arange(self.tokens.shape[1])[None, :] < self.lengths[:, None]]
+            self._max_class = int(used.max()) if used.size else 0
+        return self._max_class
+
+    def with_cand(self, cand, S):
+        """the handle for one batch: cand [B,K] (numpy) is checked against the table on the host (decoding.check_word_table) and
+        uploaded; the table goes up with the first batch.  cand may also be an int32 tensor [B,K] on the handle's device, the output of
+        lexicon_shortlist (-1 or a word index by construction): it stays where it is, and the table is checked against S once"""
+        import copy
+        import numpy as np
+        from .modules.decoding import check_word_table
+        if torch.is_tensor(cand):
+            if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[1] < 1 or not self.is_on(cand.device) or not cand.is_contiguous():
+                raise ValueError(f"with_cand: a candidate tensor must be contiguous int32 [B, K >= 1] on {self.device}")
+            if getattr(self, "_checked_S", None) != S:
+                check_word_table(self.tokens, self.lengths, np.full((1, 1), -1, dtype=np.int32), 1, S)
+                self._checked_S = S
+            self.on_device()
+            batch = copy.copy(self)
+            batch.cand, batch.cand_dev = cand, cand
+            return batch
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        check_word_table(self.tokens, self.lengths, cand, cand.shape[0], S)
+        self.on_device()
         batch = copy.copy(self)
         batch.cand, batch.cand_dev = cand, torch.from_numpy(cand).to(self.device)
         return batch
@@ -1776,6 +1806,77 @@ class CandidateHandle:
 def upload_words(tokens, lengths, device, n=1):
     """a word table (decoding.encode_attn_lexicon: tokens int32 [N,Lmax], lengths int32 [N]) -> CandidateHandle on `device`"""
     return CandidateHandle(tokens, lengths, device, n)
+
+
+def hypothesis_of_path(tokens, eos):
+    """attention head: the greedy tokens int [B,S] -> (hyp int32 [B,S], hyp_len int32 [B]): the tokens before the first eos, all S where
+    there is none (decoding.hypothesis_of_path on the tensor's device)"""
+    is_eos = tokens == int(eos)
+    n = torch.where(is_eos.any(dim=1), is_eos.to(torch.int32).argmax(dim=1), tokens.shape[1])
+    return tokens.to(torch.int32), n.to(torch.int32)
+
+
+def hypothesis_of_frames(index):
+    """CTC head: the per-frame arg-max int [B,T] -> (hyp int32 [B,T], hyp_len int32 [B]): the best path collapsed (repeats of the raw
+    index merged, blanks dropped), front-packed, 0 behind (decoding.hypothesis_of_frames on the tensor's device)"""
+    keep = index != 0
+    keep[:, 1:] &= index[:, 1:] != index[:, :-1]
+    order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)
+    hyp = torch.where(keep.gather(1, order), index.gather(1, order), 0)
+    return hyp.to(torch.int32), keep.sum(dim=1).to(torch.int32)
+
+
+SHORTLIST_WORK_BYTES = 256 << 20     # the distance bytes of one mrn_lexicon_shortlist_i32 call stay within this
+
+
+def lexicon_shortlist(hyp, hyp_len, handle, K, max_dist=None):
+    """the K words of a word table nearest to one hypothesis per sample, by unit-cost edit distance over class tokens
+    (include/mrn_shortlist.h: mrn_lexicon_shortlist_i32; modules/decoding.py states the definition): hyp integer [B,Hmax], hyp_len
+    integer [B] (clipped to 0 .. Hmax), handle = upload_words(...), max_dist None (no cut-off) or >= 0
+    -> (cand int32 [B,K] word indices ranked by (distance, index), dist int32 [B,K]; -1 in unused slots), on the device of hyp.
+    CUDA tensors within the kernel's limits (decoding.shortlist_supported) take the kernel, in chunks of samples whose distance bytes
+    stay within SHORTLIST_WORK_BYTES (samples are independent); a sample of more than 64 tokens is flagged by the kernel, finished by
+    decoding.lexicon_shortlist_host and merged (the flags are read back only where Hmax > 64).  CPU tensors and tables outside the
+    limits take the host form"""
+    from .modules import decoding as D
+    if not isinstance(handle, CandidateHandle):
+        raise ValueError(f"lexicon_shortlist needs the handle of ops.upload_words, got {type(handle).__name__}")
+    if not torch.is_tensor(hyp) or not torch.is_tensor(hyp_len) or hyp.dim() != 2 or hyp_len.shape != hyp.shape[:1]:
+        raise ValueError("lexicon_shortlist needs tensors hyp [B,Hmax] and hyp_len [B]")
+    for t in (hyp, hyp_len):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"lexicon_shortlist needs integer tokens and lengths, got {t.dtype}")
+    K = int(K)
+    if K < 1 or (max_dist is not None and max_dist < 0):
+        raise ValueError(f"lexicon_shortlist needs K >= 1 and max_dist None or >= 0, got {K}, {max_dist}")
+    B, Hmax = hyp.shape
+    N, Lmax = handle.tokens.shape
+    dev = hyp.device
+    if not hyp.is_cuda or not D.shortlist_supported(Lmax, N, K, handle.max_class()):
+        host = D.lexicon_shortlist_host(hyp.cpu().numpy(), hyp_len.cpu().numpy(), handle.tokens, handle.lengths, K, max_dist)
+        return tuple(torch.from_numpy(o).to(dev) for o in host)
+    if not handle.is_on(dev):
+        raise ValueError(f"lexicon_shortlist: the word table is on {handle.device}, the hypotheses on {dev}")
+    tokens, lengths = handle.on_device()
+    hyp32 = hyp.to(torch.int32).contiguous()
+    len32 = hyp_len.clamp(0, Hmax).to(torch.int32).contiguous()
+    cand = torch.empty(B, K, device=dev, dtype=torch.int32)
+    dist = torch.empty(B, K, device=dev, dtype=torch.int32)
+    flag = torch.zeros(B, device=dev, dtype=torch.int32)
+    row = (N + 15) // 16 * 16
+    step = max(1, min(B, SHORTLIST_WORK_BYTES // row))
+    work = torch.empty(step * (1024 + row), device=dev, dtype=torch.uint8)
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        call("mrn_lexicon_shortlist_i32", _p(hyp32[b0:b1]) if Hmax else None, Hmax, _p(len32[b0:b1]), b1 - b0, _p(tokens), Lmax,
+             _p(lengths), N, K, -1 if max_dist is None else int(max_dist), _p(cand[b0:b1]), _p(dist[b0:b1]), _p(flag[b0:b1]), _p(work),
+             work.numel(), _stream())
+    if Hmax > D.SHORTLIST_MAX_HYPOTHESIS:
+        rows = torch.nonzero(flag).view(-1)
+        if rows.numel():
+            host = D.lexicon_shortlist_host(hyp32[rows].cpu().numpy(), len32[rows].cpu().numpy(), handle.tokens, handle.lengths, K, max_dist)
+            cand[rows], dist[rows] = torch.from_numpy(host[0]).to(dev), torch.from_numpy(host[1]).to(dev)
+    return cand, dist
 
 
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):

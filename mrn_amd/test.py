@@ -55,6 +55,16 @@ ops.ctc_lexicon_decode(cand=) or its host form; an attention head scores every (
 the evaluation forward: one more launch per heads group, modules/decoding.py), so the best word is the arg-max of log p(word, [EOS] |
 image) over the list whatever a beam width would have been.  opt.lexicon_top_n entries are ranked, the best one is scored, by the
 unchanged scorer.  Together with lexicon, attn_lexicon, ctc_decode = "beam" or attn_decode = "beam" the option is an error.
+
+opt.lexicon_shortlist = K (absent or None: as above, bit for bit) decodes against a large shared lexicon, opt.lexicon on a CTC head and
+opt.attn_lexicon on the attention head, by the lexicon protocol of the CRNN paper (Shi et al., section 3.3): the lexicon-free
+transcription the forward already has (the arg-max per step; on a CTC head collapsed), the K words nearest to it by edit distance
+over class tokens (one ops.lexicon_shortlist call per batch, a tie to the lower word index; opt.lexicon_max_distance, absent or None:
+no cut-off, drops the words further away), and among those the word of largest probability by the exact candidate scoring of
+opt.candidates (ops.ctc_lexicon_decode(cand=) / attn_shortlist=(handle, K, max distance) on the evaluation forward).  The word table
+is encoded and uploaded once per call and the candidate table never leaves the device.  On the attention head the trie beam is not
+run and beam_width is not read.  opt.lexicon_top_n still applies.  A sample whose shortlist is empty scores as the empty prediction
+with confidence 0.  Without the head's lexicon option, or together with candidates, the option is an error.
 """
 import time
 
@@ -82,11 +92,12 @@ def edit_distance(a, b):
     return prev[-1]
 
 
-def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None):
+def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
     """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
     attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits; attn_lexicon (a
     trie handle beside it): the pair of the lexicon-constrained search; attn_candidates (a candidate handle instead of both): the pair
-    of the batch's exact candidate scoring"""
+    of the batch's exact candidate scoring; attn_shortlist ((word handle, K, max distance) instead of all three): the pair of the best
+    word of the greedy hypothesis' shortlist"""
     if "CTC" in opt.Prediction:
         if val_choose == "FF":
             out = model(image, cross=False, is_train=False)
@@ -101,6 +112,8 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
             kw["attn_lexicon"] = attn_lexicon
         if attn_candidates is not None:
             kw["attn_candidates"] = attn_candidates
+        if attn_shortlist is not None:
+            kw["attn_shortlist"] = attn_shortlist
         if val_choose == "FF":
             out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
@@ -108,10 +121,10 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
         else:
             out = model(image, text=sos, is_train=False, **kw)
     logits = out["logits"] if "logits" in out else out["predict"]
-    if attn_beam is None and attn_candidates is None:
+    if attn_beam is None and attn_candidates is None and attn_shortlist is None:
         return logits
     if "beam_path" not in out:
-        what = "attn_decode='beam'" if attn_candidates is None else "candidates"
+        what = "lexicon_shortlist" if attn_shortlist is not None else "attn_decode='beam'" if attn_candidates is None else "candidates"
         raise RuntimeError(f"{what}: the evaluation forward returned no beam pair (it runs under torch.no_grad() only)")
     return logits, (out["beam_path"], out["beam_prob"])
 
@@ -179,14 +192,33 @@ def _beam_pair(preds, prediction, width, top_n):
 class _Lexicon:
     """opt.lexicon encoded once per validation() call; the device copies are made when the first CUDA batch needs them"""
 
-    def __init__(self, converter, words, n):
+    def __init__(self, converter, words, n, shortlist=None):
         self.tokens, self.lengths, self.words = D.encode_lexicon(converter, words)
         self.n = n
         self.device = None
+        self.shortlist, self.handle = shortlist, None        # (K, max distance) of opt.lexicon_shortlist
+
+    def _shortlist_pair(self, preds, prediction):
+        """pair() by the lexicon protocol: the best path's tokens, their K nearest words, the exact scores of those"""
+        K, max_dist = self.shortlist
+        if self.handle is None:
+            self.handle = ops.upload_words(self.tokens, self.lengths, preds.device, self.n)
+        if preds.is_cuda:
+            cand, _ = ops.lexicon_shortlist(*ops.hypothesis_of_frames(ops.argmax_lastdim(preds)), self.handle, K, max_dist)
+            if D.lexicon_supported(prediction, preds.size(1), preds.size(2), int(self.lengths.max()), len(self.lengths), self.n):
+                return ops.ctc_lexicon_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), *self.handle.on_device(), n=self.n,
+                                              cand=cand)[3:]
+            cand = cand.cpu().numpy()
+        else:
+            cand, _ = D.lexicon_shortlist_host(*D.hypothesis_of_frames(preds.argmax(dim=2).numpy()), self.tokens, self.lengths, K, max_dist)
+        path, prob = D.ctc_lexicon_host(preds.detach().cpu().numpy(), self.tokens, self.lengths, self.n, cand)[3:]
+        return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
 
     def pair(self, preds, prediction):
         """the lexicon decoder's (path, prob) for CTC logits [B,T,C], on the device of `preds`: the kernel when it takes the batch,
         else the host form"""
+        if self.shortlist is not None:
+            return self._shortlist_pair(preds, prediction)
         N = len(self.lengths)
         if preds.is_cuda and D.lexicon_supported(prediction, preds.size(1), preds.size(2), int(self.lengths.max()), N, self.n):
             if self.device is None:
@@ -208,6 +240,21 @@ class _AttnLexicon:
         if self.handle is None:
             self.handle = ops.upload_trie(self.trie, device)
         return self.handle
+
+
+class _AttnShortlist:
+    """opt.attn_lexicon with opt.lexicon_shortlist: the word table encoded once per validation() call, uploaded when the first batch needs
+    it; no trie"""
+
+    def __init__(self, converter, words, batch_max_length, n, K, max_dist):
+        self.tokens, self.lengths, self.words = D.encode_attn_lexicon(converter, words, batch_max_length)
+        self.n, self.K, self.max_dist, self.handle = n, K, max_dist, None
+
+    def on(self, device):
+        """the attn_shortlist= of the evaluation forward"""
+        if self.handle is None:
+            self.handle = ops.upload_words(self.tokens, self.lengths, device, self.n)
+        return self.handle, self.K, self.max_dist
 
 
 class _Candidates:
@@ -256,19 +303,23 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     attn_decode, attn_width = D.attn_decode_options(opt)
     attn_beam = attn_width if attn and attn_decode == "beam" else None
     attn_words, attn_lexicon_width = D.attn_lexicon_options(opt)
-    attn_lexicon = None
-    if attn and attn_words is not None:
-        attn_lexicon, attn_beam = _AttnLexicon(converter, attn_words, opt.batch_max_length), attn_lexicon_width
+    attn_lexicon = attn_shortlist = None
     lexicon_words, lexicon_n = D.lexicon_options(opt)
+    shortlist = D.shortlist_request(opt, attn)               # (K, max distance) or None
+    if attn and attn_words is not None and shortlist is not None:
+        attn_shortlist, attn_beam = _AttnShortlist(converter, attn_words, opt.batch_max_length, lexicon_n, *shortlist), None
+    elif attn and attn_words is not None:
+        attn_lexicon, attn_beam = _AttnLexicon(converter, attn_words, opt.batch_max_length), attn_lexicon_width
     if lexicon_words is not None and not attn and ctc_decode == "beam":
         raise ValueError("lexicon and ctc_decode='beam' both replace best-path decoding on a CTC head: set one of them")
-    lexicon = _Lexicon(converter, lexicon_words, lexicon_n) if lexicon_words is not None and not attn else None
+    lexicon = _Lexicon(converter, lexicon_words, lexicon_n, shortlist) if lexicon_words is not None and not attn else None
     cand_fn, cand_n = D.candidates_options(opt)
     candidates = None
     if cand_fn is not None:
         candidates = _Candidates(converter, cand_fn, evaluation_loader, attn, opt.batch_max_length, cand_n)
-    if (attn_beam is not None or (attn and candidates is not None)) and converter.dict["[EOS]"] != D.ATTN_EOS:
-        what = "candidates" if candidates is not None else "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'"
+    if (attn_beam is not None or attn_shortlist is not None or (attn and candidates is not None)) and converter.dict["[EOS]"] != D.ATTN_EOS:
+        what = ("lexicon_shortlist" if attn_shortlist is not None else "candidates" if candidates is not None
+                else "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'")
         raise ValueError(f"{what} ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
@@ -280,8 +331,9 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         start = time.time()
         attn_cands = candidates.on(image.device, labels) if attn and candidates is not None else None
         preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam,
-                         attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device), attn_candidates=attn_cands)
-        if attn_beam is not None or attn_cands is not None:
+                         attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device), attn_candidates=attn_cands,
+                         attn_shortlist=None if attn_shortlist is None else attn_shortlist.on(image.device))
+        if attn_beam is not None or attn_cands is not None or attn_shortlist is not None:
             preds, beam_pair = preds
         if image.is_cuda:
             torch.cuda.synchronize()
@@ -302,7 +354,7 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
             preds_index, preds_max_prob = lexicon.pair(preds, opt.Prediction)
         elif ctc_decode == "beam" and not attn:
             preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
-        elif attn_beam is not None or attn_cands is not None:
+        elif attn_beam is not None or attn_cands is not None or attn_shortlist is not None:
             preds_index, preds_max_prob = beam_pair
         else:
             preds_index, preds_max_prob = ops.argmax_prob_lastdim(preds)                     # :211, :218-219
