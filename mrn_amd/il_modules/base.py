@@ -254,17 +254,57 @@ class BaseLearner(object):
 
     def build_rehearsal_memory(self, train_loader, taski):
         num_i = self.memory_per_task(taski)
-        self.build_random_current_memory(num_i, taski, train_loader)
+        self.build_current_memory(num_i, taski, train_loader)
         if len(self.memory_index) != 0 and len(self.memory_index) * len(self.memory_index[0]) > self.opt.memory_num:
             self.reduce_samplers(taski, taski_num=num_i)
         train_loader.get_dataset(taski, memory=self.opt.memory, index_list=self.memory_index)
         print("Is using rehearsal memory, has {} prev datasets, each has {}\n".format(len(self.memory_index), self.memory_index[0].size))
+
+    def build_current_memory(self, taski_num, taski, train_loader):
+        """which samples of the PREVIOUS task join the memory: opt.memory == "herding" selects them by herding, every other strategy
+        draws them at random (the reference's only one)"""
+        if self.opt.memory == "herding":
+            self.build_herding_current_memory(taski_num, taski, train_loader)
+        else:
+            self.build_random_current_memory(taski_num, taski, train_loader)
 
     def build_random_current_memory(self, taski_num, taski, train_loader):
         """taski_num random sample indices of the PREVIOUS task's dataset join the memory"""
         prev_loader, len_data = train_loader.rehearsal_prev_model(taski)
         index_list = np.random.choice(range(len_data), taski_num, replace=False)
         self.memory_index.append(index_list)
+
+    def herding_feature(self, image, taski):
+        """the contextual feature [B, T, D] the herding selection of task taski - 1's samples is made on: the network as it stood at
+        the end of task taski - 1.  Here the model's own extractor: growing the classifier for task taski does not touch it"""
+        net = self.model.module if isinstance(self.model, parallel.ReplicaDataParallel) else self.model
+        return net.model(image)
+
+    def build_herding_current_memory(self, taski_num, taski, train_loader):
+        """taski_num sample indices of the PREVIOUS task's dataset join the memory IN HERDING ORDER (modules/herding.py: the samples
+        whose running feature mean stays closest to the task's): one pass over the ordered loader of rehearsal_prev_model in eval
+        mode, the features written into one table on the device (ops.herding_features), then ops.herding_select.  A prefix of the
+        list is the herding selection of the smaller budget, so reduce_samplers' cut keeps a herding selection.  No random draw;
+        every rank makes the same selection on the whole dataset"""
+        prev_loader, len_data = train_loader.rehearsal_prev_model(taski)
+        modes = [(mod, mod.training) for mod in self.model.modules()]
+        self.model.eval()
+        table, row = None, 0
+        try:
+            with torch.no_grad():
+                for image, _ in prev_loader:
+                    feat = self.herding_feature(image.to(self.device), taski)
+                    if table is None:
+                        table = torch.zeros(len_data, feat.shape[-1], device=feat.device, dtype=torch.float32)
+                    ops.herding_features(feat.float(), out=table, row0=row)
+                    row += feat.shape[0]
+        finally:
+            for mod, training in modes:                    # (exactly the modes found: DER and MRN keep some experts in eval mode)
+                mod.training = training
+        if row != len_data:
+            raise RuntimeError(f"herding: the loader of task {taski - 1} gave {row} samples, its dataset has {len_data}")
+        picks, _ = ops.herding_select(table, taski_num)
+        self.memory_index.append(picks.cpu().numpy())
 
     def reduce_samplers(self, taski, taski_num):
         for i in range(taski):

@@ -3,6 +3,8 @@ loss = loss_clf (the auxiliary loss is computed and logged but NOT added, refere
 every task > 0."""
 import time
 
+import torch
+
 from .. import parallel
 from ..modules.model import DERNet
 from ..tools.utils import Averager
@@ -68,6 +70,11 @@ class DER(BaseLearner):
             self.model_eval_and_train(taski)
             self._update(start_iter, taski, train_loader, valid_loader)
             self.model.module.weight_align(self._total_classes - self._known_classes)       # der.py:148
+
+    def herding_feature(self, image, taski):
+        """the concatenation of the taski extractors trained so far [B, T, hidden * taski], not the freshly added one"""
+        net = self.model.module if isinstance(self.model, parallel.ReplicaDataParallel) else self.model
+        return torch.cat([net.model[i](image) for i in range(taski)], -1)
 
     def prefetch_frozen(self, image):
         """issue the frozen extractors' forward of a FUTURE batch (DERNet.frozen_prefetch); pass the result to

@@ -57,15 +57,26 @@ class MRN(BaseLearner):
 
     def build_rehearsal_memory(self, train_loader, taski):
         num_i = self.memory_per_task(taski)
-        self.build_random_current_memory(num_i, taski, train_loader)
+        self.build_current_memory(num_i, taski, train_loader)
         if self.opt.memory_num < 5000:
             if len(self.memory_index) != 0 and len(self.memory_index) * len(self.memory_index[0]) > self.opt.memory_num:
                 self.reduce_samplers(taski, taski_num=num_i)
         train_loader.get_dataset(taski, memory=self.opt.memory, index_list=self.memory_index)
         print("Is using rehearsal memory, has {} prev datasets, each has {}\n".format(len(self.memory_index), self.memory_index[0].size))
 
+    def herding_feature(self, image, taski):
+        """expert taski - 1's contextual feature: the expert trained on the task whose samples are selected"""
+        net = self.model.module if isinstance(self.model, parallel.ReplicaDataParallel) else self.model
+        return net.model[taski - 1].model(image)
+
     def _train(self, start_iter, taski, train_loader, valid_loader, step=0):
         if self.opt.start_task > taski + step * 0.5:           # resume: load this (task, step)'s checkpoint (mrn.py:187-203)
+            if taski > 0 and step == 1 and self.opt.memory == "herding":
+                # the selection reads expert taski - 1 as the trained run's did: before the router's checkpoint, whose copy of that
+                # expert has the BatchNorm statistics loop B went on updating (the other strategies do not look at the weights)
+                self.load_task_data(train_loader, taski)
+                self.load_checkpoint(self.checkpoint_path(taski, step))
+                return
             self.load_checkpoint(self.checkpoint_path(taski, step))
             if taski > 0 and step == 0:
                 train_loader.get_dataset(taski, memory=None)

@@ -1879,6 +1879,64 @@ def lexicon_shortlist(hyp, hyp_len, handle, K, max_dist=None):
     return cand, dist
 
 
+def herding_features(feat, out=None, row0=0):
+    """herding features of a batch (include/mrn_herding.h: mrn_herding_features_f32; modules/herding.py states them): feat fp32 [B,T,D]
+    (any batch and time stride, the D values of a frame contiguous) -> the time means divided by (their norm + 1e-8), written to rows
+    row0 ... row0 + B of the table out fp32 [N,D] (contiguous, on the device of feat; None: a fresh [B,D] one); the other rows are not
+    touched.  -> out.  CPU tensors take herding.features_host"""
+    from .modules import herding as H
+    if not torch.is_tensor(feat) or feat.dim() != 3 or feat.dtype != torch.float32 or feat.shape[1] < 1:
+        raise ValueError("herding_features needs a float32 tensor feat [B, T >= 1, D]")
+    B, T, D = feat.shape
+    row0 = int(row0)
+    if out is None:
+        out = torch.empty(B, D, device=feat.device, dtype=torch.float32)
+    if (not torch.is_tensor(out) or out.dim() != 2 or out.dtype != torch.float32 or out.device != feat.device or not out.is_contiguous()
+            or out.shape[1] != D or row0 < 0 or row0 + B > out.shape[0]):
+        raise ValueError(f"herding_features: out must be a contiguous float32 table [N >= {row0 + B}, {D}] on {feat.device}")
+    if not feat.is_cuda:
+        if B:
+            out[row0:row0 + B] = torch.from_numpy(H.features_host(feat.detach().numpy()).astype("float32"))
+        return out
+    N = out.shape[0]
+    if not (H.MIN_DIM <= D <= H.MAX_DIM and D % 4 == 0 and 1 <= N <= H.MAX_ROWS):
+        raise ValueError(f"herding_features: a table of {N} rows (1 ... 2^24) and D = {D} columns ({H.MIN_DIM} ... {H.MAX_DIM}, D % 4 = 0)")
+    if B == 0:
+        return out
+    feat = feat.detach()
+    if feat.stride(2) != 1 or feat.stride(0) < 0 or feat.stride(1) < 0:
+        feat = feat.contiguous()
+    call("mrn_herding_features_f32", _p(feat), B, T, D, feat.stride(0), feat.stride(1), _p(out), N, row0, _stream())
+    return out
+
+
+def herding_select(F, m):
+    """herding selection of m of the N rows of the feature table F fp32 [N,D] (include/mrn_herding.h: mrn_herding_select_f32;
+    modules/herding.py states the algorithm) -> (picks int64 [m] IN PICK ORDER, dist float32 [m]: the minimised
+    ||f||^2 - 2 f . r of every step), on the device of F.  m + 4 launches on the current stream and no synchronisation between them;
+    the one before them is the check that the table is finite.  m outside 1 ... N, an empty table or non-finite features are a
+    ValueError before any launch.  CPU tensors take herding.herding_host"""
+    from .modules import herding as H
+    if not torch.is_tensor(F) or F.dim() != 2 or F.dtype != torch.float32:
+        raise ValueError("herding_select needs a float32 tensor F [N, D]")
+    N, D = F.shape
+    m = H.check_request(N, D, m)
+    if not F.is_cuda:
+        picks, dist = H.herding_host(F.detach().numpy(), m)
+        return torch.from_numpy(picks), torch.from_numpy(dist.astype("float32"))
+    if not H.select_supported(N, D, m):
+        raise ValueError(f"herding_select: a table of {N} rows (1 ... 2^24) and D = {D} columns ({H.MIN_DIM} ... {H.MAX_DIM}, D % 4 = 0)")
+    F = F.detach().contiguous()
+    if not bool(torch.isfinite(F).all()):
+        raise ValueError("herding: the feature table has non-finite entries")
+    need = call("mrn_herding_select_work_bytes", N, D)
+    work = torch.empty(need, device=F.device, dtype=torch.uint8)
+    picks = torch.empty(m, device=F.device, dtype=torch.int32)
+    dist = torch.empty(m, device=F.device, dtype=torch.float32)
+    call("mrn_herding_select_f32", _p(F), N, D, m, _p(picks), _p(dist), _p(work), need, _stream())
+    return picks.to(torch.int64), dist
+
+
 def pack_decoder_x3(w_h2h, w_ih, w_hh, D):
     """(h2h.weight [H,H], rnn.weight_ih [4H, D+E], rnn.weight_hh [4H,H]) -> (three pack_fragment_major_h streams, w_inv float[3])"""
     a, b, c = pack_fragment_major_h(w_h2h.detach()), pack_fragment_major_h(w_ih.detach()[:, :D].contiguous()), pack_fragment_major_h(w_hh.detach())
