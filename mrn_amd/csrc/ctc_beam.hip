@@ -14,6 +14,12 @@
 // (slot 0 = stay, 1 + r = extend by the rank-r class) belongs to lane q % 64, register q / 64: W * (K + 1) <= 256 is four per lane, and
 // q is the tie order of the selection.  Every cross-lane read is a __shfl all 64 lanes execute; only the token arrays go through LDS,
 // and only this wave touches its LDS region, so there is no block-wide barrier anywhere.
+//
+// Language-model fusion (mrn_ctc_beam_lm_decode_f32, include/mrn_ctc_lm.h) is the same body with LM = true: lane i < W also holds
+// e_prev, the class before e_last, and e_lm, the sum of the model's log-probabilities over the prefix; every lane looks up the model
+// for its own up-to-four candidates (at most three bounded probe sequences of 8-byte reads each into a read-only hash table,
+// mrn_amd/modules/char_lm.py), the selection ranks by total + alpha * lm' + beta * len' instead of the total, and after the last frame
+// W more rounds of wave_argmax order the entries by the key with the end-of-text term.  With LM = false nothing of that is compiled.
 #include <math.h>
 
 #include "common.hpp"
@@ -28,6 +34,7 @@ constexpr int BEAM_CPL = 4;                 // candidates per lane: 16 * (15 + 1
 constexpr int BEAM_ROWS = 4;                // samples (waves) per block at most
 constexpr int BEAM_LDS_BUDGET = 64 * 1024;  // per block: two blocks fit the 160 KiB of a CU at any T
 constexpr int BEAM_DROP_BYTES = BEAM_MAX_W * 16;
+constexpr int64_t BEAM_LM_MAX_SLOTS = (int64_t)1 << 26;  // slots of the language model's hash table
 
 // this wave's LDS writes are visible to its other lanes: a wave's LDS accesses complete in order, the fence keeps the compiler's order
 __device__ __forceinline__ void wave_sync() {
@@ -55,10 +62,63 @@ __device__ __forceinline__ void wave_argmax(float& v, int& q) {
   }
 }
 
+// the character n-gram model of modules/char_lm.py in its device form
+struct BeamLM {
+  const unsigned long long* keys;  // [mask + 1]: n << 60 | a << 32 | b << 16 | c, 0 = empty slot
+  const float2* vals;              // [mask + 1]: (logp, bow)
+  const float* uni_logp;           // [C_lm], entry 0 = end of text
+  const float* uni_bow;            // [C_lm]
+  float* fused;                    // [B][W] out: the key the entries are ordered by
+  unsigned mask;
+  int max_probe, C_lm, order;
+  float unk_logp, alpha, beta;
+};
+
+// the 64-bit mix of char_lm.py mix(): the splitmix64 finaliser
+__device__ __forceinline__ unsigned long long lm_mix(unsigned long long h) {
+  h ^= h >> 30;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 27;
+  h *= 0x94D049BB133111EBull;
+  h ^= h >> 31;
+  return h;
+}
+
+// bounded linear probe: at most max_probe slots, whatever the table holds
+__device__ __forceinline__ bool lm_find(const BeamLM& lm, unsigned long long key, float2& v) {
+  unsigned s = (unsigned)lm_mix(key) & lm.mask;
+  for (int p = 0; p < lm.max_probe; ++p) {
+    const unsigned long long k = lm.keys[s];
+    if (k == key) {
+      v = lm.vals[s];
+      return true;
+    }
+    if (k == 0ull) return false;
+    s = (s + 1u) & lm.mask;
+  }
+  return false;
+}
+
+// log p(c | a, b) by the back-off evaluation of char_lm.py CharLM.logp, float32 sums in its order; a, b, c in 0 .. 65534
+__device__ __forceinline__ float lm_logp(const BeamLM& lm, int a, int b, int c) {
+  const float uni = c < lm.C_lm ? lm.uni_logp[c] : lm.unk_logp;
+  if (lm.order == 1) return uni;
+  const unsigned long long kb = (unsigned long long)b << 16, kc = (unsigned long long)c;
+  float2 v;
+  float bo = 0.f;
+  if (lm.order == 3) {
+    if (lm_find(lm, 3ull << 60 | (unsigned long long)a << 32 | kb | kc, v)) return v.x;
+    if (lm_find(lm, 2ull << 60 | (unsigned long long)a << 16 | (unsigned long long)b, v)) bo = v.y;
+  }
+  if (lm_find(lm, 2ull << 60 | kb | kc, v)) return bo + v.x;
+  return bo + ((b < lm.C_lm ? lm.uni_bow[b] : 0.f) + uni);
+}
+
+template <bool LM>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__ logits, long sb, long st, int B, int T, int C, int W, int K,
                                                        int32_t* __restrict__ tokens, int32_t* __restrict__ length,
                                                        float* __restrict__ score, int64_t* __restrict__ path,
-                                                       float* __restrict__ prob) {
+                                                       float* __restrict__ prob, const BeamLM lm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char beam_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -87,6 +147,8 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
   int e_len = lane == 0 ? 0 : -1, e_last = -1;
   unsigned e_hash = 0;
   int n_live = 1;
+  int e_prev = 0;    // LM: the class before e_last, 0 = begin of text
+  float e_lm = 0.f;  // LM: the model's log-probability of the prefix
 
   const float* xb = logits + (long)b * sb;
   for (int t = 0; t < T; ++t) {
@@ -171,10 +233,16 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
 
     // ---- candidate space ----
     float c_pb[BEAM_CPL], c_pnb[BEAM_CPL], c_tot[BEAM_CPL];
+    float c_key[BEAM_CPL], c_lm[BEAM_CPL];  // LM: the ranking key (-inf where the total is not finite) and lm' of the candidate
+    float(&c_rank)[BEAM_CPL] = LM ? c_key : c_tot;
     const int n_cand = n_live * kp1;
 #pragma unroll
     for (int j = 0; j < BEAM_CPL; ++j) {
       c_pb[j] = c_pnb[j] = c_tot[j] = -INFINITY;
+      if constexpr (LM) {
+        c_key[j] = -INFINITY;
+        c_lm[j] = 0.f;
+      }
       if (64 * j < n_cand) {  // wave-uniform
         const bool valid = lane + 64 * j < n_cand;
         const int i = valid ? cand_i[j] : 0;
@@ -194,6 +262,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
           const float tot = log_add_exp(c_pb[j], c_pnb[j]);
           c_tot[j] = isfinite(tot) ? tot : -INFINITY;
         }
+        if constexpr (LM) {
+          const int p_prev = __shfl(e_prev, i), p_len = __shfl(e_len, i);
+          const float p_lm = __shfl(e_lm, i);
+          if (valid && c_tot[j] > -INFINITY) {
+            const bool ext = cand_slot[j] > 0;
+            c_lm[j] = ext ? p_lm + lm_logp(lm, p_prev, max(p_last, 0), c) : p_lm;
+            c_key[j] = c_tot[j] + lm.alpha * c_lm[j] + lm.beta * (float)(p_len + (ext ? 1 : 0));
+          }
+        }
       }
     }
 
@@ -202,15 +279,22 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
     int n_len = -1, n_last = -1;
     unsigned n_hash = 0;
     int live = 0;
+    int n_prev = 0;
+    float n_lm = 0.f;
     for (int n = 0; n < W; ++n) {
       float bt = -INFINITY, l_pb = -INFINITY, l_pnb = -INFINITY;  // this lane's best candidate
+      float l_tot = -INFINITY, l_lm = 0.f;
       int bq = -1, lj = -1;
 #pragma unroll
       for (int j = 0; j < BEAM_CPL; ++j)
-        if (c_tot[j] > bt) {  // j ascends: the lower order keeps a tie
-          bt = c_tot[j];
+        if (c_rank[j] > bt) {  // j ascends: the lower order keeps a tie
+          bt = c_rank[j];
           l_pb = c_pb[j];
           l_pnb = c_pnb[j];
+          if constexpr (LM) {
+            l_tot = c_tot[j];
+            l_lm = c_lm[j];
+          }
           lj = j;
           bq = lane + 64 * j;
         }
@@ -219,9 +303,14 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
       bq = __builtin_amdgcn_readfirstlane(bq);
       const int owner = bq & 63;
       const float v_pb = __shfl(l_pb, owner), v_pnb = __shfl(l_pnb, owner);
+      float v_tot = bt, v_lm = 0.f;  // LM: bt is the key, the total and lm' come from the owner
+      if constexpr (LM) {
+        v_tot = __shfl(l_tot, owner);
+        v_lm = __shfl(l_lm, owner);
+      }
 #pragma unroll
       for (int j = 0; j < BEAM_CPL; ++j)
-        if (lane == owner && j == lj) c_tot[j] = -INFINITY;  // (the winner is its owner's best: lj is its register)
+        if (lane == owner && j == lj) c_rank[j] = -INFINITY;  // (the winner is its owner's best: lj is its register)
       const int i = bq / kp1, slot = bq - i * kp1;
       const int p_len = __shfl(e_len, i), p_last = __shfl(e_last, i);
       const unsigned p_hash = __shfl(e_hash, i);
@@ -229,10 +318,17 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
       if (lane == n) {
         n_pb = v_pb;
         n_pnb = v_pnb;
-        n_tot = bt;
+        n_tot = v_tot;
         n_len = p_len + (slot > 0 ? 1 : 0);
         n_last = slot > 0 ? c : p_last;
         n_hash = slot > 0 ? hash_push(p_hash, c) : p_hash;
+      }
+      if constexpr (LM) {
+        const int p_prev = __shfl(e_prev, i);
+        if (lane == n) {
+          n_prev = slot > 0 ? max(p_last, 0) : p_prev;
+          n_lm = v_lm;
+        }
       }
       const unsigned short* src = cur + i * T;
       unsigned short* dst = nxt + n * T;
@@ -246,6 +342,10 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
     e_len = n_len;
     e_last = n_last;
     e_hash = n_hash;
+    if constexpr (LM) {
+      e_prev = n_prev;
+      e_lm = n_lm;
+    }
     n_live = live;
     unsigned short* swap = cur;
     cur = nxt;
@@ -253,7 +353,31 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
     wave_sync();
   }
 
-  // ---- outputs: the entries in their order (descending total) ----
+  // ---- LM: order the live entries by the key with the end-of-text term; lane n takes the state of its winner, the tokens stay ----
+  int e_row = lane;  // the token row of this lane's entry
+  if constexpr (LM) {
+    const bool mine = lane < n_live;
+    const float fkey = mine ? e_tot + lm.alpha * (e_lm + lm_logp(lm, e_prev, max(e_last, 0), 0)) + lm.beta * (float)e_len : -INFINITY;
+    bool taken = !mine;
+    float n_fused = -INFINITY;
+    for (int n = 0; n < n_live; ++n) {
+      float bv = taken ? -INFINITY : fkey;
+      int bq = taken ? -1 : lane;
+      wave_argmax(bv, bq);  // (a live entry's key is finite: one is found every round)
+      if (bq < 0) break;
+      bq = __builtin_amdgcn_readfirstlane(bq);
+      if (lane == bq) taken = true;
+      if (lane == n) {
+        e_row = bq;
+        n_fused = bv;
+      }
+    }
+    e_tot = __shfl(e_tot, e_row);
+    e_len = __shfl(e_len, e_row);
+    if (lane < W) lm.fused[(long)b * W + lane] = n_fused;
+  }
+
+  // ---- outputs: the entries in their order (descending total; LM: descending key) ----
   if (lane < W) {
     length[(long)b * W + lane] = e_len;
     score[(long)b * W + lane] = e_tot;
@@ -261,9 +385,10 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__
   for (int w = 0; w < W; ++w) {
     const int len = __shfl(e_len, w);
     int32_t* out = tokens + ((long)b * W + w) * T;
-    const unsigned short* src = cur + w * T;
+    const unsigned short* src = cur + (LM ? __shfl(e_row, w) : w) * T;
     for (int u = lane; u < T; u += 64) out[u] = u < len ? (int32_t)src[u] : 0;
   }
+  if constexpr (LM) cur += __shfl(e_row, 0) * T;  // the best entry's row, for the path below
   // the best entry as a frame row: a blank between equal neighbours, blanks behind; greedy collapse gives the prefix back
   const int len0 = max(__shfl(e_len, 0), 0);
   const float tot0 = __shfl(e_tot, 0);
@@ -302,8 +427,54 @@ MRN_EXPORT int mrn_ctc_beam_decode_f32(const float* logits, int64_t stride_b, in
   int rows = BEAM_LDS_BUDGET / row_bytes;
   rows = rows > BEAM_ROWS ? BEAM_ROWS : rows;
   const dim3 grid((unsigned)((B + rows - 1) / rows)), block(64 * rows);
-  hipLaunchKernelGGL(ctc_beam_kernel, grid, block, (size_t)rows * row_bytes, (hipStream_t)stream, logits, (long)stride_b, (long)stride_t,
-                     B, T, C, W, K, tokens, length, score, path, prob);
+  hipLaunchKernelGGL(ctc_beam_kernel<false>, grid, block, (size_t)rows * row_bytes, (hipStream_t)stream, logits, (long)stride_b,
+                     (long)stride_t, B, T, C, W, K, tokens, length, score, path, prob, BeamLM{});
   MRN_LAUNCH_CHECK("ctc_beam_decode");
+  return MRN_OK;
+}
+
+MRN_EXPORT int mrn_ctc_beam_lm_decode_f32(const float* logits, int64_t stride_b, int64_t stride_t, int B, int T, int C, int W, int K,
+                                          int32_t* tokens, int32_t* length, float* score, int64_t* path, float* prob,
+                                          const void* lm_keys, const float* lm_vals, int64_t lm_mask, int lm_max_probe,
+                                          const float* uni_logp, const float* uni_bow, int C_lm, float unk_logp, int order, float alpha,
+                                          float beta, float* fused, void* stream) {
+  MRN_CHECK_ARG(B >= 0 && stride_b >= 0 && stride_t >= 0, "mrn_ctc_beam_lm_decode_f32: B = %d, strides %ld / %ld", B, (long)stride_b,
+                (long)stride_t);
+  MRN_CHECK_ARG(T >= 1 && T <= BEAM_MAX_T, "mrn_ctc_beam_lm_decode_f32: T = %d outside 1..%d", T, BEAM_MAX_T);
+  MRN_CHECK_ARG(C >= 2 && C <= BEAM_MAX_C, "mrn_ctc_beam_lm_decode_f32: C = %d outside 2..%d", C, BEAM_MAX_C);
+  MRN_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W, "mrn_ctc_beam_lm_decode_f32: beam width %d outside 1..%d", W, BEAM_MAX_W);
+  MRN_CHECK_ARG(K >= 1 && K <= BEAM_MAX_K, "mrn_ctc_beam_lm_decode_f32: cut-off %d outside 1..%d", K, BEAM_MAX_K);
+  MRN_CHECK_ARG(order >= 1 && order <= 3, "mrn_ctc_beam_lm_decode_f32: order %d outside 1..3", order);
+  MRN_CHECK_ARG(C_lm >= 1 && C_lm <= BEAM_MAX_C, "mrn_ctc_beam_lm_decode_f32: C_lm = %d outside 1..%d", C_lm, BEAM_MAX_C);
+  MRN_CHECK_ARG(lm_mask >= 0 && lm_mask < BEAM_LM_MAX_SLOTS && ((lm_mask + 1) & lm_mask) == 0,
+                "mrn_ctc_beam_lm_decode_f32: table mask %ld is not a power of two up to 2^26 less one", (long)lm_mask);
+  MRN_CHECK_ARG(lm_max_probe >= 0 && (int64_t)lm_max_probe <= lm_mask + 1, "mrn_ctc_beam_lm_decode_f32: max_probe %d outside 0..%ld",
+                lm_max_probe, (long)(lm_mask + 1));
+  MRN_CHECK_ARG(isfinite(unk_logp) && isfinite(alpha) && alpha >= 0.f && isfinite(beta),
+                "mrn_ctc_beam_lm_decode_f32: unk_logp %g, alpha %g (>= 0) and beta %g must be finite", (double)unk_logp, (double)alpha,
+                (double)beta);
+  if (B == 0) return MRN_OK;
+  MRN_CHECK_ARG(logits && tokens && length && score && path && prob && fused && lm_keys && lm_vals && uni_logp && uni_bow,
+                "mrn_ctc_beam_lm_decode_f32: bad operands");
+  BeamLM lm;
+  lm.keys = (const unsigned long long*)lm_keys;
+  lm.vals = (const float2*)lm_vals;
+  lm.uni_logp = uni_logp;
+  lm.uni_bow = uni_bow;
+  lm.fused = fused;
+  lm.mask = (unsigned)lm_mask;
+  lm.max_probe = lm_max_probe;
+  lm.C_lm = C_lm;
+  lm.order = order;
+  lm.unk_logp = unk_logp;
+  lm.alpha = alpha;
+  lm.beta = beta;
+  const int row_bytes = 2 * W * T * (int)sizeof(unsigned short) + BEAM_DROP_BYTES;  // the layout and the rows-per-block rule above
+  int rows = BEAM_LDS_BUDGET / row_bytes;
+  rows = rows > BEAM_ROWS ? BEAM_ROWS : rows;
+  const dim3 grid((unsigned)((B + rows - 1) / rows)), block(64 * rows);
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, grid, block, (size_t)rows * row_bytes, (hipStream_t)stream, logits, (long)stride_b,
+                     (long)stride_t, B, T, C, W, K, tokens, length, score, path, prob, lm);
+  MRN_LAUNCH_CHECK("ctc_beam_lm_decode");
   return MRN_OK;
 }

@@ -21,6 +21,22 @@ the best entry the pair that goes wherever argmax_prob_lastdim's goes: path [T] 
 neighbours, blanks behind (the greedy collapse gives the prefix back) and prob [T] = [exp(score), 1, 1, ...] (the cumulative product
 is exp(score): multiplying by 1.0 is exact).
 
+Language-model fusion (opt-in: lm = a modules/char_lm.py CharLM, lm_weight alpha >= 0, lm_bonus beta finite; mrn_ctc_beam_lm_decode_f32
+runs it in float32).  An entry additionally carries lm, the sum of LM.logp(prev, last, c) over its classes c, accumulated left to right
+(prev, last = the two classes in front of c, 0 where the prefix is shorter: begin of text).  lm is a function of the prefix alone, so
+two routes to one prefix carry the same bits and step 5's merge stays exact and needs no LM term.  The steps above with step 6 ranked
+by a key instead of the total:
+
+  6'. key = total + alpha * lm' + beta * len' (evaluated left to right); a stay has lm' = lm_i, len' = len_i, an extension by c has
+      lm' = lm_i + LM.logp(prev_i, last_i, c), len' = len_i + 1.  Of the candidates with a finite (acoustic) total the W largest KEYS
+      are kept, ties in candidate order as before; a candidate whose total is not finite never survives, whatever the model says;
+  7'. after the last frame the live entries are ordered once more, by fused = total + alpha * (lm + LM.logp(prev, last, 0)) + beta * len
+      (0 = end of text), descending, a tie to the earlier slot.
+
+score stays the acoustic log-probability of the label (prob[0] = exp(score) stays a probability for the scorer); one more output,
+fused [W], holds the key the entries are ordered by (-inf for a dead slot).  With alpha = beta = 0 the key is the total and tokens,
+length, score, path and prob are today's, bit for bit.
+
 The attention head (reference modules/prediction.py:70-86 feeds the arg-max back: one hypothesis) is decoded by beam search with
 opt.attn_decode = "beam"; the width is opt.beam_width.  mrn_attn_beam_decode_* (mrn_amd/csrc/attn_decode.hip attn_beam_kernel) runs it in
 float32, all steps of all experts in one launch, attn_beam_host below in float64.  Per sample: width W, S = batch_max_length + 1 steps,
@@ -110,14 +126,19 @@ def _cut_off(row, k):
     return chosen[np.lexsort((chosen, -x[chosen]))] + 1
 
 
-def _beam_one(x, W, K):
-    """one sample [T][C] -> [(prefix tuple, total)] in descending total"""
+def _beam_one(x, W, K, lm=None, alpha=0.0, beta=0.0, dtype=np.float64):
+    """one sample [T][C] -> [(prefix tuple, total)] in descending total; with a language model [(prefix tuple, total, fused)] in
+    descending fused key.  All arithmetic in `dtype`"""
     T, C = x.shape
     k = min(K, C - 1)
-    x64 = x.astype(np.float64)
+    f = dtype
+    ninf = f(-np.inf)
+    x64 = x.astype(f)
     peak = x64.max(axis=1, keepdims=True)
     lp_all = x64 - (peak + np.log(np.exp(x64 - peak).sum(axis=1, keepdims=True)))
-    prefix, pb, pnb = [()], np.zeros(1), np.full(1, -np.inf)
+    prefix, pb, pnb = [()], np.zeros(1, dtype=f), np.full(1, ninf, dtype=f)
+    e_lm = np.zeros(1, dtype=f)
+    alpha, beta = f(alpha), f(beta)
     for t in range(T):
         lp = lp_all[t]
         S = _cut_off(x[t], k)
@@ -127,7 +148,7 @@ def _beam_one(x, W, K):
         last = np.array([p[-1] if p else -1 for p in prefix], dtype=np.int64)
         in_S = np.array([int(c) in rank for c in last], dtype=bool)
         stay_pb = total + lp[0]
-        stay_pnb = np.where(in_S, pnb + lp[np.maximum(last, 0)], -np.inf)
+        stay_pnb = np.where(in_S, pnb + lp[np.maximum(last, 0)], ninf)
         ext = np.where(S[None, :] == last[:, None], pb[:, None], total[:, None]) + lp[S][None, :]        # [n][k]
         where = {p: i for i, p in enumerate(prefix)}
         dropped = np.zeros((n, k), dtype=bool)
@@ -136,14 +157,34 @@ def _beam_one(x, W, K):
                 i, r = where[p[:-1]], rank[p[-1]]
                 stay_pnb[j] = np.logaddexp(stay_pnb[j], ext[i, r])
                 dropped[i, r] = True
-        cand_pb = np.concatenate([stay_pb[:, None], np.full((n, k), -np.inf)], axis=1).reshape(-1)      # candidate order (i, slot)
-        cand_pnb = np.concatenate([stay_pnb[:, None], np.where(dropped, -np.inf, ext)], axis=1).reshape(-1)
+        cand_pb = np.concatenate([stay_pb[:, None], np.full((n, k), ninf, dtype=f)], axis=1).reshape(-1)      # candidate order (i, slot)
+        cand_pnb = np.concatenate([stay_pnb[:, None], np.where(dropped, ninf, ext)], axis=1).reshape(-1)
         cand_total = np.logaddexp(cand_pb, cand_pnb)
         cand_total[~np.isfinite(cand_total)] = -np.inf
-        keep = [q for q in np.argsort(-cand_total, kind="stable")[:W] if cand_total[q] > -np.inf]
+        key = cand_total
+        if lm is not None:
+            cand_lm = np.repeat(e_lm[:, None], k + 1, axis=1)                                              # a stay keeps lm_i
+            cand_len = np.array([len(p) for p in prefix], dtype=f)[:, None] + np.array([0] + [1] * k, dtype=f)[None, :]
+            for i, p in enumerate(prefix):
+                a, b = p[-2] if len(p) > 1 else 0, p[-1] if p else 0
+                for r, c in enumerate(S):
+                    cand_lm[i, 1 + r] = e_lm[i] + lm.logp(a, b, int(c), f)
+            cand_lm = cand_lm.reshape(-1)
+            key = cand_total + alpha * cand_lm + beta * cand_len.reshape(-1)
+            key[cand_total == -np.inf] = -np.inf
+        keep = [q for q in np.argsort(-key, kind="stable")[:W] if key[q] > -np.inf]
         prefix = [prefix[q // (k + 1)] + ((int(S[q % (k + 1) - 1]),) if q % (k + 1) else ()) for q in keep]
         pb, pnb = cand_pb[keep], cand_pnb[keep]
-    return list(zip(prefix, np.logaddexp(pb, pnb)))
+        if lm is not None:
+            e_lm = cand_lm[keep]
+    total = np.logaddexp(pb, pnb)
+    assert total.dtype == f
+    if lm is None:
+        return list(zip(prefix, total))
+    eos = np.array([lm.logp(p[-2] if len(p) > 1 else 0, p[-1] if p else 0, 0, f) for p in prefix], dtype=f)
+    fused = total + alpha * (e_lm + eos) + beta * np.array([len(p) for p in prefix], dtype=f)
+    assert fused.dtype == f
+    return [(prefix[i], total[i], fused[i]) for i in np.argsort(-fused, kind="stable")]
 
 
 def frame_path(prefix, T):
@@ -158,29 +199,81 @@ def frame_path(prefix, T):
     return row + [0] * (T - len(row))
 
 
-def ctc_beam_host(logits, W, K):
+def ctc_beam_host(logits, W, K, lm=None, lm_weight=0.0, lm_bonus=0.0, dtype=np.float64):
     """float64 prefix beam search of logits [B][T][C] (numpy) -> (tokens int32 [B][W][T], length int32 [B][W], score float64 [B][W],
     path int64 [B][T], prob float32 [B][T]): the outputs of ops.ctc_beam_decode, for CPU tensors and for batches outside the
-    kernel's limits.  Any W >= 1 and K >= 1"""
+    kernel's limits.  Any W >= 1 and K >= 1.  With lm (a char_lm.CharLM), lm_weight >= 0 and a finite lm_bonus the search is the
+    fused one of the module docstring and fused float64 [B][W] is a sixth output.  dtype = np.float32 runs all arithmetic, the
+    model's included, in float32 (what float32 costs the kernel is measured on this form)"""
     logits = np.asarray(logits)
     if logits.ndim != 3 or logits.shape[1] < 1 or logits.shape[2] < 2 or W < 1 or K < 1:
         raise ValueError(f"ctc_beam_host needs logits [B][T >= 1][C >= 2], W >= 1 and K >= 1, got {logits.shape}, {W}, {K}")
+    if dtype not in (np.float32, np.float64):
+        raise ValueError(f"ctc_beam_host: dtype must be np.float32 or np.float64, got {dtype!r}")
+    if lm is not None:
+        lm_weight, lm_bonus = check_lm_weights(lm_weight, lm_bonus)
     B, T, _ = logits.shape
     tokens = np.zeros((B, W, T), dtype=np.int32)
     length = np.full((B, W), -1, dtype=np.int32)
     score = np.full((B, W), -np.inf, dtype=np.float64)
+    fused = np.full((B, W), -np.inf, dtype=np.float64)
     path = np.zeros((B, T), dtype=np.int64)
     prob = np.ones((B, T), dtype=np.float32)
     for b in range(B):
-        entries = _beam_one(logits[b], W, K)
-        for w, (p, s) in enumerate(entries):
+        if lm is None and dtype is np.float64:
+            entries = _beam_one(logits[b], W, K)
+        else:
+            entries = _beam_one(logits[b], W, K, lm, lm_weight, lm_bonus, dtype)
+        for w, e in enumerate(entries):
+            p = e[0]
             tokens[b, w, :len(p)] = p
             length[b, w] = len(p)
-            score[b, w] = s
+            score[b, w] = e[1]
+            if lm is not None:
+                fused[b, w] = e[2]
         if entries:
             path[b] = frame_path(entries[0][0], T)
         prob[b, 0] = np.float32(np.exp(score[b, 0]))
-    return tokens, length, score, path, prob
+    return (tokens, length, score, path, prob) if lm is None else (tokens, length, score, path, prob, fused)
+
+
+DEFAULT_LM_WEIGHT = 0.5
+DEFAULT_LM_BONUS = 0.0
+BEAM_LM_MAX_CLASSES = 65535      # C_lm: classes are 16-bit fields of a table key
+BEAM_LM_MAX_SLOTS = 1 << 26
+
+
+def check_lm_weights(lm_weight, lm_bonus):
+    """(alpha, beta) as floats: alpha >= 0 and finite, beta finite; anything else is a ValueError"""
+    for name, v in (("lm_weight", lm_weight), ("lm_bonus", lm_bonus)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if lm_weight < 0:
+        raise ValueError(f"lm_weight must be >= 0, got {lm_weight!r}")
+    return float(lm_weight), float(lm_bonus)
+
+
+def lm_options(opt, attn):
+    """(lm or None, lm_weight, lm_bonus) of an options object: opt.ctc_lm is absent / None (off) or a char_lm.CharLM, opt.lm_weight
+    (default 0.5) and opt.lm_bonus (default 0) its weights.  The model fuses into the CTC beam search, so on a CTC head ctc_lm without
+    ctc_decode='beam', or together with lexicon or candidates, is a ValueError; the attention head ignores the option"""
+    from .char_lm import CharLM
+    lm = getattr(opt, "ctc_lm", None)
+    if lm is None or attn:
+        return None, DEFAULT_LM_WEIGHT, DEFAULT_LM_BONUS
+    if not isinstance(lm, CharLM):
+        raise ValueError(f"ctc_lm must be a CharLM (modules/char_lm.py build_char_lm), got {type(lm).__name__}")
+    if getattr(opt, "ctc_decode", "greedy") != "beam":
+        raise ValueError("ctc_lm fuses into the prefix beam search: set ctc_decode='beam'")
+    for key in ("lexicon", "candidates"):
+        if getattr(opt, key, None) is not None:
+            raise ValueError(f"ctc_lm and {key}: a closed-vocabulary decoder has no use for a language model, set one of them")
+    return (lm,) + check_lm_weights(getattr(opt, "lm_weight", DEFAULT_LM_WEIGHT), getattr(opt, "lm_bonus", DEFAULT_LM_BONUS))
+
+
+def beam_lm_supported(lm):
+    """does mrn_ctc_beam_lm_decode_f32 take this model (beam_supported answers for the batch)"""
+    return 1 <= lm.order <= 3 and lm.C_lm <= BEAM_LM_MAX_CLASSES and len(lm.keys) <= BEAM_LM_MAX_SLOTS
 
 
 def _f64(v):

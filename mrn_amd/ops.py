@@ -2042,13 +2042,40 @@ def greedy_score(idx, prob, label, label_len, canon, mode, eos=0):
     return tokens, result, confidence, packed
 
 
-def ctc_beam_decode(logits, beam_width, top_n):
+class CharLMHandle:
+    """a checked character n-gram model on a device (upload_char_lm): the hash table (keys as int64 bit patterns [size], values fp32
+    [size,2]), the dense unigram arrays fp32 [C_lm], the scalars the kernel takes, and the host model for CPU tensors"""
+
+    def __init__(self, lm, device):
+        import numpy as np
+        from .modules.char_lm import check_char_lm
+        self.lm = lm
+        self.size, self.stored = check_char_lm(lm)
+        self.device = torch.device(device)
+        self.order, self.C_lm, self.max_probe, self.unk_logp = int(lm.order), int(lm.C_lm), int(lm.max_probe), float(lm.unk_logp)
+        self.keys = torch.from_numpy(lm.keys.view(np.int64)).to(device)
+        self.vals = torch.from_numpy(lm.vals).to(device)
+        self.uni_logp = torch.from_numpy(lm.uni_logp.astype(np.float32)).to(device)
+        self.uni_bow = torch.from_numpy(lm.uni_bow.astype(np.float32)).to(device)
+
+
+def upload_char_lm(lm, device):
+    """a CharLM of modules/char_lm.py build_char_lm -> CharLMHandle on `device`.  The model is checked on the host first
+    (char_lm.check_char_lm, once per upload): the kernel trusts the arrays, so a malformed model is a ValueError here and never a launch"""
+    return CharLMHandle(lm, device)
+
+
+def ctc_beam_decode(logits, beam_width, top_n, lm=None, lm_weight=0.0, lm_bonus=0.0):
     """CTC prefix beam search of one batch of CTC-head logits [B,T,C], class 0 the blank (include/mrn_decode.h: mrn_ctc_beam_decode_f32):
     beam_width entries are kept per frame, only the top_n non-blank classes of a frame extend a prefix
     -> (tokens int32 [B,W,T], length int32 [B,W] (-1 = dead slot), score fp32 [B,W] = log-probability of the label, entries in
     descending score; path int64 [B,T], prob fp32 [B,T]: the best entry as the (index, probability) rows greedy_score takes).
     Batch and step strides are honoured (MRN hands out padded-row views); the last dimension is contiguous.  The limits
-    (modules/decoding.py) are the caller's to keep: outside them the call is an error, never a host fallback"""
+    (modules/decoding.py) are the caller's to keep: outside them the call is an error, never a host fallback.
+    With lm = a CharLMHandle (upload_char_lm) on the logits' device the search is fused with that character n-gram model
+    (include/mrn_ctc_lm.h: mrn_ctc_beam_lm_decode_f32; modules/decoding.py): candidates are ranked by score + lm_weight * log p_lm +
+    lm_bonus * length, the entries come in descending fused key, and fused fp32 [B,W], that key, is a sixth output; score stays the
+    acoustic log-probability.  lm_weight < 0 or a non-finite weight is a ValueError"""
     if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
         raise RuntimeError("ctc_beam_decode needs a CUDA (HIP) fp32 tensor [B,T,C] with a contiguous last dimension; there is no "
                            "CPU fallback")
@@ -2060,9 +2087,19 @@ def ctc_beam_decode(logits, beam_width, top_n):
     score = torch.empty(shape[:2], device=logits.device, dtype=torch.float32)
     path = torch.empty(B, T, device=logits.device, dtype=torch.int64)
     prob = torch.empty(B, T, device=logits.device, dtype=torch.float32)
-    call("mrn_ctc_beam_decode_f32", _p(logits), logits.stride(0), logits.stride(1), B, T, C, W, K, _p(tokens), _p(length), _p(score),
-         _p(path), _p(prob), _stream())
-    return tokens, length, score, path, prob
+    if lm is None:
+        call("mrn_ctc_beam_decode_f32", _p(logits), logits.stride(0), logits.stride(1), B, T, C, W, K, _p(tokens), _p(length), _p(score),
+             _p(path), _p(prob), _stream())
+        return tokens, length, score, path, prob
+    from .modules.decoding import check_lm_weights
+    if not isinstance(lm, CharLMHandle) or lm.keys.device != logits.device:
+        raise RuntimeError("ctc_beam_decode: lm must be a CharLMHandle (upload_char_lm) on the device of the logits")
+    alpha, beta = check_lm_weights(lm_weight, lm_bonus)
+    fused = torch.empty(shape[:2], device=logits.device, dtype=torch.float32)
+    call("mrn_ctc_beam_lm_decode_f32", _p(logits), logits.stride(0), logits.stride(1), B, T, C, W, K, _p(tokens), _p(length), _p(score),
+         _p(path), _p(prob), _p(lm.keys), _p(lm.vals), lm.size - 1, lm.max_probe, _p(lm.uni_logp), _p(lm.uni_bow), lm.C_lm, lm.unk_logp,
+         lm.order, alpha, beta, _p(fused), _stream())
+    return tokens, length, score, path, prob, fused
 
 
 LEXICON_SCORE_BYTES = 256 << 20      # the [B][Nc] score table of one mrn_ctc_lexicon_decode_f32 call stays within this

@@ -21,6 +21,13 @@ everything behind the decoding line -- scoring on either path, the returned stri
 is then the label's (pruned) probability instead of the product of the per-frame maxima.  The attention head has no alignments to
 sum over: it ignores the option.
 
+opt.ctc_lm = a CharLM (modules/char_lm.py build_char_lm; absent or None: as above, bit for bit) fuses a character n-gram model into
+that beam search: candidates are ranked by log p_ctc + opt.lm_weight * log p_lm + opt.lm_bonus * length (defaults 0.5 and 0;
+modules/decoding.py), one mrn_ctc_beam_lm_decode_f32 launch per batch with the model checked and uploaded once per call, or the
+float64 host form where the beam decoder takes it.  The best entry by the fused key goes to the unchanged scorer, and its confidence is
+still its acoustic probability.  The options are read only with ctc_decode = "beam" on a CTC head: ctc_lm without it, or together with
+lexicon or candidates, is an error; the attention head ignores the option.
+
 opt.attn_decode = "beam" (absent or "greedy": as above, bit for bit; CTC heads ignore it) decodes an attention head by beam search of
 width opt.beam_width: the evaluation forward is asked for the beam pair (attn_beam=width: one more launch per heads group on the
 same features, modules/decoding.py) and preds_index / preds_max_prob are the best entry's tokens and their probabilities instead of
@@ -180,13 +187,33 @@ def _device_scores(labels, preds_index, preds_max_prob, converter, canon, attn, 
     return out, (tokens, result), {b: st for b, (_, st) in host_rows.items()}
 
 
-def _beam_pair(preds, prediction, width, top_n):
+def _beam_pair(preds, prediction, width, top_n, fusion=None):
     """the beam decoder's (path, prob) for CTC logits [B,T,C], on the device of `preds`: one launch when the kernel takes the batch,
-    else the host form"""
+    else the host form; fusion = a _BeamLM (opt.ctc_lm) or None"""
+    if fusion is not None:
+        return fusion.pair(preds, prediction, width, top_n)
     if preds.is_cuda and D.beam_supported(prediction, preds.size(1), preds.size(2), width, top_n):
         return ops.ctc_beam_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), width, top_n)[3:]
     path, prob = D.ctc_beam_host(preds.detach().cpu().numpy(), width, top_n)[3:]
     return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
+
+
+class _BeamLM:
+    """opt.ctc_lm with its weights for one validation() call; the model is checked and uploaded when the first CUDA batch needs it"""
+
+    def __init__(self, lm, weight, bonus):
+        self.lm, self.weight, self.bonus, self.handle = lm, weight, bonus, None
+
+    def pair(self, preds, prediction, width, top_n):
+        """the fused beam decoder's (path, prob) of the best entry by the fused key; prob[0] is still exp(acoustic score)"""
+        if (preds.is_cuda and D.beam_supported(prediction, preds.size(1), preds.size(2), width, top_n)
+                and D.beam_lm_supported(self.lm)):
+            if self.handle is None:
+                self.handle = ops.upload_char_lm(self.lm, preds.device)
+            return ops.ctc_beam_decode(preds if preds.stride(-1) == 1 else preds.contiguous(), width, top_n, self.handle, self.weight,
+                                       self.bonus)[3:5]
+        path, prob = D.ctc_beam_host(preds.detach().cpu().numpy(), width, top_n, self.lm, self.weight, self.bonus)[3:5]
+        return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
 
 
 class _Lexicon:
@@ -313,6 +340,8 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     if lexicon_words is not None and not attn and ctc_decode == "beam":
         raise ValueError("lexicon and ctc_decode='beam' both replace best-path decoding on a CTC head: set one of them")
     lexicon = _Lexicon(converter, lexicon_words, lexicon_n, shortlist) if lexicon_words is not None and not attn else None
+    ctc_lm, lm_weight, lm_bonus = D.lm_options(opt, attn)
+    fusion = _BeamLM(ctc_lm, lm_weight, lm_bonus) if ctc_lm is not None else None
     cand_fn, cand_n = D.candidates_options(opt)
     candidates = None
     if cand_fn is not None:
@@ -353,7 +382,7 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         elif lexicon is not None:
             preds_index, preds_max_prob = lexicon.pair(preds, opt.Prediction)
         elif ctc_decode == "beam" and not attn:
-            preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n)
+            preds_index, preds_max_prob = _beam_pair(preds, opt.Prediction, beam_width, beam_top_n, fusion)
         elif attn_beam is not None or attn_cands is not None or attn_shortlist is not None:
             preds_index, preds_max_prob = beam_pair
         else:
