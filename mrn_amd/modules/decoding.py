@@ -1064,3 +1064,50 @@ def attn_shortlist_request(attn_shortlist, prediction, is_train, attn_beam=None,
     if "Attn" not in prediction or is_train or torch.is_grad_enabled():
         return None
     return attn_shortlist[0], K, max_dist
+
+
+# ---- one request record for the attention head's second decode -----------------------------------------------------------------------
+# The evaluation forwards of Model, DERNet and MRNNet resolve their four keywords (attn_beam, attn_lexicon, attn_candidates,
+# attn_shortlist) once, with attn_search_request; everything below them takes the record.
+ATTN_SEARCHES = ("beam", "lexicon", "candidates", "shortlist")
+# where (path, prob, word) stand in the output tuple of a kind's search: Attention.beam_search / lexicon_search / score_candidates and
+# the grouped ops of the same names; shortlist_search returns score_candidates' outputs in front of its table
+_BEST_AT = {"beam": (4, 5, None), "lexicon": (4, 5, 6), **dict.fromkeys(("candidates", "shortlist"), (3, 4, 0))}
+
+
+class AttnSearch(namedtuple("AttnSearch", "kind width trie cands words K max_dist", defaults=(None,) * 6)):
+    """the second decode of an evaluation forward: kind is one of ATTN_SEARCHES; width and trie (an ops.TrieHandle; "lexicon" only) of a
+    beam search, cands (an ops.CandidateHandle after with_cand) of "candidates", words (the handle of ops.upload_words), K and max_dist
+    of "shortlist".  Members a kind does not use are None"""
+    __slots__ = ()
+
+    @property
+    def has_word(self):          # does the search name a word of a table (the forward's beam_word)
+        return self.kind != "beam"
+
+    def scoring(self, cand, S):
+        """a shortlist request and the table cand int32 [B,K] computed for it -> the "candidates" request that scores the table"""
+        return AttnSearch("candidates", cands=self.words.with_cand(cand, S))
+
+
+def attn_search_request(prediction, is_train, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
+    """the four keywords of an evaluation forward -> AttnSearch, or None where nothing is decoded a second time (no keyword set, a CTC
+    head, training, grad enabled).  Every check is one of the four *_request functions above, in this order: attn_lexicon without
+    attn_beam is an error whatever the head"""
+    width = attn_beam_request(attn_beam, prediction, is_train)
+    trie = attn_lexicon_request(attn_lexicon, attn_beam)
+    cands = attn_candidates_request(attn_candidates, prediction, is_train, attn_beam)
+    short = attn_shortlist_request(attn_shortlist, prediction, is_train, attn_beam, attn_candidates)
+    if short is not None:
+        return AttnSearch("shortlist", words=short[0], K=short[1], max_dist=short[2])
+    if cands is not None:
+        return AttnSearch("candidates", cands=cands)
+    return None if width is None else AttnSearch("beam" if trie is None else "lexicon", width=width, trie=trie)
+
+
+def best_of(kind, res):
+    """the output tuple of a kind's search -> (path, prob, word or None) of every sample's best entry, whatever the leading dimensions
+    ([B, ...] of one head, [G, B, ...] of a heads group)"""
+    path, prob, word = _BEST_AT[kind]
+    return res[path], res[prob], None if word is None else res[word][..., 0]
+

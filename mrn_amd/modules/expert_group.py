@@ -20,6 +20,7 @@ import torch
 
 from .. import ops
 from ._nn import _pair, packed_weight, require_no_grad, to_nhwc
+from .decoding import ATTN_EOS, best_of
 from .geometry import check_call, geometry_supported, unsupported_geometry_message
 
 
@@ -728,12 +729,17 @@ class HeadsGroup(SequenceGroup):
             return False
         return SequenceGroup.sequence_supported([e.model for e in experts])
 
-    def run_greedy(self, visual, start, feats_out, logits_out, beam=None, keep=None):
+    def _operands(self):
+        """(cols, w_inv): the experts' greedy_args() as ten columns, and the tenth as the grouped launches take it (None in the exact form)"""
+        cols = list(zip(*(e.Prediction.greedy_args() for e in self.experts)))
+        return cols, cols[9] if cols[9][0] is not None else None
+
+    def run_greedy(self, visual, start, feats_out, logits_out, search=None, keep=None):
         """run() for attention experts at evaluation time: start = device int64 tensor whose first element is the start token ([SOS]);
-        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  beam = (width, eos) or (width, eos,
-        trie handle or None): one more launch for the group on the same features, Hproj and operands (run_beam) -> (path [G,B,S], prob
-        [G,B,S]), with a trie also word [G,B]; else None.  keep (a list): takes (features, Hproj, start, operand columns), what
-        run_beam needs to score a candidate table later."""
+        logits_out: list of G [B,S,C_g] padded-row views, every expert with its own class count.  search (a decoding.AttnSearch): one
+        more launch for the group on the same features, Hproj and operands (run_search) -> (path [G,B,S], prob [G,B,S], word [G,B] or
+        None); else None.  keep (a list): takes (features, Hproj, start, operands), what run_search needs to score a candidate table
+        later."""
         G = self.G
         _, B, _, T, Cf = visual.shape
         feat = self.sequence(visual)                                              # [G,B,T,hidden]
@@ -743,46 +749,38 @@ class HeadsGroup(SequenceGroup):
         cells = [h.attention_cell for h in heads]
         S = self.experts[0].opt.batch_max_length + 1
         Hproj = self._linear("i2h", ops.split_hl32(feat), B * T, hidden, [c.i2h.weight for c in cells], None).view(G, B, T, -1)
-        args = [h.greedy_args() for h in heads]      # (etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv) per expert
-        cols = list(zip(*args))
-        ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out,
-                                       w_inv=cols[9] if args[0][9] is not None else None)
+        cols, w_inv = operands = self._operands()    # (etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv) per expert
+        ops.attn_greedy_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], cells[0].hidden_size, S, logits_out, w_inv=w_inv)
         if keep is not None:
-            keep.extend((feat, Hproj, start, cols))
-        return None if beam is None else self.run_beam(feat, Hproj, start, cols, *beam)
+            keep.extend((feat, Hproj, start, operands))
+        return None if search is None else self.run_search(search, feat, Hproj, start, operands)
 
-    def run_beam(self, feat, Hproj, start, cols, width, eos, attn_lexicon=None):
-        """beam search of all G attention experts in lock-step: ONE mrn_attn_beam_decode_* launch on run_greedy's features, Hproj and
-        greedy_args() columns where every head takes the fused form; else every head's own Attention.beam_search (stepwise)
-        -> (path int64 [G,B,S], prob [G,B,S]).  attn_lexicon (the handle of ops.upload_trie, one trie for all experts): the same with
-        mrn_attn_lexicon_decode_* / Attention.lexicon_search -> (path, prob, word int32 [G,B]).  A candidate handle
-        (ops.upload_words(...).with_cand(...)) in its place, width None: every sample's candidate words scored exactly under all G
-        experts, mrn_attn_score_candidates_* / Attention.score_candidates -> (path, prob, word) of each expert's best word"""
+    def run_search(self, req, feat, Hproj, start, operands):
+        """the second decode (req: a decoding.AttnSearch of kind "beam", "lexicon" or "candidates", ending on ATTN_EOS) of all G attention
+        experts in lock-step, on run_greedy's features, Hproj and operands -> (path int64 [G,B,S], prob [G,B,S], word int32 [G,B] or None)
+        of every expert's best entry.  ONE launch where every head takes the fused form: mrn_attn_beam_decode_*, mrn_attn_lexicon_decode_*
+        (one trie for all experts) or mrn_attn_score_candidates_* (every sample's candidate words scored exactly under all G experts);
+        else every head's own Attention.search, stacked"""
         heads = [e.Prediction for e in self.experts]
         G, B, T, D = feat.shape
-        L = self.experts[0].opt.batch_max_length
-        if isinstance(attn_lexicon, ops.CandidateHandle):
-            cands = attn_lexicon
-            if all(h.score_fused(D, T, L + 1, eos, cands.n) for h in heads):
-                res = ops.attn_score_candidates_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos,
-                                                        cands.tokens_dev, cands.lengths_dev, cands.cand_dev, n=cands.n,
-                                                        w_inv=cols[9] if cols[9][0] is not None else None, check=False)
-                return res[3], res[4], res[0][:, :, 0]
-            each = [h.score_candidates(feat[g], start, eos, cands, L) for g, h in enumerate(heads)]
-            return torch.stack([r[3] for r in each]), torch.stack([r[4] for r in each]), torch.stack([r[0][:, 0] for r in each])
-        if attn_lexicon is not None:
-            if all(h.lexicon_fused(D, T, L + 1, eos, width, attn_lexicon) for h in heads):
-                res = ops.attn_lexicon_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,
-                                                      attn_lexicon, w_inv=cols[9] if cols[9][0] is not None else None)
-                return res[4], res[5], res[6][:, :, 0]
-            each = [h.lexicon_search(feat[g], start, eos, width, attn_lexicon, L) for g, h in enumerate(heads)]
-            return torch.stack([r[4] for r in each]), torch.stack([r[5] for r in each]), torch.stack([r[6][:, 0] for r in each])
-        if all(h.beam_fused(D, T, L + 1, eos, width) for h in heads):
-            res = ops.attn_beam_decode_grouped(feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, L + 1, eos, width,
-                                               w_inv=cols[9] if cols[9][0] is not None else None)
-            return res[4], res[5]
-        pairs = [h.beam_search(feat[g], start, eos, width, L)[4:] for g, h in enumerate(heads)]
-        return torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+        S = self.experts[0].opt.batch_max_length + 1
+        cols, w_inv = operands
+        common = (feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, S, ATTN_EOS)
+        if req.kind == "beam":
+            fused = all(h.beam_fused(D, T, S, ATTN_EOS, req.width) for h in heads)
+            grouped = lambda: ops.attn_beam_decode_grouped(*common, req.width, w_inv=w_inv)  # noqa: E731
+        elif req.kind == "lexicon":
+            fused = all(h.lexicon_fused(D, T, S, ATTN_EOS, req.width, req.trie) for h in heads)
+            grouped = lambda: ops.attn_lexicon_decode_grouped(*common, req.width, req.trie, w_inv=w_inv)  # noqa: E731
+        else:
+            c = req.cands
+            fused = all(h.score_fused(D, T, S, ATTN_EOS, c.n) for h in heads)
+            grouped = lambda: ops.attn_score_candidates_grouped(*common, c.tokens_dev, c.lengths_dev, c.cand_dev, n=c.n, w_inv=w_inv,  # noqa: E731
+                                                                check=False)
+        if fused:
+            return best_of(req.kind, grouped())
+        each = [h.search(req, feat[g], start, S - 1) for g, h in enumerate(heads)]
+        return tuple(None if col[0] is None else torch.stack(col) for col in zip(*each))
 
     def run(self, visual, text, feats_out, logits_out):
         """visual: Act with the backbone features [G,B,1,T,C'] (HL32 and / or fp32); feats_out [B,T,G,hidden] (router

@@ -18,7 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..functional import FaninFn, GateTailFn, HeightMeanFn, LinearFn, needs_grad
 from ._nn import to_nhwc
-from .decoding import ATTN_EOS, attn_beam_request, attn_candidates_request, attn_lexicon_request, attn_shortlist_request
+from .decoding import ATTN_EOS, attn_search_request
 from .dm_router import DM_Router
 from .feature_extraction import ResNet_FeatureExtractor, VGG_FeatureExtractor
 from .geometry import check_call, frames
@@ -124,21 +124,33 @@ class Model(nn.Module):
         self.Prediction.to(device)
 
     def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None,
-                attn_candidates=None, attn_shortlist=None):
-        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, attn_beam=attn_beam, attn_lexicon=attn_lexicon,
-                          attn_candidates=attn_candidates, attn_shortlist=attn_shortlist)
-
-    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None,
-              attn_candidates=None, attn_shortlist=None):
-        """SequenceModeling + Prediction on precomputed backbone features.  attn_beam (a width; attention head, evaluation under
-        no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of a beam search on the same features
-        (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's.  attn_lexicon (the handle of
-        ops.upload_trie, beside attn_beam): the search is walked along the lexicon's trie, and the dict also has beam_word [B], the
-        lexicon index of the best entry (-1: no word of the lexicon can be spelled).  attn_candidates (the handle of
-        ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's candidate words are scored exactly
+                attn_candidates=None, attn_shortlist=None, search=None):
+        """attn_beam (a width; attention head, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry
+        of a beam search on the same features (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's.
+        attn_lexicon (the handle of ops.upload_trie, beside attn_beam): the search is walked along the lexicon's trie, and the dict
+        also has beam_word [B], the lexicon index of the best entry (-1: no word of the lexicon can be spelled).  attn_candidates (the
+        handle of ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's candidate words are scored exactly
         (Attention.score_candidates) and the same three keys hold the best word's pair and its table index.  attn_shortlist ((the
         handle of ops.upload_words, K, max_dist or None); instead of both): the K words nearest to the greedy hypothesis (the arg-max
-        of `predict`) are scored exactly (Attention.shortlist_search) and the same three keys hold the best one"""
+        of `predict`) are scored exactly (Attention.shortlist_search) and the same three keys hold the best one.  search: the four as
+        the decoding.AttnSearch an MRNNet has resolved already"""
+        if search is None:
+            search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
+        return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, search=search)
+
+    def _second_decode(self, out, search, feat, text, logits):
+        """the beam_path / beam_prob (and beam_word) of a forward's dict: `search` (a decoding.AttnSearch or None) on the features the
+        greedy decode ran on; a shortlist's hypothesis is the arg-max of the greedy logits"""
+        if search is not None:
+            tokens = ops.argmax_lastdim(logits) if search.kind == "shortlist" else None
+            out["beam_path"], out["beam_prob"], word = self.Prediction.search(search, feat, text, self.opt.batch_max_length, tokens=tokens)
+            if search.has_word:
+                out["beam_word"] = word
+        return out
+
+    def heads(self, visual, text=None, is_train=True, feature_out=None, predict_out=None, search=None):
+        """SequenceModeling + Prediction on precomputed backbone features; search: a decoding.AttnSearch (Model.forward explains the
+        keys it adds to the dict)"""
         feat = self.model.sequence(visual, out=feature_out)
         if self.stages["Pred"] == "CTC":
             if needs_grad(self.Prediction, feat):
@@ -147,24 +159,7 @@ class Model(nn.Module):
                 pred = ops.linear(feat, self.Prediction.weight, self.Prediction.bias, out=predict_out)
         else:
             pred = self.Prediction(feat, text, is_train, batch_max_length=self.opt.batch_max_length, out=predict_out)
-        out = {"predict": pred, "feature": feat}
-        width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
-        trie = attn_lexicon_request(attn_lexicon, attn_beam)
-        cands = attn_candidates_request(attn_candidates, self.stages["Pred"], is_train, attn_beam)
-        short = attn_shortlist_request(attn_shortlist, self.stages["Pred"], is_train, attn_beam, attn_candidates)
-        if short is not None:
-            res = self.Prediction.shortlist_search(feat, text, ATTN_EOS, *short, batch_max_length=self.opt.batch_max_length,
-                                                   tokens=ops.argmax_lastdim(pred))
-            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
-        elif cands is not None:
-            res = self.Prediction.score_candidates(feat, text, ATTN_EOS, cands, self.opt.batch_max_length)
-            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
-        elif width is not None and trie is not None:
-            res = self.Prediction.lexicon_search(feat, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
-            out["beam_path"], out["beam_prob"], out["beam_word"] = res[4], res[5], res[6][:, 0]
-        elif width is not None:
-            out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(feat, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
-        return out
+        return self._second_decode({"predict": pred, "feature": feat}, search, feat, text, pred)
 
     def update_fc(self, hidden_size, nb_classes, device=None):
         fc = nn.Linear(hidden_size, nb_classes)
@@ -326,31 +321,14 @@ class DERNet(Model):
     def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None, attn_lexicon=None, attn_candidates=None,
                 attn_shortlist=None):
         """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon, attn_candidates, attn_shortlist: as
-        Model.heads (the main head's pair and beam_word)"""
+        Model.forward (the main head's pair and beam_word)"""
+        search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
         feat = self._features(image, frozen)
         logits = self._head(self.Prediction, feat, text, is_train)
         aux = self._head(self.aux_Prediction, feat[:, :, -self.out_dim:], text, is_train)
         out = {"logits": logits, "aux_logits": aux, "features": feat}
-        width = attn_beam_request(attn_beam, self.stages["Pred"], is_train)
-        trie = attn_lexicon_request(attn_lexicon, attn_beam)
-        cands = attn_candidates_request(attn_candidates, self.stages["Pred"], is_train, attn_beam)
-        short = attn_shortlist_request(attn_shortlist, self.stages["Pred"], is_train, attn_beam, attn_candidates)
-        if short is not None:
-            res = self.Prediction.shortlist_search(feat if feat.is_contiguous() else feat.contiguous(), text, ATTN_EOS, *short,
-                                                   batch_max_length=self.opt.batch_max_length, tokens=ops.argmax_lastdim(logits))
-            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
-        elif cands is not None:
-            res = self.Prediction.score_candidates(feat if feat.is_contiguous() else feat.contiguous(), text, ATTN_EOS, cands,
-                                                   self.opt.batch_max_length)
-            out["beam_path"], out["beam_prob"], out["beam_word"] = res[3], res[4], res[0][:, 0]
-        elif width is not None:
-            rows = feat if feat.is_contiguous() else feat.contiguous()
-            if trie is not None:
-                res = self.Prediction.lexicon_search(rows, text, ATTN_EOS, width, trie, self.opt.batch_max_length)
-                out["beam_path"], out["beam_prob"], out["beam_word"] = res[4], res[5], res[6][:, 0]
-            else:
-                out["beam_path"], out["beam_prob"] = self.Prediction.beam_search(rows, text, ATTN_EOS, width, self.opt.batch_max_length)[4:]
-        return out
+        rows = feat if search is None or feat.is_contiguous() else feat.contiguous()
+        return self._second_decode(out, search, rows, text, logits)
 
     def update_fc(self, hidden_size, nb_classes, device=None):
         if not tasks_supported(len(self.model) + 1):
@@ -498,22 +476,20 @@ class MRNNet(nn.Module):
         return (not is_train and self.opt.Prediction == "Attn" and ops.greedy_decode_mode() == "fused"
                 and HeadsGroup.greedy_supported(list(self.model)))
 
-    def _run_heads(self, hg, visual, text, is_train, feats, logits, beam=None, first=0):
-        """beam: None or (width, list that takes (first expert, path [G,B,S], prob [G,B,S]) of the group's beam launch, trie handle or
-        None: with a trie the launch is the lexicon-constrained one and the record also has word [G,B]); ("shortlist", list, None): the
-        list takes (first expert, the group, its features, Hproj, start and operand columns), what run_beam scores a candidate table
-        with once the routing index has given the hypotheses"""
-        if self._greedy_heads(is_train):
-            if beam is not None and beam[0] == "shortlist":
-                kept = []
-                hg.run_greedy(visual, text, feats, logits, keep=kept)
-                beam[1].append((first, hg) + tuple(kept))
-                return
-            pair = hg.run_greedy(visual, text, feats, logits, beam=None if beam is None else (beam[0], ATTN_EOS, beam[2]))
-            if beam is not None:
-                beam[1].append((first,) + pair)
-        else:
+    def _run_heads(self, hg, visual, text, is_train, feats, logits, search=None, parts=None, first=0):
+        """search (a decoding.AttnSearch) with parts (a list): the list takes (first expert, path [G,B,S], prob [G,B,S], word [G,B] or
+        None) of the group's second decode; for a shortlist (first expert, the group, (its features, Hproj, start and operand
+        columns)), what run_search scores a candidate table with once the routing index has given the hypotheses"""
+        if not self._greedy_heads(is_train):
             hg.run(visual, text, feats, logits)
+        elif search is not None and search.kind == "shortlist":
+            kept = []
+            hg.run_greedy(visual, text, feats, logits, keep=kept)
+            parts.append((first, hg, tuple(kept)))
+        else:
+            best = hg.run_greedy(visual, text, feats, logits, search=search)
+            if search is not None:
+                parts.append((first,) + best)
 
     def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None, attn_lexicon=None, attn_candidates=None,
                 attn_shortlist=None):
@@ -522,37 +498,31 @@ class MRNNet(nn.Module):
         a beam search (modules/decoding.py) of the expert the hard routing index picks for each sample, for cross=False of the newest
         expert; one more launch per heads group on the same features, `logits` is still the greedy decoder's.  attn_lexicon (the handle
         of ops.upload_trie, beside attn_beam): the search of every expert is walked along the one trie, and the dict also has beam_word
-        [B], as Model.heads.  attn_candidates (the handle of ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's
+        [B], as Model.forward.  attn_candidates (the handle of ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's
         candidate words are scored exactly under ALL experts in one grouped launch per heads group (a word with a class an expert lacks
         is dead for that expert) and the same three keys hold the routed expert's best word.  attn_shortlist ((the handle of
         ops.upload_words, K, max_dist or None); instead of both): the candidate table is the shortlist of the ROUTED expert's greedy
         hypothesis (the arg-max of `logits`), one table per batch, scored under all experts like attn_candidates'"""
         check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
-        width = attn_beam_request(attn_beam, self.opt.Prediction, is_train)
-        trie = attn_lexicon_request(attn_lexicon, attn_beam)
-        if width is None:                      # (a CTC head, training: the request is ignored like attn_beam)
-            trie = None
-        cands = attn_candidates_request(attn_candidates, self.opt.Prediction, is_train, attn_beam)
-        short = attn_shortlist_request(attn_shortlist, self.opt.Prediction, is_train, attn_beam, attn_candidates)
-        pair = None
+        search = attn_search_request(self.opt.Prediction, is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
+        best = None
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
-            newest = self.model[-1](image, text, is_train, attn_beam=width, attn_lexicon=trie, attn_candidates=cands, attn_shortlist=short)
+            newest = self.model[-1](image, text, is_train, search=search)
             features, index = newest["predict"], None
-            if width is not None or cands is not None or short is not None:
-                pair = (newest["beam_path"], newest["beam_prob"]) + ((newest["beam_word"],) if "beam_word" in newest else ())
+            if search is not None:
+                best = (newest["beam_path"], newest["beam_prob"], newest.get("beam_word"))
         elif is_train == False:  # noqa: E712
-            routed = self.cross_forward_expert(image, text, is_train, attn_beam=width, attn_lexicon=trie, attn_candidates=cands,
-                                               attn_shortlist=short)
+            routed = self.cross_forward_expert(image, text, is_train, search=search)
             features, index = routed[:2]
-            if width is not None or cands is not None or short is not None:
-                pair = routed[2]
+            if search is not None:
+                best = routed[2]
         else:
             features, index = self.cross_forward(image, text, is_train, experts=experts)
         out = {"logits": features, "index": index, "aux_logits": None}
-        if pair is not None:
-            out["beam_path"], out["beam_prob"] = pair[:2]
-            if len(pair) == 3:
-                out["beam_word"] = pair[2]
+        if best is not None:
+            out["beam_path"], out["beam_prob"] = best[:2]
+            if search.has_word:
+                out["beam_word"] = best[2]
         return out
 
     # -- shared by both routed paths -------------------------------------------------------------------
@@ -614,12 +584,20 @@ class MRNNet(nn.Module):
                 parts.append((lg, done))
             return {"parts": parts, "batch": B, "feats": feats}
 
-    def _experts_and_gate(self, image, text, is_train, experts=None, beam=None):
-        """beam: None or (width, empty list, trie handle or None): the list takes (first expert, path [G,B,S], prob [G,B,S]) per heads
-        group / expert, with a trie also word [G,B]; (None, empty list, candidate handle): the same three from the exact scorer;
-        ("shortlist", empty list, None): nothing more is launched, the list takes what cross_forward_expert scores the shortlist with
-        (_run_heads' record per heads group, else (expert index, its features [B,T,D]) per expert)"""
+    def _experts_and_gate(self, image, text, is_train, experts=None, search=None, parts=None):
+        """search (a decoding.AttnSearch) with parts (an empty list): the list takes _run_heads' record per heads group, or per expert
+        (expert, path [1,B,S], prob [1,B,S], word [1,B] or None) from its own forward.  For a shortlist nothing more is launched: the
+        list takes what _shortlist_best scores the table with, _run_heads' record or (expert, None, its features [B,T,D])"""
         I = len(self.model)
+
+        def expert_part(i, res):
+            if search is not None and search.kind == "shortlist":
+                parts.append((i, None, feats[:, :, i, :]))
+            elif search is not None:
+                word = res["beam_word"].unsqueeze(0) if search.has_word else None
+                parts.append((i, res["beam_path"].unsqueeze(0), res["beam_prob"].unsqueeze(0), word))
+
+        own = None if search is None or search.kind == "shortlist" else search      # what an expert's own forward decodes
         B = image.shape[0]
         dev = image.device
         if experts is not None:
@@ -654,13 +632,13 @@ class MRNNet(nn.Module):
                     st.wait_stream(main)
                     with torch.cuda.stream(st):
                         self._run_heads(hg, bg.visual_all(image, as_act=True), text, is_train, feats[:, :, lo:hi, :], logits[lo:hi],
-                                        beam=beam, first=lo)
+                                        search=search, parts=parts, first=lo)
                 for st in streams[:len(halves)]:
                     main.wait_stream(st)
                     image.record_stream(st)
             elif heads is not None:
                 # backbones AND heads in lock-step: one grouped launch per conv layer / Linear / recurrence, one stream
-                self._run_heads(heads, group.visual_all(image, as_act=True), text, is_train, feats, logits, beam=beam)
+                self._run_heads(heads, group.visual_all(image, as_act=True), text, is_train, feats, logits, search=search, parts=parts)
             elif self.expert_streams and I > 1:
                 # Phase 1, one stream: the conv backbones (grouped when the experts allow it, else one after the other).
                 # Phase 2, one HIP stream per expert: BiLSTM / attention decoder are latency-bound launches of 16-32
@@ -675,22 +653,18 @@ class MRNNet(nn.Module):
                 for i, expert in enumerate(self.model):
                     streams[i].wait_stream(main)
                     with torch.cuda.stream(streams[i]):
-                        kw = self._beam_kw(beam)
                         if visuals is None:
-                            res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
+                            res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], search=own)
                         else:
-                            res = expert.heads(visuals[i], text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **kw)
+                            res = expert.heads(visuals[i], text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], search=own)
                             visuals[i].record_stream(streams[i])
-                        if beam is not None:
-                            beam[1].append(self._beam_part(i, res, feats))
+                        expert_part(i, res)
                 for st in streams[:I]:
                     main.wait_stream(st)
                     image.record_stream(st)
             else:
                 for i, expert in enumerate(self.model):
-                    res = expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], **self._beam_kw(beam))
-                    if beam is not None:
-                        beam[1].append(self._beam_part(i, res, feats))
+                    expert_part(i, expert(image, text, is_train, feature_out=feats[:, :, i, :], predict_out=logits[i], search=own))
         r = self.dm_router[0].forward_l2(feats)               # [B,P,I,C]
         r = LinearFn.apply(r.view(B * self.patch, I * self.out_dim), self.channel_route.weight, self.channel_route.bias)
         return logits, r.view(B, self.patch, I)
@@ -704,78 +678,53 @@ class MRNNet(nn.Module):
         w = GateTailFn.apply(r, self.route.weight, self.route.bias, float(self.beta))
         return FaninFn.apply(w, *logits), w
 
-    @staticmethod
-    def _beam_kw(beam):
-        """the request of _experts_and_gate's `beam` as the keywords of an expert's own forward"""
-        if beam is None or beam[0] == "shortlist":
-            return {}
-        if isinstance(beam[2], ops.CandidateHandle):
-            return {"attn_candidates": beam[2]}
-        return {"attn_beam": beam[0], "attn_lexicon": beam[2]}
-
-    @staticmethod
-    def _beam_part(i, res, feats=None):
-        """expert i's record for cross_forward_expert from its own forward's dict; for a shortlist its features, scored later"""
-        if "beam_path" not in res and feats is not None:
-            return (i, feats[:, :, i, :])
-        keys = ("beam_path", "beam_prob") + (("beam_word",) if "beam_word" in res else ())
-        return (i,) + tuple(res[k].unsqueeze(0) for k in keys)
-
-    def cross_forward_expert(self, image, text=None, is_train=True, attn_beam=None, attn_lexicon=None, attn_candidates=None,
-                             attn_shortlist=None):
-        """-> (the routed expert's logits, the hard routing index); with attn_beam (a width) also the routed expert's beam pair
-        (path, prob) [B,S] as a third value, with attn_lexicon (a trie handle) beside it, or with attn_candidates (a candidate handle)
-        or attn_shortlist ((word handle, K, max_dist)) instead of both, (path, prob, word [B])"""
+    def cross_forward_expert(self, image, text=None, is_train=True, search=None):
+        """-> (the routed expert's logits, the hard routing index); with search (a decoding.AttnSearch) also the routed expert's
+        (path [B,S], prob [B,S], word [B] or None) as a third value"""
         with torch.no_grad():
-            beam = None if attn_beam is None else (attn_beam, [], attn_lexicon_request(attn_lexicon, attn_beam))
-            cands = attn_candidates_request(attn_candidates, self.opt.Prediction, is_train, attn_beam)
-            if cands is not None:
-                beam = (None, [], cands)
-            short = attn_shortlist_request(attn_shortlist, self.opt.Prediction, is_train, attn_beam, attn_candidates)
-            if short is not None:
-                beam = ("shortlist", [], None)
-            logits, r = self._experts_and_gate(image, text, is_train, beam=beam)
+            parts = []
+            logits, r = self._experts_and_gate(image, text, is_train, search=search, parts=parts)
             _, index = ops.gate_tail_fwd(r.contiguous(), self.route.weight.view(-1), self.route.bias, float(self.beta), hard=True)
-            pair = None
-            if short is not None:
+            if search is not None and search.kind == "shortlist":
                 routed = ops.select_expert(logits, index)
-                return routed, index, self._shortlist_pair(beam[1], routed, index, text, short)
-            if beam is not None:
-                main = torch.cuda.current_stream() if image.is_cuda else None
-                parts = sorted(beam[1], key=lambda p: p[0])
-                for part in parts:
-                    if main is not None:              # (decoded on a side stream that this stream has waited for)
-                        for t in part[1:]:
-                            t.record_stream(main)
-                stacks = [torch.cat(col) for col in list(zip(*parts))[1:]]      # paths, probs [I,B,S] (and words [I,B])
-                pick, rows = index.view(-1).long(), torch.arange(stacks[0].shape[1], device=stacks[0].device)
-                pair = tuple(t[pick, rows] for t in stacks)
+                return routed, index, self._shortlist_best(parts, routed, index, text, search)
+            best = None if search is None else self._routed(parts, index)
             routed = ops.select_expert(logits, index)
-            return (routed, index) if beam is None else (routed, index, pair)
+            return (routed, index) if search is None else (routed, index, best)
 
-    def _shortlist_pair(self, records, routed, index, text, short):
+    @staticmethod
+    def _routed(parts, index):
+        """parts: (first expert, tensors [G,B,...] or None in their place) per heads group or expert, in any order -> per tensor the rows
+        of the expert `index` picks for each sample, [B,...]"""
+        main = torch.cuda.current_stream() if index.is_cuda else None
+        parts = sorted(parts, key=lambda p: p[0])
+        for part in parts:
+            for t in part[1:]:
+                if main is not None and t is not None:      # (decoded on a side stream that this stream has waited for)
+                    t.record_stream(main)
+        pick = index.view(-1).long()
+        rows = torch.arange(pick.numel(), device=pick.device)
+        return tuple(None if col[0] is None else torch.cat(col)[pick, rows] for col in list(zip(*parts))[1:])
+
+    def _shortlist_best(self, records, routed, index, text, search):
         """the routed expert's (path, prob, word [B]) of the lexicon protocol: the hypotheses are the arg-max of the routed logits [B,S,C]
-        before the first [EOS], their shortlist is the batch's one candidate table, and every heads group (run_beam: one grouped launch)
-        or expert (score_candidates) of `records` scores it on the features its greedy decode ran on"""
-        handle, K, max_dist = short
+        before the first [EOS], their shortlist is the batch's one candidate table, and every heads group (run_search: one grouped
+        launch) or expert (Attention.search) of `records` scores it on the features its greedy decode ran on"""
         L = self.opt.batch_max_length
         main = torch.cuda.current_stream() if routed.is_cuda else None
-        cand, _ = ops.lexicon_shortlist(*ops.hypothesis_of_path(ops.argmax_lastdim(routed), ATTN_EOS), handle, K, max_dist)
-        cands = handle.with_cand(cand, L + 1)
+        cand, _ = ops.lexicon_shortlist(*ops.hypothesis_of_path(ops.argmax_lastdim(routed), ATTN_EOS), search.words, search.K, search.max_dist)
+        scoring = search.scoring(cand, L + 1)
         parts = []
-        for rec in sorted(records, key=lambda p: p[0]):
-            if len(rec) == 2:                         # (expert, its features): a strided slice of the router's feature tensor
-                res = self.model[rec[0]].Prediction.score_candidates(rec[1].contiguous(), text, ATTN_EOS, cands, L)
-                parts.append((res[3].unsqueeze(0), res[4].unsqueeze(0), res[0][:, 0].unsqueeze(0)))
+        for first, hg, kept in sorted(records, key=lambda p: p[0]):
+            if hg is None:                            # one expert; kept: its features, a strided slice of the router's feature tensor
+                best = self.model[first].Prediction.search(scoring, kept.contiguous(), text, L)
+                parts.append((first,) + tuple(t.unsqueeze(0) for t in best))
             else:
-                _, hg, feat, Hproj, start, cols = rec
                 if main is not None:                  # (allocated on a side stream that this stream has waited for)
-                    feat.record_stream(main)
-                    Hproj.record_stream(main)
-                parts.append(hg.run_beam(feat, Hproj, start, cols, None, ATTN_EOS, cands))
-        stacks = [torch.cat(col) for col in zip(*parts)]
-        pick, rows = index.view(-1).long(), torch.arange(stacks[0].shape[1], device=stacks[0].device)
-        return tuple(t[pick, rows] for t in stacks)
+                    kept[0].record_stream(main)
+                    kept[1].record_stream(main)
+                parts.append((first,) + hg.run_search(scoring, *kept))
+        return self._routed(parts, index)
 
     def build_fc(self, hidden_size, nb_classes):
         self.update_fc(hidden_size, nb_classes)

@@ -14,6 +14,11 @@ from ._nn import require_no_grad
 from .hidden_size import check_hidden
 
 
+def _host_result(res):
+    """the arrays of a host form of modules/decoding.py as the tensors its kernel returns: float64 becomes float32"""
+    return tuple(torch.from_numpy(r).to(torch.float32) if r.dtype == "float64" else torch.from_numpy(r) for r in res)
+
+
 class AttentionCell(nn.Module):
     def __init__(self, input_size, hidden_size, num_embeddings):
         super().__init__()
@@ -101,10 +106,45 @@ class Attention(nn.Module):
         return ops.attn_decoder(batch_H, Hproj, eproj, w_h2h, cell.h2h.bias, cell.score.weight,
                                 w_ih_ctx, w_hh, cell.rnn.bias_hh, self.hidden_size, hid=hid, h_state=h, c_state=c, w_inv=w_inv)
 
+    def _fused(self, S, eos):
+        """what beam_fused, lexicon_fused and score_fused share: MRN_ATTN_BEAM (read per call), the kernels' hidden size, steps, classes"""
+        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and self.num_class >= 2
+                and 0 <= eos < self.num_class)
+
+    def _search_operands(self, who, batch_H, sos, eos, batch_max_length, width=None, Hproj=None):
+        """what every search starts with -> (start, batch_H, Hproj, S, eos): the hidden size and the end token (and, where the search
+        has one, the width) checked, start = the start token as a one-element int64 tensor, batch_H contiguous, Hproj = i2h(batch_H)
+        unless the caller has it (None for CPU tensors: the host forms make their own)"""
+        check_hidden(None, "Attn", self.hidden_size)
+        S, eos = int(batch_max_length) + 1, int(eos)
+        if (width is not None and int(width) < 1) or not 0 <= eos < self.num_class:
+            needs, got = ("width >= 1 and ", f"{width}, ") if width is not None else ("", "")
+            raise ValueError(f"{who} needs {needs}0 <= eos < {self.num_class}, got {got}{eos}")
+        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
+        batch_H = batch_H.contiguous()
+        if Hproj is None and batch_H.is_cuda:
+            Hproj = ops.linear(batch_H, self.attention_cell.i2h.weight)
+        return start, batch_H, Hproj, S, eos
+
+    @torch.no_grad()
+    def search(self, req, batch_H, sos, batch_max_length, tokens=None, Hproj=None):
+        """the second decode a decoding.AttnSearch asks for, ending on ATTN_EOS -> (path int64 [B,S], prob [B,S], word int32 [B] or None)
+        of every sample's best entry: the one place that maps a request to the four searches below.  tokens: shortlist_search's; Hproj:
+        score_candidates'"""
+        from .decoding import ATTN_EOS, best_of
+        if req.kind == "beam":
+            res = self.beam_search(batch_H, sos, ATTN_EOS, req.width, batch_max_length)
+        elif req.kind == "lexicon":
+            res = self.lexicon_search(batch_H, sos, ATTN_EOS, req.width, req.trie, batch_max_length)
+        elif req.kind == "candidates":
+            res = self.score_candidates(batch_H, sos, ATTN_EOS, req.cands, batch_max_length, Hproj=Hproj)
+        else:
+            res = self.shortlist_search(batch_H, sos, ATTN_EOS, req.words, req.K, req.max_dist, batch_max_length, tokens=tokens)
+        return best_of(req.kind, res)
+
     def beam_fused(self, D, T, S, eos, width):
         """does beam_search take the fused launch (mrn_attn_beam_decode_*): its limits, the LDS budget and MRN_ATTN_BEAM (read per call)"""
-        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and self.num_class >= 2
-                and 0 <= eos < self.num_class and ops.attn_beam_whole_context(D, T, width, self.x3_ok()))
+        return self._fused(S, eos) and ops.attn_beam_whole_context(D, T, width, self.x3_ok())
 
     @torch.no_grad()
     def beam_search(self, batch_H, sos, eos, width, batch_max_length=25):
@@ -112,16 +152,9 @@ class Attention(nn.Module):
         tensor whose first element is the start token -> (tokens int32 [B,W,S], length int32 [B,W], score [B,W], logp [B,W,S],
         path int64 [B,S], prob [B,S]), entries in descending score.  One launch where the kernel's limits and the LDS budget allow,
         otherwise (or under MRN_ATTN_BEAM=stepwise) the step loop of forward() on the B * W-row batch.  Inference only (no_grad)"""
-        check_hidden(None, "Attn", self.hidden_size)
-        W, S, eos = int(width), int(batch_max_length) + 1, int(eos)
-        if W < 1 or not 0 <= eos < self.num_class:
-            raise ValueError(f"beam_search needs width >= 1 and 0 <= eos < {self.num_class}, got {width}, {eos}")
-        cell = self.attention_cell
         B, T, D = batch_H.shape
-        dev = batch_H.device
-        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=dev)
-        batch_H = batch_H.contiguous()
-        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        start, batch_H, Hproj, S, eos = self._search_operands("beam_search", batch_H, sos, eos, batch_max_length, width)
+        W = int(width)
         if self.beam_fused(D, T, S, eos, W):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
             return ops.attn_beam_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
@@ -130,8 +163,7 @@ class Attention(nn.Module):
 
     def lexicon_fused(self, D, T, S, eos, width, trie):
         """does lexicon_search take the fused launch (mrn_attn_lexicon_decode_*): beam_fused's limits with the lexicon launch's LDS sum"""
-        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and self.num_class >= 2
-                and 0 <= eos < self.num_class and trie.depth <= S - 1 and ops.attn_lexicon_whole_context(D, T, width, self.x3_ok()))
+        return self._fused(S, eos) and trie.depth <= S - 1 and ops.attn_lexicon_whole_context(D, T, width, self.x3_ok())
 
     @torch.no_grad()
     def lexicon_search(self, batch_H, sos, eos, width, trie_handle, batch_max_length=25):
@@ -140,23 +172,15 @@ class Attention(nn.Module):
         entry's word, -1 for a dead slot).  One launch where the kernel's limits and the LDS budget allow, otherwise (or under
         MRN_ATTN_BEAM=stepwise) beam_search's step loop with the same constraint; CPU tensors go to decoding.attn_lexicon_host"""
         from .decoding import attn_lexicon_host
-        check_hidden(None, "Attn", self.hidden_size)
-        W, S, eos = int(width), int(batch_max_length) + 1, int(eos)
-        if W < 1 or not 0 <= eos < self.num_class:
-            raise ValueError(f"lexicon_search needs width >= 1 and 0 <= eos < {self.num_class}, got {width}, {eos}")
         if not isinstance(trie_handle, ops.TrieHandle):
             raise ValueError(f"lexicon_search needs the handle of ops.upload_trie, got {type(trie_handle).__name__}")
-        if trie_handle.depth > S - 1:
-            raise ValueError(f"lexicon_search: the longest word has {trie_handle.depth} classes, more than batch_max_length={S - 1}")
-        if not batch_H.is_cuda:
-            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
-            res = attn_lexicon_host(self.state_dict(), batch_H, first, eos, W, S - 1, trie_handle.trie)
-            return tuple(torch.from_numpy(r).to(torch.float32) if r.dtype == "float64" else torch.from_numpy(r) for r in res)
-        cell = self.attention_cell
+        if trie_handle.depth > int(batch_max_length):
+            raise ValueError(f"lexicon_search: the longest word has {trie_handle.depth} classes, more than batch_max_length={int(batch_max_length)}")
         B, T, D = batch_H.shape
-        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
-        batch_H = batch_H.contiguous()
-        Hproj = ops.linear(batch_H, cell.i2h.weight)
+        start, batch_H, Hproj, S, eos = self._search_operands("lexicon_search", batch_H, sos, eos, batch_max_length, width)
+        W = int(width)
+        if not batch_H.is_cuda:
+            return _host_result(attn_lexicon_host(self.state_dict(), batch_H, int(start[0]), eos, W, S - 1, trie_handle.trie))
         if self.lexicon_fused(D, T, S, eos, W, trie_handle):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
             return ops.attn_lexicon_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
@@ -166,8 +190,7 @@ class Attention(nn.Module):
     def score_fused(self, D, T, S, eos, n):
         """does score_candidates take the fused launch (mrn_attn_score_candidates_*): its limits, the LDS budget and MRN_ATTN_BEAM (read
         per call: "stepwise" forces the step form of every search and scorer on the attention head)"""
-        return (ops.attn_beam_mode() == "fused" and self.hidden_size == 256 and 1 <= S <= 512 and 2 <= self.num_class <= 65535
-                and 0 <= eos < self.num_class and 1 <= n <= 16 and ops.attn_score_whole_context(D, T, self.x3_ok()))
+        return self._fused(S, eos) and self.num_class <= 65535 and 1 <= n <= 16 and ops.attn_score_whole_context(D, T, self.x3_ok())
 
     SCORE_ROWS_BYTES = 256 << 20      # the stepwise scorer's (sample, slot) rows go in chunks whose features and logits stay within this
 
@@ -180,25 +203,15 @@ class Attention(nn.Module):
         CPU tensors go to decoding.attn_candidates_host.  Hproj: i2h(batch_H) where the caller has it already.  Inference only
         (no_grad)"""
         from .decoding import attn_candidates_host
-        check_hidden(None, "Attn", self.hidden_size)
-        S, eos = int(batch_max_length) + 1, int(eos)
         if not isinstance(handle, ops.CandidateHandle) or handle.cand is None:
             raise ValueError(f"score_candidates needs the handle of ops.upload_words(...).with_cand(...), got {type(handle).__name__}")
-        if not 0 <= eos < self.num_class:
-            raise ValueError(f"score_candidates needs 0 <= eos < {self.num_class}, got {eos}")
         B, T, D = batch_H.shape
         if handle.cand.shape[0] != B:
             raise ValueError(f"score_candidates: {handle.cand.shape[0]} candidate rows for {B} samples")
+        start, batch_H, Hproj, S, eos = self._search_operands("score_candidates", batch_H, sos, eos, batch_max_length, Hproj=Hproj)
         if not batch_H.is_cuda:
-            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
-            res = attn_candidates_host(self.state_dict(), batch_H, first, eos, handle.tokens, handle.lengths, handle.cand, handle.n, S - 1,
-                                       want_logp=want_logp)
-            return tuple(torch.from_numpy(r).to(torch.float32) if r.dtype == "float64" else torch.from_numpy(r) for r in res)
-        cell = self.attention_cell
-        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
-        batch_H = batch_H.contiguous()
-        if Hproj is None:
-            Hproj = ops.linear(batch_H, cell.i2h.weight)
+            return _host_result(attn_candidates_host(self.state_dict(), batch_H, int(start[0]), eos, handle.tokens, handle.lengths, handle.cand,
+                                                     handle.n, S - 1, want_logp=want_logp))
         tokens, lengths, cand = handle.tokens_dev, handle.lengths_dev, handle.cand_dev
         if self.score_fused(D, T, S, eos, handle.n):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
@@ -222,24 +235,15 @@ class Attention(nn.Module):
         (decoding.attn_beam_host at width 1 is greedy decoding).  tokens int64 [B,S]: the greedy tokens where the caller has decoded
         already (the arg-max of the forward's logits): no greedy launch then.  Inference only (no_grad)"""
         from . import decoding as D
-        check_hidden(None, "Attn", self.hidden_size)
-        S, eos = int(batch_max_length) + 1, int(eos)
         if not isinstance(handle, ops.CandidateHandle):
             raise ValueError(f"shortlist_search needs the handle of ops.upload_words, got {type(handle).__name__}")
-        if not 0 <= eos < self.num_class:
-            raise ValueError(f"shortlist_search needs 0 <= eos < {self.num_class}, got {eos}")
-        B, T, Dm = batch_H.shape
+        start, batch_H, Hproj, S, eos = self._search_operands("shortlist_search", batch_H, sos, eos, batch_max_length)
         if not batch_H.is_cuda:
-            first = int(sos.reshape(-1)[0]) if torch.is_tensor(sos) else int(sos)
-            path = D.attn_beam_host(self.state_dict(), batch_H, first, eos, 1, S - 1)[4] if tokens is None else tokens.numpy()
+            path = D.attn_beam_host(self.state_dict(), batch_H, int(start[0]), eos, 1, S - 1)[4] if tokens is None else tokens.numpy()
             hyp, hyp_len = D.hypothesis_of_path(path, eos)
             cand, dist = D.lexicon_shortlist_host(hyp, hyp_len, handle.tokens, handle.lengths, K, max_dist)
             res = self.score_candidates(batch_H, sos, eos, handle.with_cand(cand, S), S - 1, want_logp=want_logp)
             return res + (torch.from_numpy(cand), torch.from_numpy(dist))
-        cell = self.attention_cell
-        start = sos.reshape(-1)[:1].contiguous() if torch.is_tensor(sos) else torch.tensor([int(sos)], dtype=torch.int64, device=batch_H.device)
-        batch_H = batch_H.contiguous()
-        Hproj = ops.linear(batch_H, cell.i2h.weight)
         if tokens is None and ops.greedy_decode_mode() == "fused":
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
             tokens = ops.attn_greedy_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,

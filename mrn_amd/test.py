@@ -99,6 +99,11 @@ def edit_distance(a, b):
     return prev[-1]
 
 
+def _search_option(shortlist, candidates, lexicon=False):
+    """the option behind an attention head's second decode, as an error names it"""
+    return "lexicon_shortlist" if shortlist else "candidates" if candidates else "attn_lexicon" if lexicon else "attn_decode='beam'"
+
+
 def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
     """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
     attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits; attn_lexicon (a
@@ -114,13 +119,8 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
             out = model(image, is_train=False)
     else:
         sos = torch.full((image.size(0),), converter.dict["[SOS]"], dtype=torch.long, device=image.device)
-        kw = {} if attn_beam is None else {"attn_beam": attn_beam}
-        if attn_lexicon is not None:
-            kw["attn_lexicon"] = attn_lexicon
-        if attn_candidates is not None:
-            kw["attn_candidates"] = attn_candidates
-        if attn_shortlist is not None:
-            kw["attn_shortlist"] = attn_shortlist
+        kw = {k: v for k, v in (("attn_beam", attn_beam), ("attn_lexicon", attn_lexicon), ("attn_candidates", attn_candidates),
+                                ("attn_shortlist", attn_shortlist)) if v is not None}
         if val_choose == "FF":
             out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
@@ -131,7 +131,7 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
     if attn_beam is None and attn_candidates is None and attn_shortlist is None:
         return logits
     if "beam_path" not in out:
-        what = "lexicon_shortlist" if attn_shortlist is not None else "attn_decode='beam'" if attn_candidates is None else "candidates"
+        what = _search_option(attn_shortlist is not None, attn_candidates is not None)
         raise RuntimeError(f"{what}: the evaluation forward returned no beam pair (it runs under torch.no_grad() only)")
     return logits, (out["beam_path"], out["beam_prob"])
 
@@ -347,8 +347,7 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     if cand_fn is not None:
         candidates = _Candidates(converter, cand_fn, evaluation_loader, attn, opt.batch_max_length, cand_n)
     if (attn_beam is not None or attn_shortlist is not None or (attn and candidates is not None)) and converter.dict["[EOS]"] != D.ATTN_EOS:
-        what = ("lexicon_shortlist" if attn_shortlist is not None else "candidates" if candidates is not None
-                else "attn_lexicon" if attn_lexicon is not None else "attn_decode='beam'")
+        what = _search_option(attn_shortlist is not None, candidates is not None, attn_lexicon is not None)
         raise ValueError(f"{what} ends an entry on token {D.ATTN_EOS}, the converter's [EOS] is {converter.dict['[EOS]']}")
     for image_tensors, labels in evaluation_loader:
         batch_size = image_tensors.size(0)
