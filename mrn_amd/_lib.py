@@ -1,8 +1,8 @@
 """ctypes binding of libmrn_hip.so.
 
 Signatures are parsed from include/mrn_hip.h, include/mrn_decode.h, include/mrn_attn_beam.h, include/mrn_lexicon.h,
-include/mrn_attn_lexicon.h, include/mrn_attn_score.h, include/mrn_shortlist.h, include/mrn_herding.h and include/mrn_ctc_lm.h, so the
-headers are the single source of truth for the C ABI.
+include/mrn_attn_lexicon.h, include/mrn_attn_score.h, include/mrn_shortlist.h, include/mrn_herding.h, include/mrn_ctc_lm.h and
+include/mrn_attn_lm.h, so the headers are the single source of truth for the C ABI.
 There is no CPU fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
@@ -24,6 +24,7 @@ ATTN_SCORE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_at
 SHORTLIST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_shortlist.h")     # lexicon shortlists by edit distance
 HERDING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_herding.h")     # herding selection for the rehearsal memory
 CTC_LM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_ctc_lm.h")     # CTC beam search with a character n-gram model
+ATTN_LM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrn_attn_lm.h")     # the same on the attention head
 
 _CTYPES = {
     "int": ctypes.c_int,
@@ -81,7 +82,8 @@ class _Lib:
         self._protos = {**parse_header(), **parse_header(DECODE_HEADER_PATH), **parse_header(ATTN_BEAM_HEADER_PATH),
                         **parse_header(LEXICON_HEADER_PATH), **parse_header(ATTN_LEXICON_HEADER_PATH),
                         **parse_header(ATTN_SCORE_HEADER_PATH), **parse_header(SHORTLIST_HEADER_PATH),
-                        **parse_header(HERDING_HEADER_PATH), **parse_header(CTC_LM_HEADER_PATH)}
+                        **parse_header(HERDING_HEADER_PATH), **parse_header(CTC_LM_HEADER_PATH),
+                        **parse_header(ATTN_LM_HEADER_PATH)}
         for name, (ret, argtypes, _) in self._protos.items():
             fn = getattr(dll, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = _CTYPES[ret]

@@ -1,10 +1,12 @@
-// Attention decoders: teacher-forced, greedy, beam and lexicon-constrained beam, one persistent kernel each around one shared
-// attention-cell step; their launch rules and entry points.
+// Attention decoders: teacher-forced, greedy, beam, lexicon-constrained beam and beam with a character n-gram model, one persistent
+// kernel each around one shared attention-cell step; their launch rules and entry points.
 //
 // Reference: modules/prediction.py:38-118 (Attention / AttentionCell, 26 decode steps).  The workgroup geometry and the MFMA
 // helpers are recurrent.hpp's, shared with the BiLSTM layer (lstm.hip) and the backward (attn_bwd.hip).
+#include "char_lm.hpp"
 #include "hl32.hpp"
 #include "recurrent.hpp"
+#include <math.h>
 #include <stdlib.h>
 
 namespace {
@@ -575,9 +577,33 @@ struct LexTrie {
 };
 constexpr int LEX_LDS_MORE = 4 * (2 * BT + BT * BT);         // the node row, its next-step twin and the candidate-node plane
 
-// the body of attn_beam_kernel (LEX = false: `lex` is not read) and attn_lexicon_kernel (LEX = true)
-template <bool X3, bool LEX>
-__device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTrie* lex) {
+// Shallow fusion of a character n-gram model into the beam search (attn_beam_lm_kernel, include/mrn_attn_lm.h; the algorithm is stated in
+// mrn_amd/modules/decoding.py): the model of char_lm.hpp, one for all experts of a launch.  What differs from the beam:
+//   per row in LDS the last two LM symbols (a << 16 | b, 0 at the start = begin of text), the LM sum, the length in characters and the
+//       fused key the row was kept by
+//   (8) an unfinished row proposes its N = n_prop best classes (N scans instead of W; W <= N <= 16); lane q < N keeps proposal q in
+//       registers and evaluates the LM term of its own class (one lm_logp: at most three probes of at most max_probe slots each): eos
+//       reads as the end of text (symbol 0), class 0 scores unk_logp flat; key = acoustic + alpha * (lm + term) + beta * len' goes to a
+//       fourth candidate plane and lm + term to a fifth.  A finished row proposes itself with its key unchanged
+//   (9) ranks the W x N proposals by the key plane and carries the acoustic value, class and logp as before, and the next context
+//       (b, symbol), LM sum, length and key
+//   (10) moves them with the parent; the tail also writes fused [B][W] = the key, -inf for a dead slot
+// score and logp stay acoustic.  With alpha = beta = 0 the key is the acoustic value and, N >= W, the survivors are the beam's (unless
+// rounding gives a proposal behind a row's W-th the very float of one in front of it and a lower class: the tie rule then takes it).
+// The host checks the arrays once per model (ops.upload_char_lm); contexts and classes are below 65535 (beam_grouped)
+struct BeamLMParams {
+  CharLMTable m;
+  float alpha, beta;
+  int n_prop;
+  float* fused[MAX_GROUPS];         // per group [B][W]
+};
+constexpr int LM_LDS_MORE = 4 * (8 * BT + 2 * BT * BT);       // context, LM sum, length, key, their next-step twins + the key and LM-sum planes
+
+// the body of attn_beam_kernel (LEX = LM = false: `lex` and `lm` are not read), attn_lexicon_kernel (LEX = true) and attn_beam_lm_kernel
+// (LM = true)
+template <bool X3, bool LEX, bool LM = false>
+__device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTrie* lex, const BeamLMParams* lm = nullptr) {
+  static_assert(!(LEX && LM), "no fusion in the trie decoder");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int gi, tile_;
   group_tile(grp.groups, grp.tiles, grp.pinned, gi, tile_);
@@ -605,6 +631,17 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
   int* node_lds = reinterpret_cast<int*>(cand_lp + BT * BT);      // LEX only: LEX_LDS_MORE
   int* nnode = node_lds + BT;
   int* cand_n = nnode + BT;
+  int* ctx_lds = node_lds;                                        // LM only (never with LEX): LM_LDS_MORE
+  float* lms_lds = reinterpret_cast<float*>(ctx_lds + BT);
+  int* len_lds = reinterpret_cast<int*>(lms_lds + BT);
+  float* key_lds = reinterpret_cast<float*>(len_lds + BT);
+  int* nctx = reinterpret_cast<int*>(key_lds + BT);
+  float* nlms = reinterpret_cast<float*>(nctx + BT);
+  int* nlen = reinterpret_cast<int*>(nlms + BT);
+  float* nkey = reinterpret_cast<float*>(nlen + BT);
+  float* cand_k = nkey + BT;
+  float* cand_lm = cand_k + BT * BT;
+  const int NP = LM ? lm->n_prop : W;         // proposals of an unfinished row
   const int b0 = v.b0, Bend = v.Bend, nrows = v.nrows, t_ = v.t_, lane = v.lane, wave = v.wave, rbase = v.rbase, j = v.j;
   float* const row_scr = bp.scratch + (long)tile_ * BT * (CP + 3 * S);      // [16][CP]
   int* const hist_par = reinterpret_cast<int*>(row_scr + (long)BT * CP);   // [S][16]
@@ -617,6 +654,12 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
     score_lds[t_] = (t_ < nrows && t_ % W == 0 && b0 + t_ / W < Bend) ? 0.f : -INFINITY;      // one live entry per sample
     fin_lds[t_] = 0;
     if constexpr (LEX) node_lds[t_] = 0;
+    if constexpr (LM) {
+      ctx_lds[t_] = 0;
+      lms_lds[t_] = 0.f;
+      len_lds[t_] = 0;
+      key_lds[t_] = score_lds[t_];
+    }
   }
   float c[4] = {0.f, 0.f, 0.f, 0.f};
   __syncthreads();
@@ -645,25 +688,42 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
       const int row = wave;
       const float sc = score_lds[row];
       const bool live = row < nrows && b0 + row / W < Bend && sc > -INFINITY;
-      if (lane < W) {
+      if (lane < NP) {
         cand_v[row * BT + lane] = -INFINITY;
         cand_c[row * BT + lane] = 0x7fffffff;
         cand_lp[row * BT + lane] = 0.f;
         if constexpr (LEX) cand_n[row * BT + lane] = 0;
+        if constexpr (LM) {
+          cand_k[row * BT + lane] = -INFINITY;
+          cand_lm[row * BT + lane] = 0.f;
+        }
       }
       const int node = LEX ? node_lds[row] : 0;
+      const int ctx = LM ? ctx_lds[row] : 0;  // LM: the row's context, LM sum and length
+      const float lms = LM ? lms_lds[row] : 0.f;
+      const int len = LM ? len_lds[row] : 0;
       if (lane == 0) {                       // the next step's row, dead until (9) fills it
         nsc[row] = -INFINITY;
         npar[row] = row;
         ntok[row] = eos;
         nlp[row] = 0.f;
         if constexpr (LEX) nnode[row] = node;
+        if constexpr (LM) {
+          nctx[row] = ctx;
+          nlms[row] = lms;
+          nlen[row] = len;
+          nkey[row] = -INFINITY;
+        }
       }
       if (live && fin_lds[row]) {
         if (lane == 0) {
           cand_v[row * BT] = sc;
           cand_c[row * BT] = eos;
           if constexpr (LEX) cand_n[row * BT] = node;
+          if constexpr (LM) {                // its key already holds the end-of-text term
+            cand_k[row * BT] = key_lds[row];
+            cand_lm[row * BT] = lms;
+          }
         }
       } else if (live) {
         const float* x = row_scr + (long)row * CP;
@@ -689,7 +749,9 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
           e1 = lex->child_off[node + 1];
           ends = lex->word_of[node] >= 0;
         }
-        for (int q = 0; q < W; ++q) {
+        float mv = -INFINITY;                 // LM: proposal `lane` of the row, kept by its lane
+        int mc = 0x7fffffff;
+        for (int q = 0; q < NP; ++q) {
           float bv = -INFINITY;
           int bc = 0x7fffffff;
           int bn = 0;
@@ -736,7 +798,12 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
             }
           }
           if (bc >= C) break;                 // fewer than W classes
-          if (lane == 0) {
+          if constexpr (LM) {
+            if (lane == q) {
+              mv = bv;
+              mc = bc;
+            }
+          } else if (lane == 0) {
             const float lp = bv - lse;
             const float cv = sc + lp;
             cand_v[row * BT + q] = cv == cv ? cv : -INFINITY;
@@ -747,30 +814,55 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
           pv = bv;
           pc = bc;
         }
+        if constexpr (LM) {
+          if (mc < C) {                       // (lanes < NP that found a class)
+            const int a = (int)((unsigned)ctx >> 16), b = ctx & 0xffff;      // (classes up to 65534: the shift is unsigned)
+            const float term = mc == eos ? lm_logp(lm->m, a, b, 0) : mc == 0 ? lm->m.unk_logp : lm_logp(lm->m, a, b, mc);
+            const float lp = mv - lse;
+            float cv = sc + lp;
+            cv = cv == cv ? cv : -INFINITY;
+            const float nl = lms + term;
+            const float key = cv + lm->alpha * nl + lm->beta * (float)(len + (mc == eos ? 0 : 1));
+            cand_v[row * BT + lane] = cv;
+            cand_c[row * BT + lane] = mc;
+            cand_lp[row * BT + lane] = lp;
+            cand_k[row * BT + lane] = key == key ? key : -INFINITY;
+            cand_lm[row * BT + lane] = nl;
+          }
+        }
       }
     }
     __syncthreads();
     // (9) rank every candidate among its sample's
     if (t_ < BT * BT) {
       const int row = t_ >> 4, q = t_ & 15;
-      if (row < nrows && q < W) {
-        const float v = cand_v[t_];
+      const float* cand_r = LM ? cand_k : cand_v;      // the plane the candidates are ranked by
+      if (row < nrows && q < NP) {
+        const float v = cand_r[t_];
         if (v > -INFINITY) {
           const int cc = cand_c[t_];
           const int r0 = (row / W) * W;
           int rank = 0;
           for (int i = r0; i < r0 + W; ++i)
-            for (int k = 0; k < W; ++k) {
-              const float ov = cand_v[i * BT + k];
+            for (int k = 0; k < NP; ++k) {
+              const float ov = cand_r[i * BT + k];
               const int oc = cand_c[i * BT + k];
               rank += (ov > v || (ov == v && (i < row || (i == row && oc < cc)))) ? 1 : 0;
             }
           if (rank < W) {
-            nsc[r0 + rank] = v;
+            nsc[r0 + rank] = LM ? cand_v[t_] : v;
             npar[r0 + rank] = row;
             ntok[r0 + rank] = cc;
             nlp[r0 + rank] = cand_lp[t_];
             if constexpr (LEX) nnode[r0 + rank] = cand_n[t_];
+            if constexpr (LM) {
+              nkey[r0 + rank] = v;
+              nlms[r0 + rank] = cand_lm[t_];
+              const bool fin = fin_lds[row] != 0;      // a finished parent keeps its context and length
+              const int pctx = ctx_lds[row];
+              nctx[r0 + rank] = fin ? pctx : (int)(((unsigned)pctx & 0xffffu) << 16 | (unsigned)(cc == eos ? 0 : cc));
+              nlen[r0 + rank] = len_lds[row] + (!fin && cc != eos ? 1 : 0);
+            }
           }
         }
       }
@@ -800,6 +892,12 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
       tok_lds[t_] = tk;
       fin_lds[t_] = tk == eos ? 1 : 0;
       if constexpr (LEX) node_lds[t_] = nnode[t_];
+      if constexpr (LM) {
+        ctx_lds[t_] = nctx[t_];
+        lms_lds[t_] = nlms[t_];
+        len_lds[t_] = nlen[t_];
+        key_lds[t_] = nkey[t_];
+      }
       const unsigned long long open = __ballot(v > -INFINITY && tk != eos);    // (threads 0 ... 15: one wave)
       if (t_ == 0) flag_lds[0] = (open & 0xffffull) != 0 ? 1 : 0;
     }
@@ -849,6 +947,7 @@ __device__ __forceinline__ void attn_beam_body(const BeamGroup& grp, const LexTr
       bp.length[(long)b * W + q] = live ? (first < S ? first + 1 : S) : -1;
       bp.score[(long)b * W + q] = live ? sc : -INFINITY;
       if constexpr (LEX) lex->word[gi][(long)b * W + q] = live ? lex->word_of[node_lds[row]] : -1;
+      if constexpr (LM) lm->fused[gi][(long)b * W + q] = live ? key_lds[row] : -INFINITY;
     }
   }
 }
@@ -861,6 +960,11 @@ __global__ __launch_bounds__(NTH) void attn_beam_kernel(const BeamGroup grp) {
 template <bool X3>
 __global__ __launch_bounds__(NTH) void attn_lexicon_kernel(const BeamGroup grp, const LexTrie lex) {
   attn_beam_body<X3, true>(grp, &lex);
+}
+
+template <bool X3>
+__global__ __launch_bounds__(NTH) void attn_beam_lm_kernel(const BeamGroup grp, const BeamLMParams lm) {
+  attn_beam_body<X3, false, true>(grp, nullptr, &lm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1337,14 +1441,25 @@ MRN_EXPORT int mrn_embed_gather_f32(const int64_t* idx, int64_t idx_stride, cons
 
 // ---- beam-search decoding on the attention head: attn_beam_kernel (include/mrn_attn_beam.h) ----------------
 // the whole-context tile plus the beam state (BEAM_LDS_EXTRA); there is no chunked form.  lex: null, or the trie of attn_lexicon_kernel
-// (include/mrn_attn_lexicon.h), whose node rows and candidate-node plane are LEX_LDS_MORE bytes on top
-static int beam_launch(BeamGroup& grp, const LexTrie* lex, int groups, int D, int T, hipStream_t st) {
+// (include/mrn_attn_lexicon.h), whose node rows and candidate-node plane are LEX_LDS_MORE bytes on top; lm: null, or the model of
+// attn_beam_lm_kernel (include/mrn_attn_lm.h), whose row state and two candidate planes are LM_LDS_MORE bytes on top (never both)
+static int beam_launch(BeamGroup& grp, const LexTrie* lex, int groups, int D, int T, hipStream_t st, const BeamLMParams* lm = nullptr) {
   grp.groups = groups;
   const int B = grp.g[0].g.a.B;
   grp.tiles = ceil_div(B, BT / grp.W);       // 16 / W samples per workgroup
   const dim3 grid = attn_grid(groups, grp.tiles, true, grp.pinned);
   const bool x3 = grp.g[0].g.a.w_inv != nullptr;
-  const size_t lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) + (lex ? LEX_LDS_MORE : 0);
+  const size_t lds = attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA) + (lex ? LEX_LDS_MORE : 0) + (lm ? LM_LDS_MORE : 0);
+  if (lm) {
+    if (lds > 64 * 1024) {
+      (void)hipFuncSetAttribute(x3 ? (const void*)attn_beam_lm_kernel<true> : (const void*)attn_beam_lm_kernel<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    if (x3) hipLaunchKernelGGL(attn_beam_lm_kernel<true>, grid, dim3(NTH), lds, st, grp, *lm);
+    else hipLaunchKernelGGL(attn_beam_lm_kernel<false>, grid, dim3(NTH), lds, st, grp, *lm);
+    MRN_LAUNCH_CHECK("attn_beam_lm");
+    return MRN_OK;
+  }
   if (lex) {
     if (lds > 64 * 1024) {
       (void)hipFuncSetAttribute(x3 ? (const void*)attn_lexicon_kernel<true> : (const void*)attn_lexicon_kernel<false>,
@@ -1368,11 +1483,28 @@ struct LexOperands {
   PtrArray word;
 };
 
+// the fusion entry points' model, as it arrives: the operands of mrn_ctc_beam_lm_decode_f32 (device arrays shared by the groups), the
+// proposals per row, a HOST array `fused` of `groups` device pointers
+struct LMOperands {
+  const void* keys;
+  const float* vals;
+  int64_t mask;
+  int max_probe;
+  const float *uni_logp, *uni_bow;
+  int C_lm;
+  float unk_logp;
+  int order;
+  float alpha, beta;
+  int top_n;
+  PtrArray fused;
+};
+
 // `groups` experts of identical geometry (B, T, D, S) and their own class counts in one launch per MAX_GROUPS experts.  Every limit is
-// checked for every group before the first launch.  trie: null, or the lexicon of the two lexicon entry points
+// checked for every group before the first launch.  trie: null, or the lexicon of the two lexicon entry points; model: null, or the
+// language model of the two fusion entry points
 static int beam_grouped(const char* who, bool x3, const DecodeOperands& o, int eos, int W, PtrArray scratch, int64_t scratch_floats,
                         PtrArray tokens, PtrArray length, PtrArray score, PtrArray logp, PtrArray path, PtrArray prob, int groups,
-                        int hidden, void* stream, const LexOperands* trie = nullptr) {
+                        int hidden, void* stream, const LexOperands* trie = nullptr, const LMOperands* model = nullptr) {
   const int B = o.B, T = o.T, D = o.D, S = o.S;
   MRN_CHECK_ARG(decode_arrays_given(o, x3) && scratch && tokens && length && score && logp && path && prob && groups >= 1,
                 "%s: null operand", who);
@@ -1390,6 +1522,26 @@ static int beam_grouped(const char* who, bool x3, const DecodeOperands& o, int e
     MRN_CHECK_ARG(nodes >= 1, "%s: a trie of nodes=%d (at least the root)", who, nodes);
     MRN_CHECK_ARG(depth >= 0 && depth <= S - 1, "%s: trie depth=%d outside 0 ... S - 1 = %d (the longest word and its end token take S steps)", who, depth, S - 1);
     for (int g = 0; g < groups; ++g) MRN_CHECK_ARG(B == 0 || word[g], "%s: null operand in group %d", who, g);
+  }
+  if (model) {
+    const LMOperands& m = *model;
+    MRN_CHECK_ARG(attn_tile_lds(x3, D, T, BEAM_LDS_EXTRA + LM_LDS_MORE) <= 160 * 1024,
+                  "%s: the whole context does not fit the LDS budget (D=%d T=%d)", who, D, T);
+    MRN_CHECK_ARG(m.top_n >= 1 && m.top_n <= BT, "%s: top_n=%d outside 1 ... %d", who, m.top_n, BT);
+    MRN_CHECK_ARG(m.order >= 1 && m.order <= 3, "%s: order %d outside 1 ... 3", who, m.order);
+    MRN_CHECK_ARG(m.C_lm >= 1 && m.C_lm <= CHAR_LM_MAX_C, "%s: C_lm=%d outside 1 ... %d", who, m.C_lm, CHAR_LM_MAX_C);
+    MRN_CHECK_ARG(m.mask >= 0 && m.mask < CHAR_LM_MAX_SLOTS && ((m.mask + 1) & m.mask) == 0,
+                  "%s: table mask %ld is not a power of two up to 2^26 less one", who, (long)m.mask);
+    MRN_CHECK_ARG(m.max_probe >= 0 && (int64_t)m.max_probe <= m.mask + 1, "%s: max_probe %d outside 0 ... %ld", who, m.max_probe,
+                  (long)(m.mask + 1));
+    MRN_CHECK_ARG(isfinite(m.unk_logp) && isfinite(m.alpha) && m.alpha >= 0.f && isfinite(m.beta),
+                  "%s: unk_logp %g, alpha %g (>= 0) and beta %g must be finite", who, (double)m.unk_logp, (double)m.alpha, (double)m.beta);
+    MRN_CHECK_ARG(m.keys && m.vals && m.uni_logp && m.uni_bow && m.fused, "%s: null model operand", who);
+    for (int g = 0; g < groups; ++g) {
+      MRN_CHECK_ARG(B == 0 || m.fused[g], "%s: null operand in group %d", who, g);
+      MRN_CHECK_ARG(o.num_class[g] <= CHAR_LM_MAX_C, "%s: num_class=%d in group %d above %d (classes are 16-bit fields of a context)", who,
+                    o.num_class[g], g, CHAR_LM_MAX_C);
+    }
   }
   const long tiles = ceil_div(B, BT / W);
   for (int g = 0; g < groups; ++g) {
@@ -1425,7 +1577,17 @@ static int beam_grouped(const char* who, bool x3, const DecodeOperands& o, int e
       lex = LexTrie{trie->child_off, trie->child_tok, trie->child_node, trie->word_of, {}, trie->nodes};
       for (int i = 0; i < n; ++i) lex.word[i] = (int32_t*)trie->word[g0 + i];
     }
-    const int rc = beam_launch(grp, trie ? &lex : nullptr, n, D, T, (hipStream_t)stream);
+    BeamLMParams lm;
+    if (model) {
+      const LMOperands& m = *model;
+      lm.m = CharLMTable{(const unsigned long long*)m.keys, (const float2*)m.vals, m.uni_logp, m.uni_bow, (unsigned)m.mask, m.max_probe,
+                         m.C_lm, m.order, m.unk_logp};
+      lm.alpha = m.alpha;
+      lm.beta = m.beta;
+      lm.n_prop = W > m.top_n ? W : m.top_n;          // N = min(16, max(W, top_n)): W and top_n are at most 16
+      for (int i = 0; i < MAX_GROUPS; ++i) lm.fused[i] = i < n ? (float*)m.fused[g0 + i] : nullptr;
+    }
+    const int rc = beam_launch(grp, trie ? &lex : nullptr, n, D, T, (hipStream_t)stream, model ? &lm : nullptr);
     if (rc) return rc;
   }
   return MRN_OK;
@@ -1491,6 +1653,42 @@ MRN_EXPORT int mrn_attn_lexicon_decode_x3_grouped(const void* const* Hb, const v
   const LexOperands trie{child_off, child_tok, child_node, word_of, nodes, depth, word};
   return beam_grouped("mrn_attn_lexicon_decode_x3_grouped", true, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
                       groups, hidden, stream, &trie);
+}
+
+// ---- beam search with a character n-gram model on the attention head: attn_beam_lm_kernel (include/mrn_attn_lm.h) ----
+MRN_EXPORT int mrn_attn_beam_lm_decode_grouped_f32(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                   const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                   const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                   const void* const* b_hh, const void* const* w_gen, const void* const* b_gen,
+                                                   const int* num_class, int eos, int W, int top_n, const void* lm_keys,
+                                                   const float* lm_vals, int64_t lm_mask, int lm_max_probe, const float* uni_logp,
+                                                   const float* uni_bow, int C_lm, float unk_logp, int order, float alpha, float beta,
+                                                   const void* const* scratch, int64_t scratch_floats, const void* const* tokens,
+                                                   const void* const* length, const void* const* score, const void* const* logp,
+                                                   const void* const* path, const void* const* prob, const void* const* fused, int groups,
+                                                   int B, int T, int D, int S, int hidden, void* stream) {
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, nullptr, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  const LMOperands model{lm_keys, lm_vals, lm_mask, lm_max_probe, uni_logp, uni_bow, C_lm, unk_logp, order, alpha, beta, top_n, fused};
+  return beam_grouped("mrn_attn_beam_lm_decode_grouped_f32", false, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path,
+                      prob, groups, hidden, stream, nullptr, &model);
+}
+
+MRN_EXPORT int mrn_attn_beam_lm_decode_x3_grouped(const void* const* Hb, const void* const* Hproj, const void* const* etab,
+                                                  const int64_t* start_token, const void* const* w_h2h, const void* const* b_h2h,
+                                                  const void* const* w_score, const void* const* w_ih_ctx, const void* const* w_hh,
+                                                  const void* const* w_inv, const void* const* b_hh, const void* const* w_gen,
+                                                  const void* const* b_gen, const int* num_class, int eos, int W, int top_n,
+                                                  const void* lm_keys, const float* lm_vals, int64_t lm_mask, int lm_max_probe,
+                                                  const float* uni_logp, const float* uni_bow, int C_lm, float unk_logp, int order,
+                                                  float alpha, float beta, const void* const* scratch, int64_t scratch_floats,
+                                                  const void* const* tokens, const void* const* length, const void* const* score,
+                                                  const void* const* logp, const void* const* path, const void* const* prob,
+                                                  const void* const* fused, int groups, int B, int T, int D, int S, int hidden,
+                                                  void* stream) {
+  const DecodeOperands o{Hb, Hproj, etab, start_token, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, w_inv, b_hh, w_gen, b_gen, num_class, B, T, D, S};
+  const LMOperands model{lm_keys, lm_vals, lm_mask, lm_max_probe, uni_logp, uni_bow, C_lm, unk_logp, order, alpha, beta, top_n, fused};
+  return beam_grouped("mrn_attn_beam_lm_decode_x3_grouped", true, o, eos, W, scratch, scratch_floats, tokens, length, score, logp, path, prob,
+                      groups, hidden, stream, nullptr, &model);
 }
 
 // ---- exact scoring of per-sample candidate words on the attention head: attn_score_kernel (include/mrn_attn_score.h) ----

@@ -18,10 +18,11 @@
 // Language-model fusion (mrn_ctc_beam_lm_decode_f32, include/mrn_ctc_lm.h) is the same body with LM = true: lane i < W also holds
 // e_prev, the class before e_last, and e_lm, the sum of the model's log-probabilities over the prefix; every lane looks up the model
 // for its own up-to-four candidates (at most three bounded probe sequences of 8-byte reads each into a read-only hash table,
-// mrn_amd/modules/char_lm.py), the selection ranks by total + alpha * lm' + beta * len' instead of the total, and after the last frame
+// char_lm.hpp), the selection ranks by total + alpha * lm' + beta * len' instead of the total, and after the last frame
 // W more rounds of wave_argmax order the entries by the key with the end-of-text term.  With LM = false nothing of that is compiled.
 #include <math.h>
 
+#include "char_lm.hpp"
 #include "common.hpp"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int BEAM_CPL = 4;                 // candidates per lane: 16 * (15 + 1
 constexpr int BEAM_ROWS = 4;                // samples (waves) per block at most
 constexpr int BEAM_LDS_BUDGET = 64 * 1024;  // per block: two blocks fit the 160 KiB of a CU at any T
 constexpr int BEAM_DROP_BYTES = BEAM_MAX_W * 16;
-constexpr int64_t BEAM_LM_MAX_SLOTS = (int64_t)1 << 26;  // slots of the language model's hash table
 
 // this wave's LDS writes are visible to its other lanes: a wave's LDS accesses complete in order, the fence keeps the compiler's order
 __device__ __forceinline__ void wave_sync() {
@@ -62,57 +62,11 @@ __device__ __forceinline__ void wave_argmax(float& v, int& q) {
   }
 }
 
-// the character n-gram model of modules/char_lm.py in its device form
-struct BeamLM {
-  const unsigned long long* keys;  // [mask + 1]: n << 60 | a << 32 | b << 16 | c, 0 = empty slot
-  const float2* vals;              // [mask + 1]: (logp, bow)
-  const float* uni_logp;           // [C_lm], entry 0 = end of text
-  const float* uni_bow;            // [C_lm]
+// the model (char_lm.hpp) with what the fused search adds: the weights and the key output
+struct BeamLM : CharLMTable {
   float* fused;                    // [B][W] out: the key the entries are ordered by
-  unsigned mask;
-  int max_probe, C_lm, order;
-  float unk_logp, alpha, beta;
+  float alpha, beta;
 };
-
-// the 64-bit mix of char_lm.py mix(): the splitmix64 finaliser
-__device__ __forceinline__ unsigned long long lm_mix(unsigned long long h) {
-  h ^= h >> 30;
-  h *= 0xBF58476D1CE4E5B9ull;
-  h ^= h >> 27;
-  h *= 0x94D049BB133111EBull;
-  h ^= h >> 31;
-  return h;
-}
-
-// bounded linear probe: at most max_probe slots, whatever the table holds
-__device__ __forceinline__ bool lm_find(const BeamLM& lm, unsigned long long key, float2& v) {
-  unsigned s = (unsigned)lm_mix(key) & lm.mask;
-  for (int p = 0; p < lm.max_probe; ++p) {
-    const unsigned long long k = lm.keys[s];
-    if (k == key) {
-      v = lm.vals[s];
-      return true;
-    }
-    if (k == 0ull) return false;
-    s = (s + 1u) & lm.mask;
-  }
-  return false;
-}
-
-// log p(c | a, b) by the back-off evaluation of char_lm.py CharLM.logp, float32 sums in its order; a, b, c in 0 .. 65534
-__device__ __forceinline__ float lm_logp(const BeamLM& lm, int a, int b, int c) {
-  const float uni = c < lm.C_lm ? lm.uni_logp[c] : lm.unk_logp;
-  if (lm.order == 1) return uni;
-  const unsigned long long kb = (unsigned long long)b << 16, kc = (unsigned long long)c;
-  float2 v;
-  float bo = 0.f;
-  if (lm.order == 3) {
-    if (lm_find(lm, 3ull << 60 | (unsigned long long)a << 32 | kb | kc, v)) return v.x;
-    if (lm_find(lm, 2ull << 60 | (unsigned long long)a << 16 | (unsigned long long)b, v)) bo = v.y;
-  }
-  if (lm_find(lm, 2ull << 60 | kb | kc, v)) return bo + v.x;
-  return bo + ((b < lm.C_lm ? lm.uni_bow[b] : 0.f) + uni);
-}
 
 template <bool LM>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(const float* __restrict__ logits, long sb, long st, int B, int T, int C, int W, int K,
@@ -445,8 +399,8 @@ MRN_EXPORT int mrn_ctc_beam_lm_decode_f32(const float* logits, int64_t stride_b,
   MRN_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W, "mrn_ctc_beam_lm_decode_f32: beam width %d outside 1..%d", W, BEAM_MAX_W);
   MRN_CHECK_ARG(K >= 1 && K <= BEAM_MAX_K, "mrn_ctc_beam_lm_decode_f32: cut-off %d outside 1..%d", K, BEAM_MAX_K);
   MRN_CHECK_ARG(order >= 1 && order <= 3, "mrn_ctc_beam_lm_decode_f32: order %d outside 1..3", order);
-  MRN_CHECK_ARG(C_lm >= 1 && C_lm <= BEAM_MAX_C, "mrn_ctc_beam_lm_decode_f32: C_lm = %d outside 1..%d", C_lm, BEAM_MAX_C);
-  MRN_CHECK_ARG(lm_mask >= 0 && lm_mask < BEAM_LM_MAX_SLOTS && ((lm_mask + 1) & lm_mask) == 0,
+  MRN_CHECK_ARG(C_lm >= 1 && C_lm <= CHAR_LM_MAX_C, "mrn_ctc_beam_lm_decode_f32: C_lm = %d outside 1..%d", C_lm, CHAR_LM_MAX_C);
+  MRN_CHECK_ARG(lm_mask >= 0 && lm_mask < CHAR_LM_MAX_SLOTS && ((lm_mask + 1) & lm_mask) == 0,
                 "mrn_ctc_beam_lm_decode_f32: table mask %ld is not a power of two up to 2^26 less one", (long)lm_mask);
   MRN_CHECK_ARG(lm_max_probe >= 0 && (int64_t)lm_max_probe <= lm_mask + 1, "mrn_ctc_beam_lm_decode_f32: max_probe %d outside 0..%ld",
                 lm_max_probe, (long)(lm_mask + 1));

@@ -44,7 +44,11 @@ lookup that has examined max_probe slots without a hit is a miss.  The hash is t
 
     h = key;  h ^= h >> 30;  h *= 0xBF58476D1CE4E5B9;  h ^= h >> 27;  h *= 0x94D049BB133111EB;  h ^= h >> 31      (mod 2^64)
 
-stated here (mix) and in mrn_amd/csrc/ctc_beam.hip (lm_mix), nowhere else.
+stated here (mix) and in mrn_amd/csrc/char_lm.hpp (lm_mix), the header both kernels that read the table include, nowhere else.
+
+On an attention head (AttnLabelConverter) the same holds with class 0 = [UNK] in the blank's place: encode_texts bans it, so it never
+occurs in a text and doubles as begin / end of text; [PAD], [SOS] and [EOS] never occur either and sit at the unigram floor
+(modules/decoding.py, "Language-model fusion on the attention head").
 """
 import numpy as np
 

@@ -56,6 +56,31 @@ sample, entries in descending score: tokens int32 [W][S] (eos behind the first e
 for an entry that never finished, -1 = dead slot), score [W] (-inf for a dead slot), logp [W][S] (the log-probability of each chosen
 token, 0 behind the first eos); and for the best entry path int64 [S] and prob [S] = exp(logp), 1.0 behind the first eos: the pair
 argmax_prob_lastdim hands the scorer.  With W = 1 this is greedy decoding.
+
+Language-model fusion on the attention head (opt-in: lm = a modules/char_lm.py CharLM over the head's classes, lm_weight alpha >= 0,
+lm_bonus beta finite, top_n; mrn_attn_beam_lm_decode_* runs it in float32 (attn_beam_lm_kernel), attn_beam_host(lm=) in float64).  An
+AttnLabelConverter's class 0 is [UNK], which no text contains (char_lm.encode_texts bans it), so 0 doubles as begin / end of text in
+the model exactly as the blank does on a CTC head; [PAD], [SOS] and [EOS] never occur in a text and sit at the unigram floor.  The
+beam search above with these differences:
+
+  state: an entry also carries the last two LM symbols (a, b), (0, 0) at the start = begin of text, its LM sum lm and its length len
+     in characters; acoustic = the score above;
+  LM symbol of a class: eos -> 0, the end of text; every other class -> itself;
+  LM term of a proposed class k behind (a, b): LM.logp(a, b, 0) for k = eos; unk_logp, flat, for k = 0; LM.logp(a, b, k) otherwise
+     (classes >= C_lm included).  After the step the context is (b, symbol(k)): a PREDICTED class 0 ([UNK]) therefore reads as begin
+     of text to its successors;
+  2'. a live unfinished entry proposes its N = min(16, max(W, top_n)) classes of largest LOGIT only (larger logit first, a tie to the
+     lower class, a NaN logit counts as -inf); a proposal has acoustic' = acoustic + lp[k] and
+     key = acoustic' + alpha * (lm + term) + beta * len' (evaluated left to right), len' = len + 1, len for eos.  A finished entry
+     proposes itself alone with its key unchanged: it already holds the end-of-text term;
+  3'. the W x N proposals of a sample are ranked by key, ties in (entry, class) order; rank < W with a key above -inf (a NaN key
+     counts as -inf) survives.
+
+score and logp stay acoustic, so prob stays a probability; one more output, fused [W], holds the key, and the entries come in
+descending fused (-inf for a dead slot).  With alpha = beta = 0 the key is the acoustic score and, because N >= W, the six outputs are
+the plain search's bit for bit -- up to one kind of rounding tie: if acoustic + lp of a proposal behind an entry's W-th rounds to the
+very float of one in front of it and its class is lower, the (entry, class) tie rule takes it where the plain search never saw it.  The margin then also covers the pruning boundary: for every live unfinished entry the gap between
+its N-th and (N + 1)-th logit, against one token's band.
 """
 import numpy as np
 
@@ -284,13 +309,109 @@ def _sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=False):
+ATTN_LM_MAX_PROPOSALS = 16       # N: the candidate planes of attn_beam_lm_kernel are [16][16]
+
+
+def attn_beam_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin=False, lm=None, lm_weight=0.0, lm_bonus=0.0,
+                   top_n=DEFAULT_BEAM_TOP_N):
     """float64 beam search on the attention head: sd = a state dict of modules/prediction.py Attention (tensors or arrays), batch_H
     [B][T][D] -> (tokens int32 [B][W][S], length int32 [B][W], score float64 [B][W], logp float64 [B][W][S], path int64 [B][S], prob
     float32 [B][S]): the outputs of ops.attn_beam_decode, for CPU tensors and as the kernel's yardstick.  Any width >= 1.
     want_margin adds margin float64 [B]: the smallest gap, over the steps, between neighbouring kept candidates and between the last
-    kept and the best dropped one, divided by the step's token count (a score of n tokens is known to n times a token's band)"""
-    return _attn_search_host("attn_beam_host", sd, batch_H, sos, eos, width, batch_max_length, None, want_margin)
+    kept and the best dropped one, divided by the step's token count (a score of n tokens is known to n times a token's band).
+    With lm (a char_lm.CharLM), lm_weight >= 0, a finite lm_bonus and top_n >= 1 the search is the fused one of the module docstring:
+    fused float64 [B][W] is a seventh output (in front of the margin), the entries come in descending fused, and the margin also
+    covers the pruning boundary (the gap between a live unfinished entry's N-th and (N + 1)-th logit, against one token's band)"""
+    if lm is None:
+        return _attn_search_host("attn_beam_host", sd, batch_H, sos, eos, width, batch_max_length, None, want_margin)
+    return _attn_fusion_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin, lm, lm_weight, lm_bonus, top_n)
+
+
+def attn_lm_proposals(width, top_n):
+    """N, the classes an unfinished entry proposes: min(16, max(W, top_n)), and never fewer than W (the host form takes any width)"""
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or top_n < 1:
+        raise ValueError(f"top_n must be an integer >= 1, got {top_n!r}")
+    return max(int(width), min(ATTN_LM_MAX_PROPOSALS, max(int(width), int(top_n))))
+
+
+def _attn_fusion_host(sd, batch_H, sos, eos, width, batch_max_length, want_margin, lm, lm_weight, lm_bonus, top_n):
+    """attn_beam_host with a language model: the fused search of the module docstring, sample by sample"""
+    W, S = int(width), int(batch_max_length) + 1
+    alpha, beta = check_lm_weights(lm_weight, lm_bonus)
+    w = {k: _f64(v) for k, v in sd.items()}
+    Hb = _f64(batch_H)
+    if Hb.ndim != 3 or W < 1 or S < 1:
+        raise ValueError(f"attn_beam_host needs batch_H [B][T][D], width >= 1 and batch_max_length >= 0, got {Hb.shape}, {W}, {S - 1}")
+    N = attn_lm_proposals(W, top_n)
+    B, T, D = Hb.shape
+    C, Hd = w["generator.weight"].shape
+    if not 0 <= eos < C:
+        raise ValueError(f"eos={eos} outside the {C} classes")
+    Hproj = Hb @ w["attention_cell.i2h.weight"].T
+    h, c = np.zeros((B, W, Hd)), np.zeros((B, W, Hd))
+    last = np.full((B, W), int(sos), dtype=np.int64)
+    score = np.full((B, W), -np.inf)
+    score[:, 0] = 0.0
+    key = score.copy()
+    ctx = np.zeros((B, W, 2), dtype=np.int64)
+    lms = np.zeros((B, W))
+    count = np.zeros((B, W), dtype=np.int64)
+    finished = np.zeros((B, W), dtype=bool)
+    tokens = np.full((B, W, S), eos, dtype=np.int32)
+    logp = np.zeros((B, W, S))
+    margin = np.full(B, np.inf)
+    classes = np.arange(C)
+    for s in range(S):
+        if not ((score > -np.inf) & ~finished).any():
+            break
+        tok = np.where((last >= C) | (last < 0), 0, last)
+        h2, c2, lp, x = _attn_cell_host(w, Hb, Hproj, h, c, tok, want_logits=True)
+        nxt = [np.empty_like(a) for a in (h, c, last, score, key, ctx, lms, count, finished, tokens, logp)]
+        for b in range(B):
+            props = []                  # (key, entry, class, acoustic, lp of the class, lm sum, context, length)
+            for i in range(W):
+                if not score[b, i] > -np.inf:
+                    continue
+                if finished[b, i]:
+                    props.append((key[b, i], i, eos, score[b, i], 0.0, lms[b, i], tuple(ctx[b, i]), count[b, i]))
+                    continue
+                ranked = np.lexsort((classes, -x[b, i]))[:N + 1]
+                if len(ranked) > N:
+                    with np.errstate(invalid="ignore"):
+                        gap = x[b, i, ranked[N - 1]] - x[b, i, ranked[N]]
+                    margin[b] = min(margin[b], gap if gap == gap else np.inf)
+                pa, pb = int(ctx[b, i, 0]), int(ctx[b, i, 1])
+                for k in map(int, ranked[:N]):
+                    term = lm.logp(pa, pb, 0) if k == eos else lm.unk_logp if k == 0 else lm.logp(pa, pb, k)
+                    acoustic = score[b, i] + lp[b, i, k]
+                    acoustic = acoustic if acoustic == acoustic else -np.inf
+                    total, n_chars = lms[b, i] + term, count[b, i] + (0 if k == eos else 1)
+                    with np.errstate(invalid="ignore"):
+                        kv = acoustic + alpha * total + beta * n_chars
+                    props.append((kv if kv == kv else -np.inf, i, k, acoustic, lp[b, i, k], total, (pb, 0 if k == eos else k), n_chars))
+            props.sort(key=lambda p: (-p[0], p[1], p[2]))
+            top = np.array([p[0] for p in props[:W + 1]] + [-np.inf] * (W + 1 - min(len(props), W + 1)))
+            with np.errstate(invalid="ignore"):
+                gaps = np.where(top[:W] > -np.inf, top[:W] - top[1:], np.inf)
+            margin[b] = min(margin[b], gaps.min() / (s + 1))
+            for q in range(W):
+                nh, nc, nlast, nscore, nkey, nctx, nlms, ncount, nfin, ntok, nlp = (a[b] for a in nxt)
+                if q < len(props) and props[q][0] > -np.inf:
+                    kv, i, k, acoustic, lpk, total, context, n_chars = props[q]
+                    nh[q], nc[q], nlast[q], nscore[q], nkey[q] = h2[b, i], c2[b, i], k, acoustic, kv
+                    nctx[q], nlms[q], ncount[q], nfin[q] = context, total, n_chars, k == eos
+                    ntok[q], nlp[q] = tokens[b, i], logp[b, i]
+                    ntok[q, s], nlp[q, s] = k, 0.0 if finished[b, i] else lpk
+                else:
+                    nh[q], nc[q], nlast[q], nscore[q], nkey[q] = 0.0, 0.0, eos, -np.inf, -np.inf
+                    nctx[q], nlms[q], ncount[q], nfin[q], ntok[q], nlp[q] = 0, 0.0, 0, False, eos, 0.0
+        h, c, last, score, key, ctx, lms, count, finished, tokens, logp = nxt
+    alive = score > -np.inf
+    is_eos = tokens == eos
+    length = np.where(is_eos.any(axis=2), is_eos.argmax(axis=2) + 1, S).astype(np.int32)
+    length[~alive] = -1
+    out = (tokens, length, score, logp, tokens[:, 0].astype(np.int64), np.exp(logp[:, 0]).astype(np.float32), key)
+    return out + (margin,) if want_margin else out
 
 
 def _attn_search_host(who, sd, batch_H, sos, eos, width, batch_max_length, trie, want_margin):
@@ -818,9 +939,10 @@ def check_word_table(lex_tokens, lex_len, cand, B, S):
     return N, Lmax, cand.shape[1]
 
 
-def _attn_cell_host(w, Hb, Hproj, h, c, tok):
+def _attn_cell_host(w, Hb, Hproj, h, c, tok, want_logits=False):
     """one step of the attention cell of modules/prediction.py in float64 on rows [B][R]: h, c [B][R][H], tok int [B][R] -> (h, c,
-    log-softmax of the generator [B][R][C] with a NaN logit counting as -inf) -- _attn_search_host's arithmetic in its order"""
+    log-softmax of the generator [B][R][C] with a NaN logit counting as -inf) -- _attn_search_host's arithmetic in its order.
+    want_logits: the logits (NaN as -inf) are a fourth output"""
     a = "attention_cell."
     hp = h @ w[a + "h2h.weight"].T + w[a + "h2h.bias"]
     e = np.tanh(Hproj[:, None] + hp[:, :, None, :]) @ w[a + "score.weight"][0]
@@ -837,7 +959,7 @@ def _attn_cell_host(w, Hb, Hproj, h, c, tok):
     peak = x.max(axis=2, keepdims=True)
     with np.errstate(invalid="ignore", divide="ignore"):
         lp = x - (peak + np.log(np.exp(x - peak).sum(axis=2, keepdims=True)))
-    return h2, c2, lp
+    return (h2, c2, lp, x) if want_logits else (h2, c2, lp)
 
 
 def rank_candidates(score_all, cand, n):
@@ -1066,9 +1188,47 @@ def attn_shortlist_request(attn_shortlist, prediction, is_train, attn_beam=None,
     return attn_shortlist[0], K, max_dist
 
 
+def attn_lm_options(opt, attn):
+    """(lm or None, lm_weight, lm_bonus, top_n) of an options object: opt.attn_lm is absent / None (off) or a char_lm.CharLM over the
+    attention head's classes, opt.lm_weight (default 0.5), opt.lm_bonus (default 0) and opt.beam_top_n (default 15) the keys opt.ctc_lm
+    reads.  The model fuses into the attention head's beam search, so on an attention head attn_lm without attn_decode='beam', or
+    together with attn_lexicon, candidates or lexicon_shortlist, is a ValueError; CTC heads ignore the option"""
+    from .char_lm import CharLM
+    lm = getattr(opt, "attn_lm", None)
+    if lm is None or not attn:
+        return None, DEFAULT_LM_WEIGHT, DEFAULT_LM_BONUS, DEFAULT_BEAM_TOP_N
+    if not isinstance(lm, CharLM):
+        raise ValueError(f"attn_lm must be a CharLM (modules/char_lm.py build_char_lm), got {type(lm).__name__}")
+    if getattr(opt, "attn_decode", "greedy") != "beam":
+        raise ValueError("attn_lm fuses into the attention head's beam search: set attn_decode='beam'")
+    for key in ("attn_lexicon", "candidates", "lexicon_shortlist"):
+        if getattr(opt, key, None) is not None:
+            raise ValueError(f"attn_lm and {key}: a closed-vocabulary decoder has no use for a language model, set one of them")
+    weights = check_lm_weights(getattr(opt, "lm_weight", DEFAULT_LM_WEIGHT), getattr(opt, "lm_bonus", DEFAULT_LM_BONUS))
+    return (lm,) + weights + (_positive_int(opt, "beam_top_n", DEFAULT_BEAM_TOP_N),)
+
+
+def attn_lm_request(attn_lm, attn_beam, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
+    """the (handle, weight, bonus, top_n) an evaluation forward fuses into its beam search, or None: attn_lm is set.  It stands beside
+    attn_beam: without a width, or together with a lexicon, candidate or shortlist search, it is an error"""
+    if attn_lm is None:
+        return None
+    if attn_beam is None:
+        raise ValueError("attn_lm fuses a language model into the beam search: pass attn_beam=<width> with it")
+    if attn_lexicon is not None or attn_candidates is not None or attn_shortlist is not None:
+        raise ValueError("attn_lm: a closed-vocabulary search (attn_lexicon, attn_candidates, attn_shortlist) has no use for a language model")
+    if not isinstance(attn_lm, tuple) or len(attn_lm) != 4:
+        raise ValueError(f"attn_lm must be (handle of ops.upload_char_lm, lm_weight, lm_bonus, top_n), got {attn_lm!r}")
+    handle, weight, bonus, top_n = attn_lm
+    if not hasattr(handle, "lm") or not hasattr(handle, "keys"):
+        raise ValueError(f"attn_lm: the first member must be the handle of ops.upload_char_lm, got {type(handle).__name__}")
+    attn_lm_proposals(1, top_n)
+    return (handle,) + check_lm_weights(weight, bonus) + (int(top_n),)
+
+
 # ---- one request record for the attention head's second decode -----------------------------------------------------------------------
-# The evaluation forwards of Model, DERNet and MRNNet resolve their four keywords (attn_beam, attn_lexicon, attn_candidates,
-# attn_shortlist) once, with attn_search_request; everything below them takes the record.
+# The evaluation forwards of Model, DERNet and MRNNet resolve their keywords (attn_beam, attn_lexicon, attn_candidates, attn_shortlist,
+# attn_lm) once, with attn_search_request; everything below them takes the record.
 ATTN_SEARCHES = ("beam", "lexicon", "candidates", "shortlist")
 # where (path, prob, word) stand in the output tuple of a kind's search: Attention.beam_search / lexicon_search / score_candidates and
 # the grouped ops of the same names; shortlist_search returns score_candidates' outputs in front of its table
@@ -1078,8 +1238,9 @@ _BEST_AT = {"beam": (4, 5, None), "lexicon": (4, 5, 6), **dict.fromkeys(("candid
 class AttnSearch(namedtuple("AttnSearch", "kind width trie cands words K max_dist", defaults=(None,) * 6)):
     """the second decode of an evaluation forward: kind is one of ATTN_SEARCHES; width and trie (an ops.TrieHandle; "lexicon" only) of a
     beam search, cands (an ops.CandidateHandle after with_cand) of "candidates", words (the handle of ops.upload_words), K and max_dist
-    of "shortlist".  Members a kind does not use are None"""
+    of "shortlist".  Members a kind does not use are None.  lm: None here; the language model of an AttnFusedSearch"""
     __slots__ = ()
+    lm = None
 
     @property
     def has_word(self):          # does the search name a word of a table (the forward's beam_word)
@@ -1090,10 +1251,37 @@ class AttnSearch(namedtuple("AttnSearch", "kind width trie cands words K max_dis
         return AttnSearch("candidates", cands=self.words.with_cand(cand, S))
 
 
-def attn_search_request(prediction, is_train, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
-    """the four keywords of an evaluation forward -> AttnSearch, or None where nothing is decoded a second time (no keyword set, a CTC
-    head, training, grad enabled).  Every check is one of the four *_request functions above, in this order: attn_lexicon without
-    attn_beam is an error whatever the head"""
+class AttnFusedSearch(AttnSearch):
+    """the "beam" request of a beam search fused with a language model: lm = (ops.CharLMHandle, lm_weight, lm_bonus, top_n) beside
+    the record's width.  Everything that takes an AttnSearch takes it; two requests are equal when record and model are.  A subclass
+    and not an eighth member of the record: tests/test_attn_search_cpu.py pins AttnSearch to its seven members.  _replace keeps the
+    model; _asdict and the hash are the record's (equal requests hash alike)"""
+
+    def __new__(cls, width, lm):
+        self = super().__new__(cls, "beam", width=width)
+        self.lm = lm
+        return self
+
+    def _replace(self, **kw):
+        lm = kw.pop("lm", self.lm)
+        new = AttnSearch._replace(self, **kw)
+        new.lm = lm
+        return new
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) and getattr(other, "lm", None) == self.lm
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = AttnSearch.__hash__
+
+
+def attn_search_request(prediction, is_train, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None, attn_lm=None):
+    """the keywords of an evaluation forward -> AttnSearch, or None where nothing is decoded a second time (no keyword set, a CTC
+    head, training, grad enabled).  Every check is one of the *_request functions above, attn_lm's first, then the four in this order:
+    attn_lexicon (or attn_lm) without attn_beam is an error whatever the head"""
+    fusion = attn_lm_request(attn_lm, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
     width = attn_beam_request(attn_beam, prediction, is_train)
     trie = attn_lexicon_request(attn_lexicon, attn_beam)
     cands = attn_candidates_request(attn_candidates, prediction, is_train, attn_beam)
@@ -1102,7 +1290,11 @@ def attn_search_request(prediction, is_train, attn_beam=None, attn_lexicon=None,
         return AttnSearch("shortlist", words=short[0], K=short[1], max_dist=short[2])
     if cands is not None:
         return AttnSearch("candidates", cands=cands)
-    return None if width is None else AttnSearch("beam" if trie is None else "lexicon", width=width, trie=trie)
+    if width is None:
+        return None
+    if fusion is not None:
+        return AttnFusedSearch(width, fusion)
+    return AttnSearch("beam" if trie is None else "lexicon", width=width, trie=trie)
 
 
 def best_of(kind, res):

@@ -758,7 +758,8 @@ class HeadsGroup(SequenceGroup):
     def run_search(self, req, feat, Hproj, start, operands):
         """the second decode (req: a decoding.AttnSearch of kind "beam", "lexicon" or "candidates", ending on ATTN_EOS) of all G attention
         experts in lock-step, on run_greedy's features, Hproj and operands -> (path int64 [G,B,S], prob [G,B,S], word int32 [G,B] or None)
-        of every expert's best entry.  ONE launch where every head takes the fused form: mrn_attn_beam_decode_*, mrn_attn_lexicon_decode_*
+        of every expert's best entry.  ONE launch where every head takes the fused form: mrn_attn_beam_decode_* (mrn_attn_beam_lm_decode_*
+        where the request carries a language model, one model for all experts), mrn_attn_lexicon_decode_*
         (one trie for all experts) or mrn_attn_score_candidates_* (every sample's candidate words scored exactly under all G experts);
         else every head's own Attention.search, stacked"""
         heads = [e.Prediction for e in self.experts]
@@ -766,7 +767,11 @@ class HeadsGroup(SequenceGroup):
         S = self.experts[0].opt.batch_max_length + 1
         cols, w_inv = operands
         common = (feat, Hproj, cols[0], start, *cols[1:9], heads[0].hidden_size, S, ATTN_EOS)
-        if req.kind == "beam":
+        if req.kind == "beam" and req.lm is not None:
+            lm, weight, bonus, top_n = req.lm
+            fused = all(h.beam_lm_fused(D, T, S, ATTN_EOS, req.width, lm, top_n) for h in heads)
+            grouped = lambda: ops.attn_beam_lm_decode_grouped(*common, req.width, lm, weight, bonus, min(top_n, 16), w_inv=w_inv)  # noqa: E731
+        elif req.kind == "beam":
             fused = all(h.beam_fused(D, T, S, ATTN_EOS, req.width) for h in heads)
             grouped = lambda: ops.attn_beam_decode_grouped(*common, req.width, w_inv=w_inv)  # noqa: E731
         elif req.kind == "lexicon":

@@ -124,7 +124,7 @@ class Model(nn.Module):
         self.Prediction.to(device)
 
     def forward(self, image, text=None, is_train=True, feature_out=None, predict_out=None, attn_beam=None, attn_lexicon=None,
-                attn_candidates=None, attn_shortlist=None, search=None):
+                attn_candidates=None, attn_shortlist=None, search=None, attn_lm=None):
         """attn_beam (a width; attention head, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry
         of a beam search on the same features (modules/decoding.py) -- one more launch, `predict` is still the greedy decoder's.
         attn_lexicon (the handle of ops.upload_trie, beside attn_beam): the search is walked along the lexicon's trie, and the dict
@@ -132,10 +132,12 @@ class Model(nn.Module):
         handle of ops.upload_words(...).with_cand(...); instead of attn_beam): every sample's candidate words are scored exactly
         (Attention.score_candidates) and the same three keys hold the best word's pair and its table index.  attn_shortlist ((the
         handle of ops.upload_words, K, max_dist or None); instead of both): the K words nearest to the greedy hypothesis (the arg-max
-        of `predict`) are scored exactly (Attention.shortlist_search) and the same three keys hold the best one.  search: the four as
-        the decoding.AttnSearch an MRNNet has resolved already"""
+        of `predict`) are scored exactly (Attention.shortlist_search) and the same three keys hold the best one.  attn_lm ((the handle of
+        ops.upload_char_lm, lm_weight, lm_bonus, top_n), beside attn_beam and nothing else): the beam search is fused with that
+        character n-gram model and beam_path / beam_prob are those of the best entry by the fused key.  search: the five as the
+        decoding.AttnSearch an MRNNet has resolved already"""
         if search is None:
-            search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
+            search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist, attn_lm)
         return self.heads(self.model.visual(image), text, is_train, feature_out, predict_out, search=search)
 
     def _second_decode(self, out, search, feat, text, logits):
@@ -319,10 +321,10 @@ class DERNet(Model):
         return head(feat if feat.is_contiguous() else feat.contiguous(), text, is_train, batch_max_length=self.opt.batch_max_length)
 
     def forward(self, image, text=None, is_train=True, frozen=None, attn_beam=None, attn_lexicon=None, attn_candidates=None,
-                attn_shortlist=None):
-        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon, attn_candidates, attn_shortlist: as
-        Model.forward (the main head's pair and beam_word)"""
-        search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
+                attn_shortlist=None, attn_lm=None):
+        """frozen: optional handle of frozen_prefetch(image) (same batch); attn_beam, attn_lexicon, attn_candidates, attn_shortlist,
+        attn_lm: as Model.forward (the main head's pair and beam_word)"""
+        search = attn_search_request(self.stages["Pred"], is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist, attn_lm)
         feat = self._features(image, frozen)
         logits = self._head(self.Prediction, feat, text, is_train)
         aux = self._head(self.aux_Prediction, feat[:, :, -self.out_dim:], text, is_train)
@@ -492,7 +494,7 @@ class MRNNet(nn.Module):
                 parts.append((first,) + best)
 
     def forward(self, image, cross=True, text=None, is_train=True, experts=None, attn_beam=None, attn_lexicon=None, attn_candidates=None,
-                attn_shortlist=None):
+                attn_shortlist=None, attn_lm=None):
         """`experts`: optional handle from experts_prefetch() -- the frozen experts' outputs for THIS batch, issued earlier.
         attn_beam (a width; attention experts, evaluation under no_grad): the dict also has beam_path / beam_prob [B,S], the best entry of
         a beam search (modules/decoding.py) of the expert the hard routing index picks for each sample, for cross=False of the newest
@@ -502,9 +504,11 @@ class MRNNet(nn.Module):
         candidate words are scored exactly under ALL experts in one grouped launch per heads group (a word with a class an expert lacks
         is dead for that expert) and the same three keys hold the routed expert's best word.  attn_shortlist ((the handle of
         ops.upload_words, K, max_dist or None); instead of both): the candidate table is the shortlist of the ROUTED expert's greedy
-        hypothesis (the arg-max of `logits`), one table per batch, scored under all experts like attn_candidates'"""
+        hypothesis (the arg-max of `logits`), one table per batch, scored under all experts like attn_candidates'.  attn_lm ((the handle
+        of ops.upload_char_lm, lm_weight, lm_bonus, top_n), beside attn_beam and nothing else): every expert's beam search is fused with
+        the one model in the grouped launch, and the pair is the routed expert's best entry by the fused key"""
         check_call(self.opt.Transformation, self.opt.FeatureExtraction, image.shape[0], image.shape[2], image.shape[3])
-        search = attn_search_request(self.opt.Prediction, is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist)
+        search = attn_search_request(self.opt.Prediction, is_train, attn_beam, attn_lexicon, attn_candidates, attn_shortlist, attn_lm)
         best = None
         if cross == False:  # noqa: E712  (learners pass cross positionally, exactly as in the reference)
             newest = self.model[-1](image, text, is_train, search=search)

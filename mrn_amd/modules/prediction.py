@@ -133,7 +133,8 @@ class Attention(nn.Module):
         score_candidates'"""
         from .decoding import ATTN_EOS, best_of
         if req.kind == "beam":
-            res = self.beam_search(batch_H, sos, ATTN_EOS, req.width, batch_max_length)
+            lm, weight, bonus, top_n = req.lm or (None, 0.0, 0.0, 15)
+            res = self.beam_search(batch_H, sos, ATTN_EOS, req.width, batch_max_length, lm=lm, lm_weight=weight, lm_bonus=bonus, top_n=top_n)
         elif req.kind == "lexicon":
             res = self.lexicon_search(batch_H, sos, ATTN_EOS, req.width, req.trie, batch_max_length)
         elif req.kind == "candidates":
@@ -146,15 +147,40 @@ class Attention(nn.Module):
         """does beam_search take the fused launch (mrn_attn_beam_decode_*): its limits, the LDS budget and MRN_ATTN_BEAM (read per call)"""
         return self._fused(S, eos) and ops.attn_beam_whole_context(D, T, width, self.x3_ok())
 
+    def beam_lm_fused(self, D, T, S, eos, width, lm, top_n):
+        """does beam_search(lm=) take the fused launch (mrn_attn_beam_lm_decode_*): beam_fused's limits with that launch's LDS sum, classes
+        that fit a 16-bit context, top_n >= 1 (the launch is given min(top_n, 16): N = min(16, max(W, top_n)) is the same search) and a
+        model the kernel takes"""
+        from .decoding import beam_lm_supported
+        return (self._fused(S, eos) and self.num_class <= 65535 and top_n >= 1 and beam_lm_supported(lm.lm)
+                and ops.attn_beam_lm_whole_context(D, T, width, self.x3_ok()))
+
     @torch.no_grad()
-    def beam_search(self, batch_H, sos, eos, width, batch_max_length=25):
+    def beam_search(self, batch_H, sos, eos, width, batch_max_length=25, lm=None, lm_weight=0.0, lm_bonus=0.0, top_n=15):
         """beam search of width `width` (modules/decoding.py states the algorithm): batch_H [B,T,D], sos an int or a device int64
         tensor whose first element is the start token -> (tokens int32 [B,W,S], length int32 [B,W], score [B,W], logp [B,W,S],
         path int64 [B,S], prob [B,S]), entries in descending score.  One launch where the kernel's limits and the LDS budget allow,
-        otherwise (or under MRN_ATTN_BEAM=stepwise) the step loop of forward() on the B * W-row batch.  Inference only (no_grad)"""
+        otherwise (or under MRN_ATTN_BEAM=stepwise) the step loop of forward() on the B * W-row batch.  Inference only (no_grad).
+        lm (the handle of ops.upload_char_lm; lm_weight >= 0, lm_bonus, top_n >= 1): the search fused with that character n-gram model
+        -> the six outputs with the entries in descending fused key and fused [B,W], that key; score and logp stay acoustic.  One
+        launch where beam_lm_fused says so; CPU tensors, calls beyond the launch's limits and MRN_ATTN_BEAM=stepwise take
+        decoding.attn_beam_host(lm=) in float64: there is no device step loop with a model"""
         B, T, D = batch_H.shape
         start, batch_H, Hproj, S, eos = self._search_operands("beam_search", batch_H, sos, eos, batch_max_length, width)
         W = int(width)
+        if lm is not None:
+            from .decoding import attn_beam_host, attn_lm_proposals, check_lm_weights
+            if not isinstance(lm, ops.CharLMHandle):
+                raise ValueError(f"beam_search needs the handle of ops.upload_char_lm, got {type(lm).__name__}")
+            lm_weight, lm_bonus = check_lm_weights(lm_weight, lm_bonus)
+            attn_lm_proposals(W, top_n)
+            if batch_H.is_cuda and self.beam_lm_fused(D, T, S, eos, W, lm, int(top_n)):
+                etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
+                return ops.attn_beam_lm_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,
+                                               self.hidden_size, S, eos, W, lm, lm_weight, lm_bonus, min(int(top_n), 16), w_inv=w_inv)
+            res = _host_result(attn_beam_host(self.state_dict(), batch_H, int(start[0]), eos, W, S - 1, lm=lm.lm, lm_weight=lm_weight,
+                                              lm_bonus=lm_bonus, top_n=int(top_n)))
+            return tuple(r.to(batch_H.device) for r in res)
         if self.beam_fused(D, T, S, eos, W):
             etab, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen, w_inv = self.greedy_args()
             return ops.attn_beam_decode(batch_H, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih_ctx, w_hh, b_hh, w_gen, b_gen,

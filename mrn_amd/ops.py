@@ -1539,9 +1539,11 @@ def attn_beam_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih
     return _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, None)
 
 
-def _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, trie):
-    """attn_beam_decode_grouped (trie None) and attn_lexicon_decode_grouped (a TrieHandle: the trie operands go in behind W, the word
-    output behind prob)"""
+def _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, trie,
+                       fusion=None):
+    """attn_beam_decode_grouped (trie None), attn_lexicon_decode_grouped (a TrieHandle: the trie operands go in behind W, the word
+    output behind prob) and attn_beam_lm_decode_grouped (fusion = (CharLMHandle, alpha, beta, top_n): top_n and the model operands go in
+    behind W, the fused output behind prob)"""
     import ctypes
     _chk(Hb, Hproj)
     G, B, T, D = Hb.shape
@@ -1570,7 +1572,16 @@ def _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh
             raise ValueError("attn_lexicon_decode needs the handle of upload_trie on the device of the features")
         lex = (_p(trie.child_off), _p(trie.child_tok), _p(trie.child_node), _p(trie.word_of), trie.nodes, trie.depth)
         word = (torch.empty(G, B, Wd, device=dev, dtype=torch.int32),)
-    _x3_call("attn_beam_decode" if trie is None else "attn_lexicon_decode", True, w_inv,
+    stem = "attn_beam_decode" if trie is None else "attn_lexicon_decode"
+    if fusion is not None:
+        lm, alpha, beta, top_n = fusion
+        if not isinstance(lm, CharLMHandle) or lm.keys.device != dev:
+            raise ValueError("attn_beam_lm_decode needs the handle of upload_char_lm on the device of the features")
+        stem = "attn_beam_lm_decode"
+        lex = (int(top_n), _p(lm.keys), _p(lm.vals), lm.size - 1, lm.max_probe, _p(lm.uni_logp), _p(lm.uni_bow), lm.C_lm, lm.unk_logp,
+               lm.order, alpha, beta)
+        word = (torch.empty(G, B, Wd, device=dev, dtype=torch.float32),)
+    _x3_call(stem, True, w_inv,
              _decode_operands(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh),
              (_ptrs(b_hh), _ptrs(w_gen), _ptrs(b_gen), (ctypes.c_int * G)(*classes), int(eos), W, *lex, _ptrs(scratch), per,
               *map(_ptrs, outs + word), G, B, T, D, S, hidden, _stream()))
@@ -1594,6 +1605,43 @@ def attn_lexicon_whole_context(D, T, W, x3=None):
     (Attention.lexicon_search)"""
     x3 = DECODER_X3 if x3 is None else x3
     return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and _attn_tile_lds(D, T, x3, ATTN_LEXICON_LDS_EXTRA) <= 160 * 1024
+
+
+ATTN_BEAM_LM_LDS_EXTRA = ATTN_BEAM_LDS_EXTRA + 4 * (8 * 16 + 2 * 16 * 16)      # attn_beam_lm_kernel: + eight state rows, the key and LM-sum planes
+
+
+def attn_beam_lm_whole_context(D, T, W, x3=None):
+    """attn_beam_whole_context for the launch with a language model (csrc/attn_decode.hip beam_launch / beam_grouped with a model): the same
+    sum with ATTN_BEAM_LM_LDS_EXTRA, 2560 bytes more.  There is no chunked form and no device step loop with a model: what does not fit
+    takes the float64 host form (Attention.beam_search(lm=))"""
+    x3 = DECODER_X3 if x3 is None else x3
+    return 1 <= W <= 16 and D > 0 and D % (32 if x3 else 16) == 0 and _attn_tile_lds(D, T, x3, ATTN_BEAM_LM_LDS_EXTRA) <= 160 * 1024
+
+
+def attn_beam_lm_decode_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width,
+                                lm=None, lm_weight=0.0, lm_bonus=0.0, top_n=15, w_inv=None):
+    """beam search on the attention head fused with a character n-gram model, for G experts of one geometry in one launch (per eight
+    experts; include/mrn_attn_lm.h): the operands of attn_beam_decode_grouped, lm = a CharLMHandle (upload_char_lm) on the device of the
+    features, one model for all experts; an unfinished entry proposes its min(16, max(width, top_n)) best classes, and the proposals are
+    ranked by score + lm_weight * log p_lm + lm_bonus * length (modules/decoding.py) -> the six outputs of attn_beam_decode_grouped with
+    the entries in descending fused key, and fused fp32 [G,B,W], that key; score and logp stay acoustic.  lm_weight < 0 or a non-finite
+    weight is a ValueError.  The limits are the caller's to keep (attn_beam_lm_whole_context, S <= 512, 2 <= classes <= 65535, 1 <= top_n
+    <= 16, hidden 256): outside them the call is an error"""
+    from .modules.decoding import check_lm_weights
+    if lm is None:
+        raise ValueError("attn_beam_lm_decode needs the handle of upload_char_lm, got None")
+    alpha, beta = check_lm_weights(lm_weight, lm_bonus)
+    return _attn_beam_grouped(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, w_inv, None,
+                              fusion=(lm, alpha, beta, top_n))
+
+
+def attn_beam_lm_decode(Hb, Hproj, etab, start, w_h2h, b_h2h, w_score, w_ih, w_hh, b_hh, w_gen, b_gen, hidden, S, eos, width, lm=None,
+                        lm_weight=0.0, lm_bonus=0.0, top_n=15, w_inv=None):
+    """attn_beam_lm_decode_grouped for one expert (G = 1) -> the seven outputs without the expert dimension"""
+    res = attn_beam_lm_decode_grouped(Hb.unsqueeze(0), Hproj.unsqueeze(0), [etab], start, [w_h2h], [b_h2h], [w_score], [w_ih], [w_hh],
+                                      [b_hh], [w_gen], [b_gen], hidden, S, eos, width, lm, lm_weight, lm_bonus, top_n,
+                                      w_inv=None if w_inv is None else [w_inv])
+    return tuple(r[0] for r in res)
 
 
 class TrieHandle:
@@ -2043,8 +2091,9 @@ def greedy_score(idx, prob, label, label_len, canon, mode, eos=0):
 
 
 class CharLMHandle:
-    """a checked character n-gram model on a device (upload_char_lm): the hash table (keys as int64 bit patterns [size], values fp32
-    [size,2]), the dense unigram arrays fp32 [C_lm], the scalars the kernel takes, and the host model for CPU tensors"""
+    """a checked character n-gram model on a device (upload_char_lm; the CTC beam search and the attention head's take the same handle):
+    the hash table (keys as int64 bit patterns [size], values fp32 [size,2]), the dense unigram arrays fp32 [C_lm], the scalars the
+    kernel takes, and the host model for CPU tensors"""
 
     def __init__(self, lm, device):
         import numpy as np

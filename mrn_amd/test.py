@@ -35,6 +35,15 @@ the per-step arg-max and its probability.  The loss is still computed on the gre
 drops the last character" quirk and the returned strings are the code above, unchanged: the confidence is then the probability of
 the kept tokens of the best entry.
 
+opt.attn_lm = a CharLM over the attention head's classes (build_char_lm on the AttnLabelConverter; absent or None: as above, bit for
+bit; CTC heads ignore it, as the attention head ignores ctc_lm) fuses a character n-gram model into that beam search: an entry proposes
+its min(16, max(beam_width, opt.beam_top_n)) best classes and the proposals are ranked by log p + opt.lm_weight * log p_lm +
+opt.lm_bonus * length (the keys ctc_lm reads; modules/decoding.py), one mrn_attn_beam_lm_decode_* launch per heads group with the model
+checked and uploaded once per call (attn_lm=(handle, weight, bonus, top_n) beside attn_beam on the evaluation forward), or the
+float64 host form where the launch does not take the batch.  The best entry by the fused key goes to the unchanged scorer, and its
+confidence is still the probability of its kept tokens.  The option is read only with attn_decode = "beam" on an attention head:
+attn_lm without it, or together with attn_lexicon, candidates or lexicon_shortlist, is an error.
+
 opt.lexicon = a sequence of words (absent or None: as above, bit for bit; the attention head ignores it: opt.attn_lexicon below is its
 counterpart there) decodes a CTC head to the
 lexicon word of largest log p(word | image), the exact CTC forward score of every (sample, word) pair (modules/decoding.py): the words
@@ -104,12 +113,14 @@ def _search_option(shortlist, candidates, lexicon=False):
     return "lexicon_shortlist" if shortlist else "candidates" if candidates else "attn_lexicon" if lexicon else "attn_decode='beam'"
 
 
-def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None):
+def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexicon=None, attn_candidates=None, attn_shortlist=None,
+             attn_lm=None):
     """the reference's call patterns (test.py:163-201): "FF" = newest expert, "TF" = routed ensemble, else a plain Model.
     attn_beam (a width, attention heads only): -> (logits, (beam path, beam probabilities)) instead of the logits; attn_lexicon (a
     trie handle beside it): the pair of the lexicon-constrained search; attn_candidates (a candidate handle instead of both): the pair
     of the batch's exact candidate scoring; attn_shortlist ((word handle, K, max distance) instead of all three): the pair of the best
-    word of the greedy hypothesis' shortlist"""
+    word of the greedy hypothesis' shortlist; attn_lm ((model handle, weight, bonus, top_n) beside attn_beam alone): the pair of the
+    beam search fused with that language model"""
     if "CTC" in opt.Prediction:
         if val_choose == "FF":
             out = model(image, cross=False, is_train=False)
@@ -120,7 +131,7 @@ def _forward(model, image, opt, converter, val_choose, attn_beam=None, attn_lexi
     else:
         sos = torch.full((image.size(0),), converter.dict["[SOS]"], dtype=torch.long, device=image.device)
         kw = {k: v for k, v in (("attn_beam", attn_beam), ("attn_lexicon", attn_lexicon), ("attn_candidates", attn_candidates),
-                                ("attn_shortlist", attn_shortlist)) if v is not None}
+                                ("attn_shortlist", attn_shortlist), ("attn_lm", attn_lm)) if v is not None}
         if val_choose == "FF":
             out = model(image, cross=False, text=sos, is_train=False, **kw)
         elif val_choose == "TF":
@@ -214,6 +225,19 @@ class _BeamLM:
                                        self.bonus)[3:5]
         path, prob = D.ctc_beam_host(preds.detach().cpu().numpy(), width, top_n, self.lm, self.weight, self.bonus)[3:5]
         return torch.from_numpy(path).to(preds.device), torch.from_numpy(prob).to(preds.device)
+
+
+class _AttnLM:
+    """opt.attn_lm with its weights for one validation() call; the model is checked and uploaded when the first batch needs it"""
+
+    def __init__(self, lm, weight, bonus, top_n):
+        self.lm, self.weight, self.bonus, self.top_n, self.handle = lm, weight, bonus, top_n, None
+
+    def on(self, device):
+        """the attn_lm= of the evaluation forward"""
+        if self.handle is None:
+            self.handle = ops.upload_char_lm(self.lm, device)
+        return self.handle, self.weight, self.bonus, self.top_n
 
 
 class _Lexicon:
@@ -342,6 +366,8 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
     lexicon = _Lexicon(converter, lexicon_words, lexicon_n, shortlist) if lexicon_words is not None and not attn else None
     ctc_lm, lm_weight, lm_bonus = D.lm_options(opt, attn)
     fusion = _BeamLM(ctc_lm, lm_weight, lm_bonus) if ctc_lm is not None else None
+    attn_lm = D.attn_lm_options(opt, attn)
+    attn_fusion = _AttnLM(*attn_lm) if attn_lm[0] is not None else None
     cand_fn, cand_n = D.candidates_options(opt)
     candidates = None
     if cand_fn is not None:
@@ -360,7 +386,8 @@ def validation(model, criterion, evaluation_loader, converter, opt, val_choose="
         attn_cands = candidates.on(image.device, labels) if attn and candidates is not None else None
         preds = _forward(model, image, opt, converter, val_choose, attn_beam=attn_beam,
                          attn_lexicon=None if attn_lexicon is None else attn_lexicon.on(image.device), attn_candidates=attn_cands,
-                         attn_shortlist=None if attn_shortlist is None else attn_shortlist.on(image.device))
+                         attn_shortlist=None if attn_shortlist is None else attn_shortlist.on(image.device),
+                         attn_lm=None if attn_fusion is None else attn_fusion.on(image.device))
         if attn_beam is not None or attn_cands is not None or attn_shortlist is not None:
             preds, beam_pair = preds
         if image.is_cuda:
